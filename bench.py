@@ -1,22 +1,31 @@
 #!/usr/bin/env python
 """Benchmark of the ETDRK4 hot path on MI355X (contract: task statement, section 4).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 One "step" = one full ETDRK4 time step (4 stages; 32 fused 2-D transforms + in-step budgets) of CoupledModel 4096^2
 fp64 (BASELINE.json configs[2]: LambDipole q, uniform phi, filter on), state resident in HBM.  Prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the line; its `roofline` is the whole step's canonical bytes
+ over the measured step time.  Everything that takes passes of its own -- the per-kernel-class table and the
+dominant class's roofline, the stream-copy peak, the exchange-stream pass and the replica / single-GPU comparisons of the
+slab modes, the CPU baseline -- runs only with --full, as described below.
+--dump-outputs DIR: after the timed steps, the state the timed path left (q; phi as real and imaginary parts; the budget
+increments of the single-context path) as DIR/<name>.npy in float64; a field with more points than its share of 48 MB is
+written as a fixed sample (seeded flat indices, the same in every run).  The inputs are deterministic: two builds of the
+project can be compared output for output with the same arguments.
+
 * `value` = K steps / wall time of the region bracketed by barrier + synchronize on both sides (max over ranks).
   The K steps are issued as 5 blocks with a HIP event between blocks (no synchronisation inside the region):
   `blocks_ms_per_step` / `median_block_steps_per_s` are SURVEY 8d's "median of 5".
-* `roofline` describes the DOMINANT kernel class (largest total time among all six classes in an untimed pass with every
+* with --full, `roofline` describes the DOMINANT kernel class (largest total time among all six classes in an untimed pass with every
   launch bracketed by HIP events on the context's stream); INSIDE the timed region every 7th launch of that class is
   bracketed again (`--region-stride`; an event pair costs the stream ~9 us: all 44 launches of a step 4.6 % of it, all 20 of
   the dominant class ~1 %, and 10 % of a rank's step on eight slab ranks; 7 is coprime with the 20 launches of a step, so every
   position is sampled equally often), and achieved = algorithmic bytes per launch / the average duration of those launches.  `traffic` = HBM bytes per launch from the committed rocprofv3 PMC summary, used
   only if that summary was taken from the very sources that are running (sha256 of niwqg_amd/csrc + include/ stamped
   into it), else null.  `peak_measured_copy` = a 1r + 1w stream copy timed in the untimed part of the same run.
-* `cpu_baseline` times the numpy oracle in its reference-faithful mode (104 c2c numpy.fft transforms per step, one thread)
+* with --full, `cpu_baseline` times the numpy oracle in its reference-faithful mode (104 c2c numpy.fft transforms per step, one thread)
   AT THE TARGET GRID in this run: one `_step_etdrk4` at 4096^2 (about 60 s; `--cpu-baseline-nx 2048` for a shorter, scaled
   sample).  `value` is always this run's own number; the round-2 recording rides along under its own key.
 With --gpus N > 1 and no WORLD_SIZE in the environment the script starts N ranks itself (torch.distributed.run, child
@@ -103,6 +112,40 @@ def measured_traffic(symbol):
     if n:
         per = tot / n
     return per, step, "committed profile of these sources: " + d.get("note", "")[:120]
+
+
+DUMP_BYTES = 48 << 20            # --dump-outputs: at most this much in all (float64), fixed samples of larger fields
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: `arrays` (name -> host array) as d/<name>.npy in float64, complex ones as <name>_re / <name>_im.  A field
+    with more points than its share of DUMP_BYTES is written as a fixed sample: sorted flat indices from default_rng(0), the same
+    for every field of the same size and in every run."""
+    parts = []
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if np.iscomplexobj(a):
+            parts += [(name + "_re", a.real), (name + "_im", a.imag)]
+        else:
+            parts.append((name, a))
+    cap = DUMP_BYTES // 8 // max(len(parts), 1)
+    os.makedirs(d, exist_ok=True)
+    for name, a in parts:
+        flat = np.ravel(a)
+        if flat.size > cap:
+            flat = flat[np.sort(np.random.default_rng(0).choice(flat.size, cap, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(flat, dtype=np.float64))
+
+
+def ctx_outputs(ctx, model):
+    """what a caller of the single-context step receives: the physical fields of the new state and the budget increments"""
+    from niwqg_amd import _lib
+    out = {"q": ctx.field(_lib.F_Q)}
+    if model != "qg":
+        out["phi"] = ctx.field(_lib.F_PHI)
+    if ctx.budgets_enabled:
+        out["budget_increments"] = np.array(ctx.take_budget_increments())
+    return out
 
 
 def c3_kwargs(nx, model):
@@ -344,6 +387,8 @@ def bench_ensemble(args, grp, rank, world, local_rank):
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     sps, wall = aggregate_throughput(grp, args.steps * len(ens.members), wall)
+    if rank == 0 and args.dump_outputs:                    # this rank's members
+        dump_outputs(args.dump_outputs, {"%s_member%d" % (f, j): getattr(m, f) for j, m in zip(ens.ids, ens.members) for f in ("q", "phi")})
     if rank == 0:
         npts = float(nx) ** 2
         print(json.dumps({
@@ -379,6 +424,8 @@ def bench_any_size(args, m, grp, rank, world):
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     sps, wall = aggregate_throughput(grp, args.steps, wall)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {f: getattr(m, f) for f in (("q",) if args.model == "qg" else ("q", "phi"))})
     if rank == 0:
         npts = float(args.nx) ** 2
         step_bytes = CANONICAL_B_PER_PT_STEP[args.model] * npts
@@ -452,6 +499,11 @@ def main():
                     "dominant kernel class with HIP events (1 = every launch, as rounds 1-3 did)")
     ap.add_argument("--replicas", action="store_true", help="with --gpus N > 1: N independent replicas instead of one "
                                                             "slab-decomposed simulation")
+    ap.add_argument("--full", action="store_true", help="also measure what takes passes of its own: the per-kernel-class table and "
+                    "the dominant class's roofline, the stream-copy peak, the slab modes' exchange / replica / single-GPU figures, "
+                    "the CPU baseline (a plain run: set-up, warm-up, the timed steps, the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write the state they left as "
+                    "DIR/<name>.npy (float64; fixed seeded samples of fields larger than their share of 48 MB)")
     args = ap.parse_args()
 
     env_world = os.environ.get("WORLD_SIZE")
@@ -541,7 +593,8 @@ def main():
     # roofline fractions; untimed part of the run
     copy_gbs = None
     try:
-        copy_gbs = ctx.stream_copy_gbs(512 << 20, 5) if hasattr(ctx, "stream_copy_gbs") else _lib_copy(ctx)
+        if args.full:
+            copy_gbs = ctx.stream_copy_gbs(512 << 20, 5) if hasattr(ctx, "stream_copy_gbs") else _lib_copy(ctx)
     except Exception as e:                                  # pragma: no cover - e.g. not enough free memory for 1 GiB
         sys.stderr.write("bench.py: stream-copy measurement skipped (%s)\n" % e)
     watchdog("timed region")
@@ -563,7 +616,8 @@ def main():
     # class is dominant), then INSIDE the timed region only the launches of that dominant class are bracketed: the roofline's
     # kernel is measured live over the timed region (20 of the 44 launches of a step at most); small grids -- everything in
     # a separate pass right after the timed region.
-    events_in_region = args.nx >= 4096
+    # (all of it only with --full: a plain run brackets nothing but the five blocks)
+    events_in_region = args.full and args.nx >= 4096
     classes_all, ksteps_all = None, 0
     if events_in_region:
         ksteps_all = min(args.steps, 5)
@@ -580,7 +634,7 @@ def main():
         # launches per stage / 20 per step of that class, so every position of the step is sampled equally often.
         ctx.profile_stride(args.region_stride)
     xt = None
-    if sim is not None:
+    if sim is not None and args.full:
         # the exchange stream's own time (two event records per exchange) is taken in a short UNTIMED pass, not in the region
         sim.counters(reset=2)
         advance(min(args.steps, 5))
@@ -597,17 +651,30 @@ def main():
     wall = time.perf_counter() - t0
     block_ms = [ctx.event_elapsed(i, i + 1) / nb for i, nb in enumerate(blocks)]
     dev_ms = ctx.event_elapsed(0, NBLK)
-    cnt = sim.counters() if sim is not None else None
+    cnt = sim.counters() if (sim is not None and args.full) else None
+    if args.dump_outputs:                                   # the state the timed steps left, before anything steps on
+        if sim is not None:                                 # (a collective with more than one rank: every rank gathers; --rank-of: the one rank's rows)
+            from niwqg_amd import _lib
+            outs = {"q": sim.gather_rows(_lib.F_Q)}
+            if phys_model != "qg":
+                outs["phi"] = sim.gather_rows(_lib.F_PHI)
+        else:
+            outs = ctx_outputs(ctx, phys_model)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outs)
+        del outs
     ksteps = args.steps
-    if not events_in_region:
+    classes = None
+    if args.full and not events_in_region:
         ksteps = max(1, min(args.steps, 20))
         ctx.profile_enable(-2)
         advance(ksteps)
         ctx.profile_read_all()                              # first pass creates the events, second one is read
         advance(ksteps)
-    classes = ctx.profile_read_all()
-    ctx.profile_enable(-1)
-    ctx.profile_stride(1)
+    if args.full:
+        classes = ctx.profile_read_all()
+        ctx.profile_enable(-1)
+        ctx.profile_stride(1)
     dom_timed = None
     if events_in_region:                                    # `classes` holds the dominant class over the timed region only
         dom_timed = (dom_class, classes[dom_class])
@@ -620,7 +687,7 @@ def main():
         sps, wall = aggregate_throughput(grp, args.steps, wall)   # all ranks' steps / max-over-ranks time
 
     extra = {}
-    if sim is not None:
+    if sim is not None and args.full:
         nst = max(cnt["steps"], 1)
         # rank 0's step, taken apart with HIP events on the two streams: kernels on the compute stream (every launch of the
         # six classes bracketed), the rest of the compute stream's time = it waited for an exchange (or a launch gap), and
@@ -650,7 +717,7 @@ def main():
             extra["replicas_aggregate_steps_per_s"] = aggregate_throughput(grp, args.steps, time.perf_counter() - t1)[0]
             del m2
 
-    if sim is not None and args.rank_of and args.rank_only:
+    if sim is not None and args.rank_of and (args.rank_only or not args.full):
         extra.update(rank_of=args.rank_of, rank_compute_ms_per_step=dev_ms / args.steps)
     elif sim is not None and args.rank_of:
         # the single-GPU step on the same box in the same run: what the rank's compute is held against (gate: <= 1.15 x step / P)
@@ -672,23 +739,59 @@ def main():
     if rank == 0:
         npts = float(args.nx) ** 2
         share = (args.rank_of or peers_n or world) if sim is not None else 1     # a slab rank's launch covers 1/P of the grid
-        table = KERNEL_B_PER_PT[args.model]
-        cands = [k for k in classes if k in table and classes[k][0] > 0]
-        dom = max(cands, key=lambda k: classes[k][1])
-        launches, kms = classes[dom]
-        if dom_timed is not None and dom_timed[0] in table and dom_timed[1][0] > 0:
-            dom, (launches, kms) = dom_timed                # measured live inside the timed region
-        k_ms = kms / launches
-        k_bytes = table[dom] * npts / share
-        achieved = k_bytes / (k_ms * 1e-3) / 1e9
         step_bytes = CANONICAL_B_PER_PT_STEP[args.model] * npts
-        design_bytes = sum(table[k] * npts / share * classes[k][0] for k in cands) / ksteps * share
-        traffic, pmc_step, pmc_note = (None, None, "PMC summary is for the default workload only")
-        if sim is None and args.nx == 4096 and args.model == "coupled" and ctx.budgets_enabled:
-            traffic, pmc_step, pmc_note = measured_traffic(KERNEL_SYMBOL[dom])
-        real_bytes = pmc_step if pmc_step else design_bytes
         s_per_step = wall / args.steps
         peak = HBM_PEAK_GBS * share
+        if args.full:
+            table = KERNEL_B_PER_PT[args.model]
+            cands = [k for k in classes if k in table and classes[k][0] > 0]
+            dom = max(cands, key=lambda k: classes[k][1])
+            launches, kms = classes[dom]
+            if dom_timed is not None and dom_timed[0] in table and dom_timed[1][0] > 0:
+                dom, (launches, kms) = dom_timed                # measured live inside the timed region
+            k_ms = kms / launches
+            k_bytes = table[dom] * npts / share
+            achieved = k_bytes / (k_ms * 1e-3) / 1e9
+            design_bytes = sum(table[k] * npts / share * classes[k][0] for k in cands) / ksteps * share
+            traffic, pmc_step, pmc_note = (None, None, "PMC summary is for the default workload only")
+            if sim is None and args.nx == 4096 and args.model == "coupled" and ctx.budgets_enabled:
+                traffic, pmc_step, pmc_note = measured_traffic(KERNEL_SYMBOL[dom])
+            real_bytes = pmc_step if pmc_step else design_bytes
+            roofline = {"bound": "hbm", "kernel": KERNEL_SYMBOL[dom], "achieved": achieved, "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": pmc_note,
+                        "launches": launches, "avg_launch_ms": k_ms, "algorithmic_bytes_per_launch": k_bytes,
+                        "kernel_events": ("every %d-th launch of the dominant class bracketed inside the timed region (%d launches sampled, all "
+                                          "positions of the step equally often); per-class table from an untimed pass of %d steps right before "
+                                          "it (an event pair costs the stream ~9 us: all six classes in the region 4.6 %% of the step, all launches "
+                                          "of the dominant class 2 %%)" % (args.region_stride, launches, ksteps)) if events_in_region
+                                         else "separate pass of %d steps after the timed region" % ksteps,
+                        "per_kernel_ms_per_step": {k: round(v[1] / ksteps, 4) for k, v in classes.items()},
+                        "per_kernel_frac_of_peak": {k: round(table[k] * npts / share / (classes[k][1] / classes[k][0] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+                                                    for k in cands},
+                        "step_canonical_bytes": step_bytes,
+                        "step_achieved_GBs": step_bytes / s_per_step / 1e9,
+                        "step_frac_of_peak": step_bytes / s_per_step / 1e9 / peak,
+                        "step_real_bytes": real_bytes,
+                        "step_real_source": "rocprofv3 PMC (profiles/pmc_summary.json)" if pmc_step else "design table x launches",
+                        "step_real_GBs": real_bytes / s_per_step / 1e9,
+                        "step_real_frac": real_bytes / s_per_step / 1e9 / peak,
+                        # second denominator: the 1r + 1w stream-copy rate measured on this device in this run
+                        "peak_guide_copy": GUIDE_COPY_GBS,
+                        "frac_of_guide_copy": achieved / GUIDE_COPY_GBS,
+                        "step_frac_of_guide_copy": step_bytes / s_per_step / 1e9 / (GUIDE_COPY_GBS * share),
+                        "step_real_frac_of_guide_copy": real_bytes / s_per_step / 1e9 / (GUIDE_COPY_GBS * share),
+                        "peak_measured_copy": copy_gbs,
+                        "frac_of_copy": (achieved / copy_gbs) if copy_gbs else None,
+                        "step_frac_of_copy": (step_bytes / s_per_step / 1e9 / (copy_gbs * share)) if copy_gbs else None,
+                        "step_real_frac_of_copy": (real_bytes / s_per_step / 1e9 / (copy_gbs * share)) if copy_gbs else None}
+        else:
+            # a plain run takes no pass of its own: the whole step's canonical bytes over the measured step time (the per-kernel
+            # roofline of the dominant class, the measured copy peak and the PMC traffic come with --full)
+            gbs = step_bytes / s_per_step / 1e9
+            roofline = {"bound": "hbm", "kernel": "whole step (canonical bytes of SURVEY 8d; per-kernel roofline with --full)",
+                        "achieved": gbs, "peak": peak, "unit": "GB/s", "frac": gbs / peak, "traffic": None,
+                        "step_canonical_bytes": step_bytes, "step_achieved_GBs": gbs, "step_frac_of_peak": gbs / peak,
+                        "peak_guide_copy": GUIDE_COPY_GBS, "step_frac_of_guide_copy": gbs / (GUIDE_COPY_GBS * share)}
         out = {
             "metric": ("rank-compute steps/sec of ONE rank of %d alone (no exchange; NOT a simulation rate), " % args.rank_of if args.rank_of else "")
                       + "time-steps/sec, %sModel %d^2 fp64 (achieved HBM GB/s in roofline)" % (
@@ -707,35 +810,9 @@ def main():
                        "blocks_ms_per_step": [round(b, 5) for b in block_ms],
                        "median_block_steps_per_s": 1e3 / float(np.median(block_ms)),
                        "device_bytes": ctx.device_bytes(), **extra},
-            "roofline": {"bound": "hbm", "kernel": KERNEL_SYMBOL[dom], "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": pmc_note,
-                         "launches": launches, "avg_launch_ms": k_ms, "algorithmic_bytes_per_launch": k_bytes,
-                         "kernel_events": ("every %d-th launch of the dominant class bracketed inside the timed region (%d launches sampled, all "
-                                           "positions of the step equally often); per-class table from an untimed pass of %d steps right before "
-                                           "it (an event pair costs the stream ~9 us: all six classes in the region 4.6 %% of the step, all launches "
-                                           "of the dominant class 2 %%)" % (args.region_stride, launches, ksteps)) if events_in_region
-                                          else "separate pass of %d steps after the timed region" % ksteps,
-                         "per_kernel_ms_per_step": {k: round(v[1] / ksteps, 4) for k, v in classes.items()},
-                         "per_kernel_frac_of_peak": {k: round(table[k] * npts / share / (classes[k][1] / classes[k][0] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-                                                     for k in cands},
-                         "step_canonical_bytes": step_bytes,
-                         "step_achieved_GBs": step_bytes / s_per_step / 1e9,
-                         "step_frac_of_peak": step_bytes / s_per_step / 1e9 / peak,
-                         "step_real_bytes": real_bytes,
-                         "step_real_source": "rocprofv3 PMC (profiles/pmc_summary.json)" if pmc_step else "design table x launches",
-                         "step_real_GBs": real_bytes / s_per_step / 1e9,
-                         "step_real_frac": real_bytes / s_per_step / 1e9 / peak,
-                         # second denominator: the 1r + 1w stream-copy rate measured on this device in this run
-                         "peak_guide_copy": GUIDE_COPY_GBS,
-                         "frac_of_guide_copy": achieved / GUIDE_COPY_GBS,
-                         "step_frac_of_guide_copy": step_bytes / s_per_step / 1e9 / (GUIDE_COPY_GBS * share),
-                         "step_real_frac_of_guide_copy": real_bytes / s_per_step / 1e9 / (GUIDE_COPY_GBS * share),
-                         "peak_measured_copy": copy_gbs,
-                         "frac_of_copy": (achieved / copy_gbs) if copy_gbs else None,
-                         "step_frac_of_copy": (step_bytes / s_per_step / 1e9 / (copy_gbs * share)) if copy_gbs else None,
-                         "step_real_frac_of_copy": (real_bytes / s_per_step / 1e9 / (copy_gbs * share)) if copy_gbs else None},
+            "roofline": roofline,
         }
-        if world == 1 and not args.no_cpu_baseline and not args.rank_of and not peers_n:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.rank_of and not peers_n:
             out["cpu_baseline"] = cpu_baseline(phys_model, args.nx, nx_sample=args.cpu_baseline_nx or None)
         print(json.dumps(out))
     watchdog("shutdown")

@@ -313,7 +313,7 @@ def test_config4_8192_on_virtual_ranks_against_the_oracle(nranks, nchunks):
 
 @pytest.mark.parametrize("model", ["coupled", "ybj"])
 def test_bench_contract_with_two_ranks_rehearsed_over_gloo(model):
-    """`bench.py --gpus 2` exactly as the driver launches it (torch.distributed.run, one process per rank), with both
+    """`bench.py --gpus 2 --full` exactly as the driver launches it (torch.distributed.run, one process per rank), with both
     ranks on the one GPU of the test box and the collectives staged through gloo (NIWQG_AMD_DIST_BACKEND): the slab
     set-up, the all-ranks agreement, barrier + max-over-ranks timing and the single JSON line of rank 0."""
     from conftest import free_port
@@ -326,7 +326,7 @@ def test_bench_contract_with_two_ranks_rehearsed_over_gloo(model):
     env = dict(os.environ, NIWQG_AMD_DIST_BACKEND="gloo")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                          "--gpus", "2", "--steps", "5", "--warmup", "1", "--nx", "256", "--model", model],
+                          "--gpus", "2", "--steps", "5", "--warmup", "1", "--nx", "256", "--model", model, "--full"],
                          capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -485,15 +485,15 @@ def test_rccl_link_with_rank_threads_over_a_mock_librccl(tmp_path):
 
 
 def test_bench_contract_on_one_gpu():
-    """`python bench.py` (N = 1): the JSON line's contract fields, the roofline object with both denominators, and the CPU-baseline
-    object (a small grid so that the oracle leg takes seconds)."""
+    """`python bench.py --full` (N = 1): the JSON line's contract fields, the roofline object with both denominators, and the
+    CPU-baseline object (a small grid so that the oracle leg takes seconds)."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "20", "--warmup", "5", "--nx", "128",
-                          "--model", "coupled"], capture_output=True, text=True, timeout=600, cwd=root)
+                          "--model", "coupled", "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, lines
@@ -510,6 +510,47 @@ def test_bench_contract_on_one_gpu():
     assert set(("value", "unit", "cores", "kind", "sample")) <= set(cb) and cb["kind"] == "port" and cb["cores"] == 1 and cb["value"] > 0
 
 
+def test_plain_bench_run_and_its_dumped_outputs(tmp_path):
+    """A plain `bench.py` run (no --full): the contract fields, exactly --steps timed steps, no CPU baseline; --dump-outputs
+    writes float64 arrays that are the state of a context stepped warm-up + timed steps from the same inputs, the same in
+    two runs."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(d):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "12", "--warmup", "3", "--nx", "128",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, lines
+        return json.loads(lines[0])
+    d = run(tmp_path / "a")
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "roofline"):
+        assert key in d, key
+    assert d["steps"] == 12 and d["warmup"] == 3 and d["dtype"] == "f64" and d["unit"] == "steps/s" and d["higher_is_better"]
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-6 and "cpu_baseline" not in d
+    r = d["roofline"]
+    assert r["bound"] == "hbm" and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12 and "per_kernel_ms_per_step" not in r
+    run(tmp_path / "b")
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["budget_increments.npy", "phi_im.npy", "phi_re.npy", "q.npy"] and names == sorted(os.listdir(tmp_path / "b"))
+    a = {n[:-4]: np.load(str(tmp_path / "a" / n)) for n in names}
+    for n in names:
+        assert a[n[:-4]].dtype == np.float64
+        np.testing.assert_allclose(np.load(str(tmp_path / "b" / n)), a[n[:-4]], rtol=1e-12, atol=0)
+    import bench
+    from niwqg_amd import _lib
+    m = bench.build_model("coupled", 128, 0)
+    m._ctx.step(3 + 12)
+    np.testing.assert_allclose(a["q"], m._ctx.field(_lib.F_Q).ravel(), rtol=1e-12, atol=1e-12 * np.abs(a["q"]).max())
+    phi = m._ctx.field(_lib.F_PHI).ravel()
+    np.testing.assert_allclose(a["phi_re"] + 1j * a["phi_im"], phi, rtol=1e-12, atol=1e-12 * np.abs(phi).max())
+    m._ctx.close()
+
+
 def test_bench_peers_link_and_rank_of_on_one_gpu():
     """`bench.py --gpus 2 --link peers`: ONE process drives both ranks (on a multi-GPU node rank r sits on device r and the blocks
     cross by peer copies; here both share the one device) -- no launcher, no RCCL; `bench.py --rank-of 4`: one rank of the
@@ -522,7 +563,7 @@ def test_bench_peers_link_and_rank_of_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
 
     def line(*args):
-        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "3", "--no-cpu-baseline"] + list(args),
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--full"] + list(args),
                              capture_output=True, text=True, timeout=600, cwd=root, env=env)
         assert out.returncode == 0, (args, out.stdout[-1500:], out.stderr[-3000:])
         lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -330,3 +330,28 @@ def test_any_size_path_host_logic(built):
     src = open(os.path.join(ROOT, "niwqg_amd", "csrc", "nq_anysize.hpp")).read()
     for name, val in re.findall(r"\b(EW_[A-Z0-9]+|RD_[A-Z0-9]+) = (\d+)", src):
         assert ids["NQ_" + name] == int(val), name
+
+
+def test_bench_dump_outputs_layout_and_sampling(tmp_path):
+    """bench.py --dump-outputs: float64 .npy per array, complex arrays as _re / _im, whole arrays while they fit, a fixed seeded
+    sample (the same indices for every field of one size, in every run) of larger ones, DUMP_BYTES at most in all."""
+    import bench
+    small = np.arange(12.0).reshape(3, 4)
+    z = np.arange(6.0) - 1j * np.arange(6.0)
+    bench.dump_outputs(str(tmp_path / "s"), {"q": small, "phi": z, "b": np.array([1.0, 2.0, 3.0])})
+    assert sorted(os.listdir(str(tmp_path / "s"))) == ["b.npy", "phi_im.npy", "phi_re.npy", "q.npy"]
+    assert np.array_equal(np.load(str(tmp_path / "s" / "q.npy")), small.ravel())
+    assert np.array_equal(np.load(str(tmp_path / "s" / "phi_im.npy")), -np.arange(6.0))
+    n = 4096
+    big = np.random.default_rng(5).standard_normal((n, n)) + 1j * np.random.default_rng(6).standard_normal((n, n))
+    for d in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / d), {"q": big.real, "phi": big})
+    total = 0
+    for name in ("q", "phi_re", "phi_im"):
+        a = np.load(str(tmp_path / "x" / (name + ".npy")))
+        assert a.dtype == np.float64 and a.size == bench.DUMP_BYTES // 8 // 3
+        assert np.array_equal(a, np.load(str(tmp_path / "y" / (name + ".npy"))))
+        total += os.path.getsize(str(tmp_path / "x" / (name + ".npy")))
+    assert total <= 64 << 20
+    assert np.array_equal(np.load(str(tmp_path / "x" / "q.npy")), np.load(str(tmp_path / "x" / "phi_re.npy")))
+    assert np.isin(np.load(str(tmp_path / "x" / "q.npy"))[:100], big.real).all()

@@ -10,7 +10,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 DST=$ROOT/gpurun_out/profiles_$TAG
 mkdir -p "$OUT" "$DST"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o run --output-format csv -- python3 "$ROOT/bench.py" --model $MODEL --nx $NX --steps $STEPS --warmup 2 --no-cpu-baseline > "$OUT/bench_line.json" 2> "$OUT/bench_stderr.log"
+rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o run --output-format csv -- python3 "$ROOT/bench.py" --model $MODEL --nx $NX --steps $STEPS --warmup 2 --full --no-cpu-baseline > "$OUT/bench_line.json" 2> "$OUT/bench_stderr.log"
 echo "stats rc=$?"
 cp "$(find "$OUT/stats" -name '*kernel_stats.csv' | head -1)" "$DST/${TAG}_kernel_stats.csv"
 grep '^{' "$OUT/bench_line.json" | tail -1 > "$DST/${TAG}_bench_line.json"

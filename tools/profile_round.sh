@@ -1,7 +1,7 @@
 #!/bin/bash
 # One gpurun call's worth of evidence for the headline workload (run from the repo root ON THE GPU BOX):
 #   tools/profile_round.sh TAG        e.g. TAG=r02_a
-# 1. rocprofv3 --kernel-trace --stats of `python3 bench.py --steps 20 --warmup 5` (kernel stats csv + the bench line)
+# 1. rocprofv3 --kernel-trace --stats of `python3 bench.py --steps 20 --warmup 5 --full` (kernel stats csv + the bench line)
 # 2. rocprofv3 --pmc passes (FETCH_SIZE | WRITE_SIZE | LDS | waits), each in its own run with --kernel-trace only
 # 3. summaries copied to profiles/ (and mirrored to gpurun_out/profiles_TAG/ so that they travel back)
 set -u
@@ -11,9 +11,9 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT" "$ROOT/gpurun_out/profiles_$TAG"
 cd /tmp && export TMPDIR=/tmp
 # the headline line itself, un-profiled, with the measured CPU sample
-python3 "$ROOT/bench.py" > "$OUT/bench_plain.json" 2> "$OUT/bench_plain_stderr.log"
+python3 "$ROOT/bench.py" --full > "$OUT/bench_plain.json" 2> "$OUT/bench_plain_stderr.log"
 grep '^{' "$OUT/bench_plain.json" | tail -1 > "$ROOT/gpurun_out/profiles_$TAG/${TAG}_bench_line_plain.json"
-rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o run --output-format csv -- python3 "$ROOT/bench.py" --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_line.json" 2> "$OUT/bench_stderr.log"
+rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o run --output-format csv -- python3 "$ROOT/bench.py" --steps 20 --warmup 5 --full --no-cpu-baseline > "$OUT/bench_line.json" 2> "$OUT/bench_stderr.log"
 echo "stats rc=$?"
 cp "$(find "$OUT/stats" -name '*kernel_stats.csv' | head -1)" "$ROOT/gpurun_out/profiles_$TAG/${TAG}_kernel_stats.csv"
 grep '^{' "$OUT/bench_line.json" | tail -1 > "$ROOT/gpurun_out/profiles_$TAG/${TAG}_bench_line.json"

@@ -15,7 +15,7 @@ mkdir -p "$OUT"
 for nx in $SIZES; do
   for P in 2 4 8; do
     for ch in 1 2 4; do
-      python3 bench.py --nx $nx --rank-of $P --chunks $ch --steps 30 --warmup 5 2> "$OUT/err_${nx}_${P}_${ch}.log" | grep '^{' > "$OUT/rank_of_${P}_${nx}_chunks${ch}.json"
+      python3 bench.py --nx $nx --rank-of $P --chunks $ch --steps 30 --warmup 5 --full 2> "$OUT/err_${nx}_${P}_${ch}.log" | grep '^{' > "$OUT/rank_of_${P}_${nx}_chunks${ch}.json"
       python3 - "$OUT/rank_of_${P}_${nx}_chunks${ch}.json" <<'PY'
 import json, sys
 try:
