@@ -201,6 +201,18 @@ int nq_refraction(nq_ctx* ctx, double* out_cplx);
  * which the last step evaluated its fourth stage, as the reference's are at a tick).                          */
 int nq_diagnostics(nq_ctx* ctx, double* out32);
 
+/* Isotropic spectra of the diagnostics tick: out[s * nb + b] = the sum, over the wavenumbers of shell b,
+ * of the exact term nq_diagnostics adds into sum s (same expression, weights, Hermitian parts, dual copies, passenger row and
+ * filter ratios), so that sum_b out[s * nb + b] = out32[s] up to summation order.  Shell of (l, k), i = kx/dk, j = ly/dk: the
+ * unique b >= 0 with 2b - 1 <= 2 sqrt(i^2 + j^2) < 2b + 1 (integers: b = (isqrt(4 (i^2 + j^2)) + 1) / 2); shells b <= nx/2 lie
+ * wholly inside the square, the outer ones are partial.  nb must be nq_spectrum_shells(ctx) = round(nx / sqrt 2) + 1.  Binned
+ * rows: Kernel family [0..3], [6..14], [24], [27], [28], [31]; QGModel [6..14] and with its passive scalar [16..19]; every
+ * other row is zero.  Deterministic (no floating-point atomics: one workgroup per shell); the products passes of the tick are
+ * run again, nothing else a step or a later call reads is touched.  The first call allocates two real full planes (Kernel
+ * family; counted by nq_device_bytes).  Single-rank contexts.                                                          */
+int nq_spectrum_shells(const nq_ctx* ctx);
+int nq_diagnostics_binned(nq_ctx* ctx, int nb, double* out);
+
 /* copy of one ETDRK4 coefficient plane (0:E 1:Eh 2:Q 3:f0 4:fab 5:fc) of equation eq (0: q, (nx, nx/2+1) complex;
  * 1: phi, (nx, nx) complex; 2: QGModel's passive scalar, (nx, nx/2+1)), without the filter folded in; values as the
  * reference's expch, expch_h, Qh, f0, fab, fc (Kernel.py:417-454, QGModel.py:426-461).                           */
@@ -314,6 +326,11 @@ int nq_slab_spectral_read(nq_ctx* ctx, int half, double* out_cplx);
 /* nq_diagnostics of a slab-decomposed simulation: the same 32 sums, every rank's part summed over the ranks (collective);
  * nq_slab_local_max: max|u|, max|v|, max|phi| over this rank's rows (the caller takes the max over ranks for the CFL) */
 int nq_slab_diagnostics(nq_ctx* ctx, double* out32);
+/* nq_diagnostics_binned of a slab-decomposed simulation (collective): every context bins its own columns (global k from its
+ * first column), the products passes exchange as the tick's do, and the contexts of this process are summed in rank order:
+ * peer ranks in one process give the whole (32, nb) array; with one rank per process the result is that rank's part, which
+ * the caller gathers (all_gather) and sums in rank order, so that every rank holds the same array. */
+int nq_slab_diagnostics_binned(nq_ctx* ctx, int nb, double* out);
 int nq_slab_local_max(nq_ctx* ctx, double* out3);
 /* counters since the last reset: out[0] host calls of nq_slab_step, [1] steps, [2] exchange chunks issued, [3] bytes this
  * rank sent to OTHER ranks, [4] milliseconds the exchange stream spent in exchanges (HIP events; 0 unless timing was
@@ -394,6 +411,10 @@ int nq_any_reduce(nq_any* eng, int op, const void* a, const void* b, long long e
 int nq_any_expand_half(nq_any* eng, void* full, const void* half, int rows, int n, int project);
 int nq_any_take_cols(nq_any* eng, void* dst, const void* src, int rows, int src_cols, int dst_cols);
 int nq_any_set_elem(nq_any* eng, void* plane, long long index, double re, double im);
+/* isotropic shell sums of the REAL part of a complex plane: layout 0 a full (rows, rows) plane in fftfreq order, 1 an rfft half
+ * plane (rows, rows/2 + 1); out: nb = round(rows / sqrt 2) + 1 doubles; the integer shell rule and the deterministic kernel of
+ * nq_diagnostics_binned (no weights: the caller forms each element's term, half planes with their weight folded in).    */
+int nq_any_bin(nq_any* eng, const void* plane, int rows, int cols, int layout, int nb, double* out);
 /* E = exp(c dt), Eh = exp(c dt / 2), Q, f0, fab, fc of the linear operator c(l, k) on a (n, cols) plane, WITHOUT the filter
  * (Kernel.py:417-454, QGModel.py:426-466); eq 0: q of the Kernel family, 1: phi, 2: QGModel's q (beta term), 3: its passive
  * scalar.  The entries within delta of the contour are listed (near_*; at most cap) for the host to recompute exactly as the

@@ -619,6 +619,72 @@ class KernelFamily(object):
         with np.errstate(invalid="ignore", divide="ignore"):
             return np.float64((qp ** 3).mean()) / (np.float64((qp ** 2).mean()) ** 1.5)
 
+    # ---- isotropic spectra (niwqg_amd/spectra.py) -----------------------------------------------
+    def _bin(self, plane, layout):
+        """shell sums of Re(plane) on the device (nq_any_bin; layout 0 full, 1 half plane)"""
+        e, nx = self._eng, self.nx
+        nb = int(np.floor(nx / np.sqrt(2) + 0.5)) + 1
+        out = np.zeros(nb)
+        e.chk(e.L.nq_any_bin(e.h, plane.ptr, plane.shape[0], plane.shape[1], int(layout), nb, _lib._dptr(out)), "nq_any_bin")
+        return out
+
+    def _spectra(self, names):
+        """the named spectra of the current state: each scalar of this path written by Parseval as a sum over the full plane
+        of one term per wavenumber (formed here from the planes this path holds, with the device's transforms and element-wise
+        calls), binned into shells.  Nothing this path keeps is written: u, v, q_psi, lapphi are formed locally."""
+        d, K = self._d, self._K
+        M2 = float(self.M) ** 2
+        M2f = M2 * self.f
+        phih = d["phih"]
+        a2 = phih.abs2()
+        out = {}
+        need = set(names)
+        if need & {"ens", "ep_psi"}:
+            Q = self._fft(d["q"])
+        if "ke_qg" in need:
+            out["ke_qg"] = self._bin(K["wv2"] * d["ph"].abs2() * (0.5 / M2), 0)
+        if "ens" in need:
+            out["ens"] = self._bin(Q.abs2() * (0.5 / M2), 0)
+        if "ke_niw" in need:
+            out["ke_niw"] = self._bin(a2 * (0.5 / M2), 0)
+        if "pe_niw" in need:
+            out["pe_niw"] = self._bin(K["wv2"] * a2 * (0.25 / M2 / self.kappa2), 0)
+        if "ep_phi" in need:
+            w = K["wv4"] * (-self.nu4w) - K["wv2"] * self.nuw - self.muw
+            out["ep_phi"] = self._bin(w * a2 / M2, 0)
+        if "ep_psi" in need:
+            t = Q.conj() * (K["wv4"] * d["ph"]) * self.nu4
+            if self.model_id != _lib.YBJ:            # the reference's p stays zero there
+                P = self._fft(d["p"])
+                t = t + P.conj() * (K["wv2"] * d["qh"] * self.nu + Q * self.mu)
+            out["ep_psi"] = self._bin(t / M2, 0)
+        if "chi_q" in need:
+            out["chi_q"] = self._bin(K["wv4"] * d["qh"].abs2() * (-self.nu4 / M2), 0)
+        if "chi_phi" in need:
+            w = K["wv4"] * K["wv2"] * self.nu4w + K["wv4"] * self.nuw + K["wv2"] * self.muw
+            out["chi_phi"] = self._bin(w * a2 * (-0.5 / M2 / self.kappa2), 0)
+        if need & {"gamma_r", "gamma_a", "xi_r", "xi_a"}:
+            lap = K["mwv2"] * phih
+            diss = (K["wv4"] * (-self.nu4w) - K["wv2"] * self.nuw - self.muw) * phih
+            if need & {"gamma_a", "xi_r"}:
+                u, v = self._ifft(K["mil"] * d["ph"]).real, self._ifft(K["ik"] * d["ph"]).real
+                FJ = self._fft(u * d["phix"] + v * d["phiy"])
+                if "gamma_a" in need:
+                    out["gamma_a"] = self._bin(lap.conj() * FJ * (0.5 * self.hslash / M2f), 0)
+                if "xi_r" in need:
+                    out["xi_r"] = self._bin((diss.conj() * FJ).imag / M2f, 0)
+            if need & {"gamma_r", "xi_a"}:
+                if self.model_id == _lib.COUPLED:
+                    q_psi = d["q"] - self._ifft(d["qwh"]).real
+                else:
+                    q_psi = d["q"]
+                R = self._fft(d["phi"] * q_psi)        # i F[phi q_psi] enters as -Im(.) of the products with R
+                if "gamma_r" in need:
+                    out["gamma_r"] = self._bin((lap.conj() * R).imag * (-0.25 * self.hslash / M2f), 0)
+                if "xi_a" in need:
+                    out["xi_a"] = self._bin(diss.conj() * R * (0.5 / M2f), 0)
+        return out
+
     def _calc_ke_qg_decomp(self):   # ref: niwqg/CoupledModel.py:99-113
         d, K = self._d, self._K
         phq = K["mwv2i"] * d["qh"]
@@ -906,6 +972,49 @@ class QGFamily(object):
         self._user.pop("u", None)
         self._user.pop("v", None)
         return max(self._d["u"].absmax(), self._d["v"].absmax()) * self.dt / self.dx
+
+    # ---- isotropic spectra (niwqg_amd/spectra.py) -----------------------------------------------
+    _bin = KernelFamily._bin
+
+    def _spectra(self, names):
+        """as KernelFamily._spectra on the half planes of this class: weights w (2 on the interior columns, 1 on the two
+        self-mirrored ones) folded into each term; products of a real field's rfft with any half plane are exact there"""
+        d, K = self._d, self._K
+        M2 = float(self.M) ** 2
+        if "_svw1" not in K:                          # spec_var's weights with the mean included
+            w = np.full((self.nx, self.nx // 2 + 1), 2.0)
+            w[:, 0] = w[:, -1] = 1.0
+            K["_svw1"] = self._eng.plane(w)
+        w1, sv = K["_svw1"], K["svw"]
+        need = set(names)
+        out = {}
+        if need & {"ens", "ep_psi"}:
+            Q = self._rfft(d["q"])
+        if "ke_qg" in need:
+            out["ke_qg"] = self._bin(sv * K["wv2"] * d["ph"].abs2() * (0.5 / M2), 1)
+        if "ens" in need:
+            out["ens"] = self._bin(w1 * Q.abs2() * (0.5 / M2), 1)
+        if "ep_psi" in need:
+            P = self._rfft(d["p"])
+            t = Q.conj() * (K["wv4"] * d["ph"]) * self.nu4 + P.conj() * (K["wv2"] * d["qh"] * self.nu + Q * self.mu)
+            out["ep_psi"] = self._bin(w1 * t / M2, 1)
+        if "chi_q" in need:
+            out["chi_q"] = self._bin(sv * K["wv4"] * d["qh"].abs2() * (-self.nu4 / M2), 1)
+        if need & {"C2", "gradC2", "ep_c", "chi_c"}:
+            ch = d["ch"]
+            c2 = sv * ch.abs2()
+            LC = self._rfft(self._irfft(K["mwv2"] * ch))          # the transform of the REAL lap c
+            lc2 = w1 * LC.abs2()
+            if "C2" in need:
+                out["C2"] = self._bin(c2 / M2, 1)
+            if "gradC2" in need:
+                out["gradC2"] = self._bin(K["wv2"] * c2 / M2, 1)
+            if "ep_c" in need:
+                out["ep_c"] = self._bin((lc2 * (-2 * self.nu4c) - K["wv2"] * c2 * (2 * self.nu) - c2 * (2 * self.muc)) / M2, 1)
+            if "chi_c" in need:
+                t = w1 * (LC.conj() * (K["wv4"] * ch)) * (2 * self.nu4c) - lc2 * (2 * self.nu) - K["wv2"] * c2 * (2 * self.muc)
+                out["chi_c"] = self._bin(t / M2, 1)
+        return out
 
     def _calc_derived_fields(self):     # ref: niwqg/QGModel.py:724-737
         if self.passive_scalar:

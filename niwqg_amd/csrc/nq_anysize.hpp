@@ -342,6 +342,18 @@ k_any_split_rows(const cd* src, cd* dst, int nrows, int pitch, const cd* __restr
   }
 }
 
+// nq_any_bin: the real part of a complex (rows, pitch) plane, one term per element, for the shell binning kernel of nq_lib.hip
+// (k_bin_shells: full fftfreq-ordered planes and rfft half planes alike)
+struct AnyBinRe {
+  static constexpr int NQ = 1;
+  const cd* a;
+  int pitch;
+  __device__ void operator()(int l, int k, int kl, double* v) const {
+    (void)k;
+    v[0] += a[(size_t)l * pitch + kl].x;
+  }
+};
+
 }  // namespace nq
 
 struct nq_any {

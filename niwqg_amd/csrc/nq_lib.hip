@@ -118,6 +118,7 @@ struct nq_ctx {
   double *partW = nullptr, *partQ = nullptr;      // [4 stages][workgroups][NQ_PARTW | 3]
   double *part0W = nullptr, *part0Q = nullptr;    // partials of set_phi / set_q / nq_invert
   double *diag_part = nullptr, *diag_out = nullptr;   // diagnostics tick: workgroup partials, 32 reduced sums
+  double *spec_out = nullptr, *spec_r = nullptr;     // isotropic spectra of the tick: 32 x nb shell sums, two real planes
   double *carryW = nullptr, *carryQ = nullptr;    // spectral sums of the state at the start of the next step
   double *gradS1 = nullptr, *acc = nullptr;       // stale-aware sum wv2|phih_grad|^2 ; Ke,Pw,Kw increments
   double* bsums = nullptr;                        // [4 stages][11] reduced sums of one step
@@ -568,6 +569,176 @@ __global__ void k_diag_c(const cd* __restrict__ ch, int N, int width, int pitch,
   }
   diag_block_store<4>(v, part);
 }
+
+// isotropic spectra of the diagnostics tick (nq_diagnostics_binned) ------------------------------
+// Shell of the wavenumber with integer indices (i, j): the unique b >= 0 with 2b - 1 <= 2 sqrt(i^2 + j^2) < 2b + 1, i.e.
+// b = (isqrt(4 (i^2 + j^2)) + 1) / 2 -- integers only, no ties.  Only the sign-free i^2, j^2 enter, so the k = N/2 column
+// of the half spectrum (+N/2) and of the full plane (-N/2) fall into the same shell.
+__host__ __device__ inline long long nq_isqrt(long long v) {          // floor(sqrt(v)), v >= 0 (exact: v < 2^52 here)
+  long long r = (long long)sqrt((double)v);
+  while (r * r > v) --r;
+  while ((r + 1) * (r + 1) <= v) ++r;
+  return r;
+}
+__host__ __device__ inline int nq_shell_of(long long i, long long j) { return (int)((nq_isqrt(4 * (i * i + j * j)) + 1) / 2); }
+// shells of an N x N grid: the corner i = j = N/2 lies in shell round(N / sqrt 2)
+inline int nq_shell_count(int N) { return nq_shell_of(N / 2, N / 2) + 1; }
+// the i >= 0 of row j that lie in shell b: [*lo, *hi] (empty when *lo > *hi)
+__device__ inline void shell_run(int b, int j, int* lo, int* hi) {
+  const long long j2 = 4LL * j * j, ub = (2LL * b + 1) * (2LL * b + 1) - j2;       // 4 i^2 < ub
+  const long long lb = (b == 0) ? 0 : (2LL * b - 1) * (2LL * b - 1) - j2;           // 4 i^2 >= lb
+  if (ub <= 0) { *lo = 1; *hi = 0; return; }
+  *hi = (int)nq_isqrt((ub - 1) / 4);
+  *lo = (lb <= 0) ? 0 : (int)nq_isqrt((lb + 3) / 4 - 1) + 1;                          // smallest i with i^2 >= ceil(lb / 4)
+}
+// Shell-stationary binning: workgroup b owns shell b and walks the rows |j| <= b, one row per thread; in a row the k of the
+// shell are one run (half spectrum: k = i) or two (full plane: k = i and k = N - i), cut to the local columns [k0, k0 + width)
+// (a slab rank's; the whole plane: 0, N/2 + 1 or N).  Every thread adds its rows in a fixed order, the workgroup reduces in a
+// fixed tree: no atomics, bit-identical results from call to call.  Term::NQ sums per element, t(l, kg, kl, v) ADDS the
+// terms of the element at row l, global column kg, local column kl = kg - k0 to v; out[q * nb + b] (q < Term::NQ).  256 threads.
+template <class Term>
+__global__ void __launch_bounds__(256) k_bin_shells(Term t, int N, int nb, int full, int k0, int width, double* __restrict__ out) {
+  constexpr int NQ = Term::NQ;
+  const int b = blockIdx.x;
+  double v[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) v[q] = 0.0;
+  const int j0 = (b < N / 2) ? -b : -N / 2, j1 = (b < N / 2 - 1) ? b : N / 2 - 1;
+  for (int j = j0 + (int)threadIdx.x; j <= j1; j += blockDim.x) {
+    int lo, hi;
+    shell_run(b, j, &lo, &hi);
+    const int l = (j < 0) ? j + N : j;
+    int a = (lo > k0) ? lo : k0, e = (hi < N / 2) ? hi : N / 2;
+    if (e > k0 + width - 1) e = k0 + width - 1;
+    for (int i = a; i <= e; ++i) t(l, i, i - k0, v);                          // k = i (the half spectrum's only run)
+    if (full) {                                                                // k = N - i: negative kx, i in [1, N/2 - 1]
+      a = (lo > 1) ? lo : 1;
+      if (a < N - k0 - width + 1) a = N - k0 - width + 1;
+      e = (hi < N / 2 - 1) ? hi : N / 2 - 1;
+      if (e > N - k0) e = N - k0;
+      for (int i = a; i <= e; ++i) t(l, N - i, N - i - k0, v);
+    }
+  }
+  __shared__ double sh[4][NQ];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    double x = v[q];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+    if (lane == 0) sh[wave][q] = x;
+  }
+  __syncthreads();
+  if (threadIdx.x < NQ) out[(size_t)threadIdx.x * nb + b] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+}
+// per-element terms of k_diag_phi: [0..3] wv2^n |phih|^2 (full plane)
+struct BinPhi {
+  static constexpr int NQ = 4;
+  const cd* phih;
+  int pitch;
+  const double *kk, *ll;
+  __device__ void operator()(int l, int k, int kl, double* v) const {
+    const cd z = phih[(size_t)l * pitch + kl];
+    const double kx = kk[k], ly = ll[l];
+    const double wv2 = kx * kx + ly * ly, m2 = z.x * z.x + z.y * z.y;
+    v[0] += m2;
+    v[1] += wv2 * m2;
+    v[2] += wv2 * wv2 * m2;
+    v[3] += wv2 * wv2 * wv2 * m2;
+  }
+};
+// per-element terms of k_diag_q: [6..14] (half spectrum; weights, Hermitian parts, dual copies, filter ratios and the passenger
+// row exactly as there)
+struct BinQ {
+  static constexpr int NQ = 9;
+  const cd *qh, *qwh, *ph;
+  int N, pitch;
+  const double *kk, *ll;
+  const cd *qp, *qm_;
+  const double *filt_p, *filt_m;
+  const cd* passenger;
+  __device__ void operator()(int l, int k, int kl, double* v) const {
+    const size_t idx = (size_t)l * pitch + kl;
+    const cd q = qh[idx], w = qwh ? qwh[idx] : cmake(0, 0), p = ph[idx];
+    cd hq = q, hw = w, hp = p;
+    double wt = 2.0;
+    if (k == 0 || k == N / 2) {
+      wt = 1.0;
+      const size_t im = (size_t)((N - l) % N) * pitch + kl;
+      const cd qm = qh[im], wm = qwh ? qwh[im] : cmake(0, 0), pm = ph[im];
+      hq = cmake(0.5 * (q.x + qm.x), 0.5 * (q.y - qm.y));
+      hw = cmake(0.5 * (w.x + wm.x), 0.5 * (w.y - wm.y));
+      hp = cmake(0.5 * (p.x + pm.x), 0.5 * (p.y - pm.y));
+    }
+    const double kx = kk[k], ly = ll[l];
+    const double wv2 = kx * kx + ly * ly, wv4 = wv2 * wv2, wv2i = (wv2 != 0.0) ? 1.0 / wv2 : 0.0;
+    double q2 = q.x * q.x + q.y * q.y;
+    if (qp != nullptr && wt == 2.0) {
+      const cd a = qp[idx], b = qm_[idx];
+      q2 = 0.5 * (a.x * a.x + a.y * a.y + b.x * b.x + b.y * b.y);
+    }
+    if (passenger != nullptr && l == N / 2 && wt == 2.0) {
+      const cd a = passenger[kl];
+      q2 += a.x * a.x + a.y * a.y;
+    }
+    v[0] += wt * (hq.x * hq.x + hq.y * hq.y);
+    v[1] += wt * wv4 * q2;
+    v[2] += wt * wv2i * q2;
+    double w2 = w.x * w.x + w.y * w.y;
+    if (filt_p != nullptr) {
+      const double fp = filt_p[idx], fm = filt_m[idx], fs = 0.5 * (fp + fm);
+      if (fs > 0.0) {
+        const double a = fp / fs, b = fm / fs;
+        w2 *= (wt == 2.0) ? 0.5 * (a * a + b * b) : a * a;
+      }
+    }
+    v[3] += wt * wv2i * w2;
+    const double w2eff = ((l == N / 2) ? 0.0 : ly * ly) + ((k == N / 2) ? 0.0 : kx * kx);
+    v[4] += wt * wv2i * wv2i * w2eff * (hq.x * hw.x + hq.y * hw.y);
+    const cd pk = (qp != nullptr) ? hp : p;
+    v[5] += (l == 0 && k == 0) ? 0.0 : wt * wv2 * (pk.x * pk.x + pk.y * pk.y);
+    const double pq = hp.x * hq.x + hp.y * hq.y;
+    v[6] += wt * wv4 * pq;
+    v[7] += wt * wv2 * pq;
+    v[8] += wt * pq;
+  }
+};
+// per-element terms of k_diag_c: [16..19] w wv2^n |c-hat|^2 (half spectrum)
+struct BinC {
+  static constexpr int NQ = 4;
+  const cd* ch;
+  int N, pitch;
+  const double *kk, *ll;
+  __device__ void operator()(int l, int k, int kl, double* v) const {
+    const cd z = ch[(size_t)l * pitch + kl];
+    cd h = z;
+    double wt = 2.0;
+    if (k == 0 || k == N / 2) {
+      wt = 1.0;
+      const cd zm = ch[(size_t)((N - l) % N) * pitch + kl];
+      h = cmake(0.5 * (z.x + zm.x), 0.5 * (z.y - zm.y));
+    }
+    const double kx = kk[k], ly = ll[l], wv2 = kx * kx + ly * ly;
+    const double m2 = wt * (z.x * z.x + z.y * z.y), m2h = wt * (h.x * h.x + h.y * h.y);
+    v[0] += (l == 0 && k == 0) ? 0.0 : m2;
+    v[1] += wv2 * m2;
+    v[2] += wv2 * wv2 * m2h;
+    v[3] += wv2 * wv2 * wv2 * m2h;
+  }
+};
+// k_s_project_bin's two real planes of per-element terms, in the places of [24..27] / [28..31]: Re-lap -> +0, Im-diss -> +3
+// (+1, +2, the Im-lap and Re-diss projections, are not binned and stay zero)
+struct BinProj {
+  static constexpr int NQ = 4;
+  const double *rlap, *rdiss;
+  int pitch;
+  __device__ void operator()(int l, int k, int kl, double* v) const {
+    (void)k;
+    const size_t idx = (size_t)l * pitch + kl;
+    v[0] += rlap[idx];
+    v[3] += rdiss[idx];
+  }
+};
 
 // budget bookkeeping ----------------------------------------------------------------------------
 struct BudgetAcc {
@@ -1797,6 +1968,17 @@ static void launch_project_s(nq_ctx* c, double* part) {
 }
 static void launch_project(nq_ctx* c, double* part) {
 #define CALL_(s, clx) launch_project_s<s, clx>(c, part)
+  NQ_S1_SWITCH(c, CALL_)
+#undef CALL_
+}
+template <int S, int CLX>
+static void launch_project_bin_s(nq_ctx* c, double* rlap, double* rdiss) {
+  typedef YPlanT<S, CLX> Y;
+  hipLaunchKernelGGL((k_s_project_bin<S, CLX>), dim3(c->Wf / CLX, c->S2), dim3(Y::THREADS), Y::LDS_BYTES, c->stream, c->mW,
+                     (const cd*)c->w.y[c->w.cur], geom_full(c), c->kk, c->ll, c->tw, 1, c->p.nu4w, c->p.nuw, c->p.muw, rlap, rdiss, c->Wf);
+}
+static void launch_project_bin(nq_ctx* c, double* rlap, double* rdiss) {
+#define CALL_(s, clx) launch_project_bin_s<s, clx>(c, rlap, rdiss)
   NQ_S1_SWITCH(c, CALL_)
 #undef CALL_
 }
@@ -3751,6 +3933,118 @@ int nq_diagnostics(nq_ctx* c, double* out) {
   return nq_sync(c);
 }
 
+// ---- isotropic spectra of the diagnostics tick ----------------------------------------------------
+int nq_spectrum_shells(const nq_ctx* c) { return c ? nq_shell_count(c->N) : -1; }
+
+// out[s * nb + b]: the terms nq_diagnostics adds into sum s, summed over the wavenumbers of shell b.  Binned: the Kernel family's
+// [0..3], [6..14], [24], [27], [28], [31]; QGModel's [6..14] and, with its passive scalar, [16..19]; every other row is zero.
+// The same passes as the tick (the two products passes included, so its side effects are the tick's), the binning kernels in
+// place of the workgroup sums.
+// this context's local columns: allocate, zero, and bin the spectral rows ([0..3], [6..14], [16..19]) into spec_out
+static int bin_local_spectral(nq_ctx* x, int nb) {
+  const int N = x->N;
+  const bool waves = x->kernel_family;
+  if (!x->spec_out) ALLOC(x, x->spec_out, (size_t)32 * nb);
+  if (waves && !x->spec_r) ALLOC(x, x->spec_r, (size_t)2 * N * x->Wf);
+  double* d = x->spec_out;
+  HIPCHK(x, hipMemsetAsync(d, 0, sizeof(double) * 32 * nb, x->stream));
+  const cd* qh = x->q.y[x->q.cur];
+  if (x->dual) {                                      // as the tick: the mean of the two copies
+    if (x->P == 1) {
+      hipLaunchKernelGGL(k_avg_interior, dim3((x->Wh + 63) / 64, N), dim3(64), 0, x->stream, qh, (const cd*)x->q2.y[x->q2.cur], x->scr_f1, x->Wh, x->Ph, N);
+      qh = x->scr_f1;
+    } else {
+      if (!x->scr_h1) ALLOC(x, x->scr_h1, (size_t)N * x->Ph);
+      if (x->Wh > 0) hipLaunchKernelGGL(k_avg_interior_g, dim3((x->Wh + 63) / 64, N), dim3(64), 0, x->stream, qh, (const cd*)x->q2.y[x->q2.cur], x->scr_h1, x->Wh, x->Ph, N, x->kh0);
+      qh = x->scr_h1;
+    }
+  }
+  if (waves && x->Wf > 0) {
+    const BinPhi t{(const cd*)x->w.y[x->w.cur], x->Wf, x->kk, x->ll};
+    hipLaunchKernelGGL(k_bin_shells<BinPhi>, dim3(nb), dim3(256), 0, x->stream, t, N, nb, 1, x->kf0, x->Wf, d);
+  }
+  if (x->Wh > 0) {
+    const BinQ t{qh, (const cd*)(x->p.model == NQ_MODEL_COUPLED ? x->qwh : nullptr), (const cd*)x->ph, N, x->Ph, x->kk, x->ll,
+                 (const cd*)(x->dual ? x->q.y[x->q.cur] : nullptr), (const cd*)(x->dual ? x->q2.y[x->q2.cur] : nullptr),
+                 (const double*)(x->dual ? x->filt_h : nullptr), (const double*)(x->dual ? x->filt_m : nullptr),
+                 (const cd*)(x->pass ? x->qp.y[x->qp.cur] : nullptr)};
+    hipLaunchKernelGGL(k_bin_shells<BinQ>, dim3(nb), dim3(256), 0, x->stream, t, N, nb, 0, x->kh0, x->Wh, d + (size_t)6 * nb);
+    if (!waves && x->passive) {
+      const BinC tc{(const cd*)x->cq.y[x->cq.cur], N, x->Ph, x->kk, x->ll};
+      hipLaunchKernelGGL(k_bin_shells<BinC>, dim3(nb), dim3(256), 0, x->stream, tc, N, nb, 0, x->kh0, x->Wh, d + (size_t)16 * nb);
+    }
+  }
+  return 0;
+}
+// after the products pass `which` (0: J, 1: i F[phi q_psi]) and its A sub-pass: rows 24 + 4 which .. 27 + 4 which
+static void bin_local_project(nq_ctx* x, int nb, int which) {
+  double *rl = x->spec_r, *rd = x->spec_r + (size_t)x->N * x->Wf;
+  launch_project_bin(x, rl, rd);
+  const BinProj t{rl, rd, x->Wf};
+  hipLaunchKernelGGL(k_bin_shells<BinProj>, dim3(nb), dim3(256), 0, x->stream, t, x->N, nb, 1, x->kf0, x->Wf, x->spec_out + (size_t)(24 + 4 * which) * nb);
+}
+
+int nq_diagnostics_binned(nq_ctx* c, int nb, double* out) {
+  NQ_SINGLE_RANK(c, "nq_diagnostics_binned");
+  if (!out) NQ_FAIL(c, -1, "nq_diagnostics_binned: null output");
+  if (nb != nq_shell_count(c->N)) NQ_FAIL(c, -1, "nq_diagnostics_binned: nb = %d, the grid has %d shells", nb, nq_shell_count(c->N));
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool waves = c->kernel_family;
+  if (waves && !c->have_phi) NQ_FAIL(c, -4, "nq_diagnostics_binned: set_phi has not been called");
+  {
+    const int rc = bin_local_spectral(c, nb);
+    if (rc) return rc;
+  }
+  if (waves) {
+    // [24], [27] from F[u phix + v phiy], [28], [31] from i F[phi q_psi]: the tick's two products passes
+    for (int which = 0; which < 2; ++which) {
+      launch_products(c, which == 0 ? 1.0 : 0.0, which == 0 ? 0.0 : 1.0);
+      launch_A_m(c, false, {&c->mW});
+      bin_local_project(c, nb, which);
+    }
+  }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, c->spec_out, sizeof(double) * 32 * nb, hipMemcpyDeviceToHost, c->stream));
+  return nq_sync(c);
+}
+
+// the same on a slab-decomposed simulation (collective, like nq_slab_diagnostics): every context of this process bins its own
+// columns, the products passes exchange as the tick's do, and the contexts of this process are summed in rank order on the host
+// (peers: all ranks -- the whole result; one rank per process: that rank's part, which the caller gathers and sums in rank order)
+int nq_slab_diagnostics_binned(nq_ctx* c, int nb, double* out) {
+  if (!c || !out) return -1;
+  if (nb != nq_shell_count(c->N)) NQ_FAIL(c, -1, "nq_slab_diagnostics_binned: nb = %d, the grid has %d shells", nb, nq_shell_count(c->N));
+  std::vector<nq_ctx*> grp;
+  SLABTRY(slab_group(c, &grp));
+  SLABTRY(slab_settle(grp));
+  const bool waves = grp[0]->kernel_family;
+  for (nq_ctx* x : each(grp)) {
+    HIPCHK(x, hipSetDevice(x->device));
+    if (waves && !x->have_phi) NQ_FAIL(x, -4, "nq_slab_diagnostics_binned: set_phi has not been called");
+    SLABTRY(bin_local_spectral(x, nb));
+  }
+  if (waves) {
+    for (int which = 0; which < 2; ++which) {
+      for (nq_ctx* x : each(grp)) launch_products(x, which == 0 ? 1.0 : 0.0, which == 0 ? 0.0 : 1.0);
+      SLABTRY(exchange_now(grp, 0, true));
+      for (nq_ctx* x : each(grp)) {
+        launch_A_m(x, false, {&x->mW});
+        if (x->Wf > 0) bin_local_project(x, nb, which);
+      }
+    }
+  }
+  std::vector<double> part((size_t)32 * nb);
+  for (size_t i = 0; i < part.size(); ++i) out[i] = 0.0;
+  for (nq_ctx* x : grp) {                               // rank order
+    HIPCHK(x, hipSetDevice(x->device));
+    HIPCHK(x, hipGetLastError());
+    HIPCHK(x, hipMemcpyAsync(part.data(), x->spec_out, sizeof(double) * part.size(), hipMemcpyDeviceToHost, x->stream));
+    SLABTRY(nq_sync(x));
+    for (size_t i = 0; i < part.size(); ++i) out[i] += part[i];
+  }
+  return 0;
+}
+
 // fft(phi * q_psi), (ny, nx): the refraction source of ref Kernel.py:332, :350, :367, :385 before its -0.5j factor,
 // formed by the row kernel exactly as inside a step (mean NOT removed)
 int nq_refraction(nq_ctx* c, double* out_cplx) {
@@ -4192,6 +4486,23 @@ int nq_any_take_cols(nq_any* e, void* dst, const void* src, int rows, int scols,
   if (!e || !dst || !src || rows < 1 || dcols < 1 || dcols > scols) return -1;
   hipLaunchKernelGGL(k_any_take_cols, dim3((dcols + 63) / 64, rows), dim3(64), 0, e->stream, reinterpret_cast<const cd*>(src), reinterpret_cast<cd*>(dst), rows, scols, dcols);
   return 0;
+}
+// isotropic shell sums of Re(plane): layout 0 a full (rows, rows) plane in fftfreq order, 1 an rfft half plane (rows, rows/2+1);
+// out: nb = round(rows / sqrt 2) + 1 doubles, the shell rule of nq_diagnostics_binned, deterministic (no atomics)
+int nq_any_bin(nq_any* e, const void* plane, int rows, int cols, int layout, int nb, double* out) {
+  if (!e || !plane || !out || rows < 2 || (rows & 1)) return -1;
+  if (layout != 0 && layout != 1) ANYFAIL(e, -1, "nq_any_bin: layout %d (0: full plane, 1: half plane)", layout);
+  if (cols != (layout == 0 ? rows : rows / 2 + 1)) ANYFAIL(e, -1, "nq_any_bin: %d columns for a %s plane of %d rows", cols, layout == 0 ? "full" : "half", rows);
+  if (nb != nq_shell_count(rows)) ANYFAIL(e, -1, "nq_any_bin: nb = %d, the grid has %d shells", nb, nq_shell_count(rows));
+  ANYCHK(e, hipSetDevice(e->device));
+  double* d = nullptr;
+  AnyScratch tmp;
+  ANYCHK(e, tmp.get(&d, (size_t)nb));
+  const AnyBinRe t{reinterpret_cast<const cd*>(plane), cols};
+  hipLaunchKernelGGL(k_bin_shells<AnyBinRe>, dim3(nb), dim3(256), 0, e->stream, t, rows, nb, layout == 0 ? 1 : 0, 0, cols, d);
+  ANYCHK(e, hipGetLastError());
+  ANYCHK(e, hipMemcpyAsync(out, d, sizeof(double) * nb, hipMemcpyDeviceToHost, e->stream));
+  return nq_any_sync(e);
 }
 int nq_any_set_elem(nq_any* e, void* plane, long long index, double re, double im) {
   if (!e || !plane || index < 0) return -1;

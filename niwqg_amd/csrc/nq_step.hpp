@@ -1106,6 +1106,43 @@ k_s_project(MArr Hw, const cd* __restrict__ phih, YGeom g, const double* __restr
   block_sum_store<4>(s, red, part + 4 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x));
 }
 
+// ---- isotropic spectra of the tick (nq_diagnostics_binned): k_s_project's two binned terms written out per element ----------
+// The same B-fft and the same products as k_s_project, but instead of workgroup sums each element's -wv2 Re(conj(phih) a) goes
+// to rlap[l][k] and -(nu4w wv4 + nuw wv2 + muw) Im(conj(phih) a) to rdiss[l][k] (real planes of the local columns, row pitch
+// rpitch); a shell
+// binning kernel then sums them.
+template <int S1, int CLX = CL>
+__global__ void __launch_bounds__((YPlanT<S1, CLX>::THREADS))
+k_s_project_bin(MArr Hw, const cd* __restrict__ phih, YGeom g, const double* __restrict__ kk, const double* __restrict__ ll,
+                const cd* __restrict__ tw, int tw_step_N, double nu4w, double nuw, double muw, double* __restrict__ rlap,
+                double* __restrict__ rdiss, int rpitch) {
+  typedef YPlanT<S1, CLX> Y;
+  constexpr int P = Y::P, T = Y::T;
+  const int c = threadIdx.x % CLX, j = threadIdx.x / CLX;
+  const int k = blockIdx.x * CLX + c, l1 = blockIdx.y;
+  const int kg = g.k0 + k, S2 = g.S2;
+  const int N = S1 * S2;
+  cd* lds = reinterpret_cast<cd*>(nq_smem);
+  typename Y::F::Tw twr;
+  Y::F::load_tw(twr, j, tw, tw_step_N * (N / S1));
+  cd a[P];
+#pragma unroll
+  for (int t = 0; t < P; ++t) a[t] = Hw.ys[(size_t)(l1 * S1 + j + t * T) * Hw.pitch + k];
+  Y::F::template run<false>(a, j, c, lds, twr);
+  const double kx = kk[kg];
+#pragma unroll
+  for (int t = 0; t < P; ++t) {
+    const int l = l1 + S2 * (j + t * T);
+    const cd ys = phih[(size_t)l * g.pitch_s + k];
+    const double ly = ll[l];
+    const double wv2 = kx * kx + ly * ly;
+    const double d = nu4w * wv2 * wv2 + nuw * wv2 + muw;
+    const double re = ys.x * a[t].x + ys.y * a[t].y, im = ys.x * a[t].y - ys.y * a[t].x;   // conj(ys) * a
+    rlap[(size_t)l * rpitch + k] = -wv2 * re;
+    rdiss[(size_t)l * rpitch + k] = -d * im;
+  }
+}
+
 // ---- diagnostics tick of QGModel's passive scalar: Gamma_c = 2 mean(lap c * J(psi, c)) (ref QGModel.py:727-731) by Parseval ----
 // part[workgroup] = sum over the tile of w * Re(conj(-wv2 c-hat) * (i k F[u c] + i l F[v c])), w = 1 on the two self-mirrored
 // columns, 2 elsewhere; Huc, Hvc already went through the A sub-pass.

@@ -330,6 +330,22 @@ class SlabSimulation(object):
         self._lead_chk(self.L.nq_slab_diagnostics(self.lead.h, _lib._dptr(out)), "nq_slab_diagnostics")
         return out
 
+    def diagnostics_binned(self):
+        """nq_slab_diagnostics_binned, (32, nb): this process's ranks summed in rank order by the library; with one rank per
+        process every rank's part is all-gathered and summed in rank order, so that every rank returns the same array"""
+        nb = int(self.L.nq_spectrum_shells(self.lead.h))
+        out = np.zeros((32, nb))
+        self._lead_chk(self.L.nq_slab_diagnostics_binned(self.lead.h, nb, _lib._dptr(out)), "nq_slab_diagnostics_binned")
+        if self.link in ("peers", "null"):
+            return out
+        self.sync()            # the library's streams are drained before torch's communicator runs
+        parts = [None] * self.nranks
+        self.dist.all_gather_object(parts, out)
+        tot = np.zeros_like(out)
+        for p in parts:        # rank order
+            tot += p
+        return tot
+
     def max_over_ranks(self, values):
         """element-wise max over all ranks of the simulation of a small vector this process computed for its ranks"""
         v = np.max(np.asarray(values, float).reshape(len(self.ranks), -1), axis=0)
@@ -529,6 +545,9 @@ class SlabContext(object):
 
     def qh_passenger(self):
         return self.sim.gather_qh_passenger()
+
+    def diagnostic_sums_binned(self):
+        return self.sim.diagnostics_binned()
 
     def diagnostic_sums(self):
         if self._ds is None:
