@@ -368,7 +368,7 @@ void* nq_stream(nq_ctx* ctx);
 
 /* ---- the any-size engine: grids without a fused plan -----------------------------------------------------------------------
  * The reference takes any nx (niwqg/Kernel.py:100-103; numpy.fft transforms any length, :562-566; QGModel.py:93-96, :551-552).
- * The fused step above exists for powers of two in [64, 8192].  For every other even nx in [4, 4096] the model classes run the
+ * The fused step above exists for powers of two in [64, 8192].  For every other even nx in [4, 8192] the model classes run the
  * reference's own sequence of whole-plane operations (niwqg_amd/_anysize.py) on device planes through these calls: 1-D transforms
  * of any length along either axis (Bluestein's chirp-z identity on the power-of-two row engine), element-wise operations,
  * deterministic reductions.  Planes are contiguous arrays of complex128 owned by the engine; everything is asynchronous on the
@@ -402,8 +402,10 @@ int nq_any_alloc(nq_any* eng, long long elems, void** plane);                 /*
 int nq_any_free(nq_any* eng, void* plane, long long elems);
 int nq_any_upload(nq_any* eng, void* plane, const double* host_cplx, long long elems);
 int nq_any_download(nq_any* eng, const void* plane, double* host_cplx, long long elems);
-/* numpy.fft.fft / ifft along one axis of a (rows, cols) plane (axis 1: the contiguous index); dst may be src */
+/* numpy.fft.fft / ifft along one axis of a (rows, cols) plane (axis 1: the contiguous index); dst may be src.  Transform lengths:
+ * 1 to 8192, and 16384; any other length returns non-zero with nq_any_last_error set */
 int nq_any_fft(nq_any* eng, void* dst, const void* src, int rows, int cols, int axis, int inverse);
+/* operands the op does not read may be NULL; d may alias any operand */
 int nq_any_ew(nq_any* eng, int op, void* d, const void* a, const void* b, const void* c, long long elems, const double* scalars6);
 int nq_any_reduce(nq_any* eng, int op, const void* a, const void* b, long long elems, double* out2);
 /* (rows, n/2+1) -> (rows, n): full[l, n-k] = conj(half[-l, k]); project != 0 first takes the Hermitian part (in l) of columns 0

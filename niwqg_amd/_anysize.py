@@ -548,7 +548,7 @@ class KernelFamily(object):
 
     def _calc_cfl(self):            # ref: niwqg/Kernel.py:660-662
         d = self._d
-        return max(d["u"].absmax(), d["v"].absmax(), d["phi"].absmax()) * self.dt / self.dx
+        return float(np.max([d["u"].absmax(), d["v"].absmax(), d["phi"].absmax()])) * self.dt / self.dx   # NaN propagates (not max())
 
     def _status_cfl(self):
         return self._calc_cfl()
@@ -971,7 +971,7 @@ class QGFamily(object):
         self._uv_d()
         self._user.pop("u", None)
         self._user.pop("v", None)
-        return max(self._d["u"].absmax(), self._d["v"].absmax()) * self.dt / self.dx
+        return float(np.max([self._d["u"].absmax(), self._d["v"].absmax()])) * self.dt / self.dx      # NaN propagates (not max())
 
     # ---- isotropic spectra (niwqg_amd/spectra.py) -----------------------------------------------
     _bin = KernelFamily._bin

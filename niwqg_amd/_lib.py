@@ -323,7 +323,7 @@ class Context:
         reference's status line takes its CFL from after a step without a tick (ref niwqg/Kernel.py:594, :660-662, :364-368)"""
         uv = np.zeros(2)
         self._chk(self.L.nq_get_stage4_max(self.h, _dptr(uv)), "nq_get_stage4_max")
-        return max(uv[0], uv[1], self.scalar(S_MAX_PHI))
+        return float(np.max([uv[0], uv[1], self.scalar(S_MAX_PHI)]))      # (not max(): NaN anywhere must give NaN)
 
     # --- reads
     _REAL = (F_Q, F_P, F_U, F_V, F_QPSI, F_QW, F_C)

@@ -1,9 +1,11 @@
 // niwqg_amd: the any-size engine -- grids the fused kernels have no plan for.
 //
 // The reference takes any nx (ref niwqg/Kernel.py:100-103; numpy.fft transforms any length, :562-566).  The fused step of
-// nq_step.hpp exists for powers of two in [64, 8192]; for every other EVEN nx in [4, 4096] the model classes run the reference's
-// own sequence of whole-plane operations (niwqg_amd/_anysize.py) on device planes through this engine:
-//   * 1-D transforms of ANY length n along either axis of a (rows, cols) complex128 plane, numpy.fft conventions, by
+// nq_step.hpp exists for powers of two in [64, 8192]; for every other EVEN nx in [4, 8192], and for 16384, the model classes run
+// the reference's own sequence of whole-plane operations (niwqg_amd/_anysize.py) on device planes through this engine:
+//   * 1-D transforms along either axis of a (rows, cols) complex128 plane, numpy.fft conventions, of any length n in [1, 8192]
+//     and of 16384: powers of two >= 64 directly on the row engine (16384 as a four-step 128 x 128 transform), 3 m and 5 m
+//     (m a power of two in [64, 2048]) by a radix-3 / radix-5 split, length 1 as a copy, every other length by
 //     Bluestein's chirp-z identity on top of the power-of-two row engine (WgFft / k_x_c2c of length M >= 2n - 1):
 //         X[k] = w[k] sum_j (x[j] w[j]) conj(w[k - j]),   w[j] = exp(-i pi j^2 / n)
 //     pack (chirp multiply, zero padding, transposing for axis 0) -> FFT_M -> multiply by the transformed chirp -> IFFT_M ->
@@ -31,8 +33,8 @@ enum { RD_SUM = 0, RD_SUMABS2 = 1, RD_DOT = 2, RD_DOTC = 3, RD_MAXABS = 4, RD_WS
 // scalars: s[0..1] = s0, s[2..3] = s1, s[4..5] = s2 (complex)
 struct EwScalars { double s[6]; };
 
-__global__ void __launch_bounds__(256) k_any_ew(int op, cd* __restrict__ d, const cd* __restrict__ a, const cd* __restrict__ b,
-                                                const cd* __restrict__ c, size_t n, EwScalars sc) {
+// d may alias any operand (include/niwqg_amd.h: nq_any_ew), so no operand is __restrict__: element i is read before it is written
+__global__ void __launch_bounds__(256) k_any_ew(int op, cd* d, const cd* a, const cd* b, const cd* c, size_t n, EwScalars sc) {
   const cd s0 = cmake(sc.s[0], sc.s[1]), s1 = cmake(sc.s[2], sc.s[3]), s2 = cmake(sc.s[4], sc.s[5]);
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     cd r;
@@ -67,8 +69,8 @@ __global__ void __launch_bounds__(256) k_any_reduce1(int op, const cd* __restric
       case RD_SUMABS2: x += v.x * v.x + v.y * v.y; break;
       case RD_DOT: { const cd p = cmul(v, b[i]); x += p.x; y += p.y; } break;
       case RD_DOTC: { const cd p = cmul(cconj(v), b[i]); x += p.x; y += p.y; } break;
-      case RD_MAXABS: x = fmax(x, sqrt(v.x * v.x + v.y * v.y)); break;
-      case RD_MAXABSRE: x = fmax(x, fabs(v.x)); break;
+      case RD_MAXABS: x = nan_max(x, sqrt(v.x * v.x + v.y * v.y)); break;
+      case RD_MAXABSRE: x = nan_max(x, fabs(v.x)); break;
       case RD_WSUMABS2: x += b[i].x * (v.x * v.x + v.y * v.y); break;
     }
   }
@@ -79,7 +81,7 @@ __global__ void __launch_bounds__(256) k_any_reduce1(int op, const cd* __restric
   const bool mx = (op == RD_MAXABS || op == RD_MAXABSRE);
   for (int s = 128; s > 0; s >>= 1) {
     if ((int)threadIdx.x < s) {
-      sx[threadIdx.x] = mx ? fmax(sx[threadIdx.x], sx[threadIdx.x + s]) : sx[threadIdx.x] + sx[threadIdx.x + s];
+      sx[threadIdx.x] = mx ? nan_max(sx[threadIdx.x], sx[threadIdx.x + s]) : sx[threadIdx.x] + sx[threadIdx.x + s];
       sy[threadIdx.x] += sy[threadIdx.x + s];
     }
     __syncthreads();
@@ -95,7 +97,7 @@ __global__ void __launch_bounds__(256) k_any_reduce2(int op, const double* __res
   const bool mx = (op == RD_MAXABS || op == RD_MAXABSRE);
   double x = 0.0, y = 0.0;
   for (int i = threadIdx.x; i < nblocks; i += 256) {
-    x = mx ? fmax(x, part[2 * i]) : x + part[2 * i];
+    x = mx ? nan_max(x, part[2 * i]) : x + part[2 * i];
     y += part[2 * i + 1];
   }
   __shared__ double sx[256], sy[256];
@@ -104,7 +106,7 @@ __global__ void __launch_bounds__(256) k_any_reduce2(int op, const double* __res
   __syncthreads();
   for (int s = 128; s > 0; s >>= 1) {
     if ((int)threadIdx.x < s) {
-      sx[threadIdx.x] = mx ? fmax(sx[threadIdx.x], sx[threadIdx.x + s]) : sx[threadIdx.x] + sx[threadIdx.x + s];
+      sx[threadIdx.x] = mx ? nan_max(sx[threadIdx.x], sx[threadIdx.x + s]) : sx[threadIdx.x] + sx[threadIdx.x + s];
       sy[threadIdx.x] += sy[threadIdx.x + s];
     }
     __syncthreads();

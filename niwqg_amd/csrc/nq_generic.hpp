@@ -64,6 +64,10 @@ template <int N> using XPlan1 = XPlanT<N, NQ_XP1, 2, 16>;
 
 extern __shared__ __attribute__((aligned(16))) unsigned char nq_smem[];
 
+// max that propagates NaN from either operand (fmax returns the other one): the CFL maxima of a status line must be NaN when
+// any element is, as numpy's max is (ref niwqg/Kernel.py:598 then stops the run).  Equal to fmax on non-NaN operands.
+__device__ __forceinline__ double nan_max(double a, double b) { return (a != a || a > b) ? a : b; }
+
 // Sum NV per-thread values over the workgroup and let thread 0 store them at dst[0..NV) (one slot per
 // workgroup: deterministic, no atomics; a later kernel adds the slots up).  `scratch` = 512 B of LDS.
 template <int NV>

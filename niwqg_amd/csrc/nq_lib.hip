@@ -398,7 +398,8 @@ __global__ void k_avg_interior_g(const cd* __restrict__ a, const cd* __restrict_
 // kind 0: sum |a|^2 (complex plane, width N)       -> out[0]
 // kind 1: sum weight_k * wv2 * |a|^2 (half spectrum psi -> 2*ke_qg*M^2), skipping [0,0]
 // kind 2: sum wv2 * |a|^2 (full complex plane)
-// kind 3: max |a| over complex plane (out[0] as max via atomicMax on bits, values >= 0)
+// kind 3: max |a| over complex plane (out[0] as max via atomicMax on bits, values >= 0).  NaN propagates (nan_max): a NaN
+//         with either sign bit orders above +inf as an unsigned bit pattern, so the atomicMax keeps it too
 __global__ void k_reduce(const cd* __restrict__ a, int width, int pitch, int N, int kind, const double* __restrict__ kk,
                          const double* __restrict__ ll, double* out) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x, l = blockIdx.y;
@@ -421,7 +422,7 @@ __global__ void k_reduce(const cd* __restrict__ a, int width, int pitch, int N, 
   sh[threadIdx.x] = v;
   __syncthreads();
   for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) sh[threadIdx.x] = (kind == 3) ? fmax(sh[threadIdx.x], sh[threadIdx.x + s]) : sh[threadIdx.x] + sh[threadIdx.x + s];
+    if (threadIdx.x < s) sh[threadIdx.x] = (kind == 3) ? nan_max(sh[threadIdx.x], sh[threadIdx.x + s]) : sh[threadIdx.x] + sh[threadIdx.x + s];
     __syncthreads();
   }
   if (threadIdx.x == 0) {
@@ -429,14 +430,15 @@ __global__ void k_reduce(const cd* __restrict__ a, int width, int pitch, int N, 
     else atomicAdd(out, sh[0]);
   }
 }
+// max |a| of a real plane into out[0] (atomicMax on bits as kind 3 of k_reduce: NaN propagates)
 __global__ void k_reduce_real_max(const double* __restrict__ a, size_t n, double* out) {
   double v = 0.0;
-  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) v = fmax(v, fabs(a[i]));
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) v = nan_max(v, fabs(a[i]));
   __shared__ double sh[256];
   sh[threadIdx.x] = v;
   __syncthreads();
   for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-    if (threadIdx.x < s) sh[threadIdx.x] = fmax(sh[threadIdx.x], sh[threadIdx.x + s]);
+    if (threadIdx.x < s) sh[threadIdx.x] = nan_max(sh[threadIdx.x], sh[threadIdx.x + s]);
     __syncthreads();
   }
   if (threadIdx.x == 0) atomicMax(reinterpret_cast<unsigned long long*>(out), (unsigned long long)__double_as_longlong(sh[0]));
@@ -4202,14 +4204,35 @@ static int any_tmp(nq_any* e, size_t elems, bool four_step = false) {
   if (rc == 0 && four_step) rc = any_buf(e, &e->tmp2, &e->tmp2_elems, elems);
   return rc;
 }
+static void any_plan_free(nq_any::Plan& p) {
+  for (nq::cd** q : {&p.chirp, &p.bhat, &p.tw, &p.tw_small})
+    if (*q) {
+      (void)hipFree(*q);
+      *q = nullptr;
+    }
+}
+static int any_plan_build(nq_any* e, int n, nq_any::Plan& pl);
 // Bluestein plan for transforms of length n: chirp w[j] = exp(-i pi j^2 / n) (angle reduced exactly: j^2 mod 2n), the transform of
-// conj(w) laid out circularly on M >= 2n - 1 points, and the twiddle table of the M-point row engine
+// conj(w) laid out circularly on M >= 2n - 1 points, and the twiddle table of the M-point row engine.  A plan that fails half
+// way frees what it allocated (after the work queued on e->stream that may still read its host vectors or e->tmp is done).
 static int any_plan(nq_any* e, int n, const nq_any::Plan** out) {
   for (const nq_any::Plan& p : e->plans)
     if (p.n == n) { *out = &p; return 0; }
   const bool pow2 = n >= 64 && (n & (n - 1)) == 0;
-  if (n < 2 || (pow2 ? n > 16384 : n > 8192)) ANYFAIL(e, -2, "any-size engine: transform length %d (any n in [2, 8192], or 16384)", n);
+  if (n < 2 || (pow2 ? n > 16384 : n > 8192)) ANYFAIL(e, -2, "any-size engine: transform length %d (any n in [1, 8192], or 16384)", n);
   nq_any::Plan pl;
+  const int rc = any_plan_build(e, n, pl);
+  if (rc) {
+    (void)hipStreamSynchronize(e->stream);
+    any_plan_free(pl);
+    return rc;
+  }
+  e->plans.push_back(pl);
+  *out = &e->plans.back();
+  return 0;
+}
+static int any_plan_build(nq_any* e, int n, nq_any::Plan& pl) {
+  const bool pow2 = n >= 64 && (n & (n - 1)) == 0;
   pl.n = n;
   pl.direct = pow2;
   pl.M = 64;
@@ -4279,14 +4302,15 @@ static int any_plan(nq_any* e, int n, const nq_any::Plan** out) {
     ANYCHK(e, hipMemcpy(pl.chirp, w.data(), sizeof(cd) * n, hipMemcpyHostToDevice));
     int rc = any_tmp(e, (size_t)M, M == 16384);
     if (rc) return rc;
-    ANYCHK(e, hipMemcpy(e->tmp, b.data(), sizeof(cd) * M, hipMemcpyHostToDevice));
+    // e->tmp may still be read by transforms queued before this call: the upload goes in stream order (the synchronisation
+    // below keeps b alive until it is done)
+    ANYCHK(e, hipMemcpyAsync(e->tmp, b.data(), sizeof(cd) * M, hipMemcpyHostToDevice, e->stream));
     rc = any_rows_fft<false>(e, pl, 1, 1.0);
     if (rc) return rc;
     ANYCHK(e, hipMemcpyAsync(pl.bhat, e->tmp, sizeof(cd) * M, hipMemcpyDeviceToDevice, e->stream));
     ANYCHK(e, hipStreamSynchronize(e->stream));
+    ANYCHK(e, hipGetLastError());
   }
-  e->plans.push_back(pl);
-  *out = &e->plans.back();
   return 0;
 }
 
@@ -4332,6 +4356,7 @@ int nq_any_destroy(nq_any* e) {
 const char* nq_any_last_error(const nq_any* e) { return e ? e->err.c_str() : g_last_error.c_str(); }
 int nq_any_sync(nq_any* e) {
   if (!e) return -1;
+  ANYCHK(e, hipSetDevice(e->device));
   ANYCHK(e, hipStreamSynchronize(e->stream));
   ANYCHK(e, hipGetLastError());
   return 0;
@@ -4350,6 +4375,7 @@ int nq_any_alloc(nq_any* e, long long elems, void** plane) {
 }
 int nq_any_free(nq_any* e, void* plane, long long elems) {
   if (!e || !plane) return -1;
+  ANYCHK(e, hipSetDevice(e->device));
   for (size_t i = 0; i < e->allocs.size(); ++i)
     if (e->allocs[i] == plane) {
       ANYCHK(e, hipStreamSynchronize(e->stream));
@@ -4362,20 +4388,26 @@ int nq_any_free(nq_any* e, void* plane, long long elems) {
 }
 int nq_any_upload(nq_any* e, void* plane, const double* host_cplx, long long elems) {
   if (!e || !plane || !host_cplx || elems <= 0) return -1;
+  ANYCHK(e, hipSetDevice(e->device));
   ANYCHK(e, hipMemcpyAsync(plane, host_cplx, (size_t)elems * sizeof(cd), hipMemcpyHostToDevice, e->stream));
   return nq_any_sync(e);
 }
 int nq_any_download(nq_any* e, const void* plane, double* host_cplx, long long elems) {
   if (!e || !plane || !host_cplx || elems <= 0) return -1;
+  ANYCHK(e, hipSetDevice(e->device));
   ANYCHK(e, hipMemcpyAsync(host_cplx, plane, (size_t)elems * sizeof(cd), hipMemcpyDeviceToHost, e->stream));
   return nq_any_sync(e);
 }
 // dst <- 1-D transforms of src along `axis` (1: along the contiguous index, length cols; 0: length rows), numpy.fft conventions
-// (forward unnormalised, inverse scaled by 1/n); dst may be src
+// (forward unnormalised, inverse scaled by 1/n; length 1 is the identity); dst may be src
 int nq_any_fft(nq_any* e, void* dst, const void* src, int rows, int cols, int axis, int inverse) {
   if (!e || !dst || !src || rows < 1 || cols < 1 || (axis != 0 && axis != 1)) return -1;
   ANYCHK(e, hipSetDevice(e->device));
   const int n = axis == 1 ? cols : rows, nlines = axis == 1 ? rows : cols;
+  if (n == 1) {
+    if (dst != src) ANYCHK(e, hipMemcpyAsync(dst, src, (size_t)rows * cols * sizeof(cd), hipMemcpyDeviceToDevice, e->stream));
+    return 0;
+  }
   const nq_any::Plan* pl = nullptr;
   int rc = any_plan(e, n, &pl);
   if (rc) return rc;
@@ -4456,18 +4488,21 @@ int nq_any_ew(nq_any* e, int op, void* d, const void* a, const void* b, const vo
   const bool need_b = (op == EW_MUL || op == EW_MULCONJ || op == EW_AXPBY || op == EW_AXPBYPCZ || op == EW_MULADD);
   const bool need_c = (op == EW_AXPBYPCZ || op == EW_MULADD);
   if ((need_b && !b) || (need_c && !c)) ANYFAIL(e, -1, "nq_any_ew: op %d needs more operands", op);
+  ANYCHK(e, hipSetDevice(e->device));
   EwScalars sc;
   for (int i = 0; i < 6; ++i) sc.s[i] = scalars6 ? scalars6[i] : (i == 0 ? 1.0 : 0.0);
   const size_t n = (size_t)elems;
   const int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
   hipLaunchKernelGGL(k_any_ew, dim3(grid), dim3(256), 0, e->stream, op, reinterpret_cast<cd*>(d), reinterpret_cast<const cd*>(a),
                      reinterpret_cast<const cd*>(b), reinterpret_cast<const cd*>(c), n, sc);
+  ANYCHK(e, hipGetLastError());
   return 0;
 }
 // out2 <- reduction over `elems` complex values (NQ_RD_*): deterministic (fixed grid, partials added in order)
 int nq_any_reduce(nq_any* e, int op, const void* a, const void* b, long long elems, double* out2) {
   if (!e || !a || !out2 || elems <= 0 || op < 0 || op > RD_MAXABSRE) return -1;
   if ((op == RD_DOT || op == RD_DOTC || op == RD_WSUMABS2) && !b) ANYFAIL(e, -1, "nq_any_reduce: op %d needs two operands", op);
+  ANYCHK(e, hipSetDevice(e->device));
   const size_t n = (size_t)elems;
   const int grid = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
   hipLaunchKernelGGL(k_any_reduce1, dim3(grid), dim3(256), 0, e->stream, op, reinterpret_cast<const cd*>(a), reinterpret_cast<const cd*>(b), n, e->part);
@@ -4478,13 +4513,17 @@ int nq_any_reduce(nq_any* e, int op, const void* a, const void* b, long long ele
 // (rows, n/2+1) half spectrum -> (rows, n) Hermitian extension; project: Hermitian part (in l) of the two self-mirrored columns first
 int nq_any_expand_half(nq_any* e, void* full, const void* half, int rows, int n, int project) {
   if (!e || !full || !half || rows < 1 || n < 2 || (n & 1)) return -1;
+  ANYCHK(e, hipSetDevice(e->device));
   hipLaunchKernelGGL(k_any_expand_half, dim3((n + 63) / 64, rows), dim3(64), 0, e->stream, reinterpret_cast<const cd*>(half), reinterpret_cast<cd*>(full), rows, n, project);
+  ANYCHK(e, hipGetLastError());
   return 0;
 }
 // the first dcols columns of a (rows, scols) plane as a (rows, dcols) plane
 int nq_any_take_cols(nq_any* e, void* dst, const void* src, int rows, int scols, int dcols) {
   if (!e || !dst || !src || rows < 1 || dcols < 1 || dcols > scols) return -1;
+  ANYCHK(e, hipSetDevice(e->device));
   hipLaunchKernelGGL(k_any_take_cols, dim3((dcols + 63) / 64, rows), dim3(64), 0, e->stream, reinterpret_cast<const cd*>(src), reinterpret_cast<cd*>(dst), rows, scols, dcols);
+  ANYCHK(e, hipGetLastError());
   return 0;
 }
 // isotropic shell sums of Re(plane): layout 0 a full (rows, rows) plane in fftfreq order, 1 an rfft half plane (rows, rows/2+1);
@@ -4506,7 +4545,9 @@ int nq_any_bin(nq_any* e, const void* plane, int rows, int cols, int layout, int
 }
 int nq_any_set_elem(nq_any* e, void* plane, long long index, double re, double im) {
   if (!e || !plane || index < 0) return -1;
+  ANYCHK(e, hipSetDevice(e->device));
   hipLaunchKernelGGL(k_any_set_elem, dim3(1), dim3(1), 0, e->stream, reinterpret_cast<cd*>(plane), (size_t)index, re, im);
+  ANYCHK(e, hipGetLastError());
   return 0;
 }
 // ETDRK4 planes of the linear operator c(l, k) on the whole (n, cols) plane, no filter folded in (the any-size path multiplies by
@@ -4556,6 +4597,7 @@ int nq_any_etdrk4(nq_any* e, int eq, const nq_params* p, const double* kk, const
 int nq_any_etdrk4_patch(nq_any* e, void* const* out6, int cols, int count, const int* l, const int* k, const double* vals) {
   if (!e || !out6 || count < 0 || (count > 0 && (!l || !k || !vals))) return -1;
   if (count == 0) return 0;
+  ANYCHK(e, hipSetDevice(e->device));
   int *dl = nullptr, *dk = nullptr;
   cd* dv = nullptr;
   AnyScratch tmp;
