@@ -213,6 +213,21 @@ int nq_diagnostics(nq_ctx* ctx, double* out32);
 int nq_spectrum_shells(const nq_ctx* ctx);
 int nq_diagnostics_binned(nq_ctx* ctx, int nb, double* out);
 
+/* Spectral transfer: out[r * nb + b] = the RAW shell sum of row r over the wavenumbers of shell b, on
+ * the full plane of the reference (no signs, no 1/M^2; shells as nq_diagnostics_binned, nb = nq_spectrum_shells(ctx)).
+ * With P = F[psi], Q = F[q] (the q-hat the tick bins: the mean of the two copies on dual_q contexts), Jq = ik F[u q] +
+ * il F[v q], J = F[u phix + v phiy] and R = i F[phi q_psi] of the tick (phix, phiy as last refreshed: quirk Q1), C = F[c],
+ * Jc = ik F[u c] + il F[v c], u, v, q_psi of the current state:
+ *   [0] sum Re(conj(P) Jq)      [1] sum Re(conj(Q) Jq)          (CoupledModel, UnCoupledModel, QGModel; zero for YBJModel)
+ *   [2] sum Re(conj(phih) J)    [3] sum Re(conj(phih) R)        (Kernel family)
+ *   [4] sum Re(conj(C) Jc)      [5] sum wv2 Re(conj(C) Jc)      (QGModel with its passive scalar)
+ * every other row is zero.  Deterministic (no floating-point atomics: one workgroup per shell).  The products passes the tick
+ * runs (J, then R; the first also gives F[u q], F[v q] and F[u c], F[v c]) are run again into scratch planes; nothing else a
+ * step or a later call reads is touched.  Slab contexts allocate their planes on the first call (counted by nq_device_bytes).
+ * Single-rank contexts; nq_slab_transfer_binned below for slabs.                                                            */
+#define NQ_TRANSFER_ROWS 6
+int nq_transfer_binned(nq_ctx* ctx, int nb, double* out);
+
 /* copy of one ETDRK4 coefficient plane (0:E 1:Eh 2:Q 3:f0 4:fab 5:fc) of equation eq (0: q, (nx, nx/2+1) complex;
  * 1: phi, (nx, nx) complex; 2: QGModel's passive scalar, (nx, nx/2+1)), without the filter folded in; values as the
  * reference's expch, expch_h, Qh, f0, fab, fc (Kernel.py:417-454, QGModel.py:426-461).                           */
@@ -331,6 +346,10 @@ int nq_slab_diagnostics(nq_ctx* ctx, double* out32);
  * peer ranks in one process give the whole (32, nb) array; with one rank per process the result is that rank's part, which
  * the caller gathers (all_gather) and sums in rank order, so that every rank holds the same array. */
 int nq_slab_diagnostics_binned(nq_ctx* ctx, int nb, double* out);
+/* nq_transfer_binned of a slab-decomposed simulation (collective): every context bins its own columns, the products passes
+ * exchange as the tick's do, and the ranks are summed in rank order exactly as nq_slab_diagnostics_binned does
+ * (NQ_TRANSFER_ROWS x nb doubles; with one rank per process the caller gathers and sums the parts in rank order). */
+int nq_slab_transfer_binned(nq_ctx* ctx, int nb, double* out);
 int nq_slab_local_max(nq_ctx* ctx, double* out3);
 /* counters since the last reset: out[0] host calls of nq_slab_step, [1] steps, [2] exchange chunks issued, [3] bytes this
  * rank sent to OTHER ranks, [4] milliseconds the exchange stream spent in exchanges (HIP events; 0 unless timing was

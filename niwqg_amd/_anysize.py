@@ -685,6 +685,38 @@ class KernelFamily(object):
                     out["xi_a"] = self._bin(diss.conj() * R * (0.5 / M2f), 0)
         return out
 
+    # ---- spectral transfer (niwqg_amd/transfer.py) ----------------------------------------------
+    def _transfer(self, names):
+        """the named transfer spectra of the current state: the full-plane co-spectra of the definitions (psi-hat, q-hat, phi-hat
+        against Jq = ik F[u q] + il F[v q], J = F[u phix + v phiy], R = i F[phi q_psi]), formed from the planes this path holds
+        and binned on the device.  u, v, q_psi are formed locally: nothing this path keeps is written."""
+        d, K = self._d, self._K
+        M2 = float(self.M) ** 2
+        need = set(names)
+        out = {}
+        u = v = None
+        if need & {"ke_qg", "ens", "ke_niw_adv"}:
+            u, v = self._ifft(K["mil"] * d["ph"]).real, self._ifft(K["ik"] * d["ph"]).real
+        if need & {"ke_qg", "ens"}:
+            q = d["q"]
+            Jq = K["ik"] * self._fft(u * q) + K["il"] * self._fft(v * q)
+            if "ke_qg" in need:
+                out["ke_qg"] = self._bin(d["ph"].conj() * Jq / M2, 0)
+            if "ens" in need:
+                out["ens"] = self._bin(self._fft(q).conj() * Jq * (-1.0 / M2), 0)
+        phih = d["phih"]
+        if "ke_niw_adv" in need:
+            J = self._fft(u * d["phix"] + v * d["phiy"])
+            out["ke_niw_adv"] = self._bin(phih.conj() * J * (-1.0 / M2), 0)
+        if "ke_niw_ref" in need:
+            if self.model_id == _lib.COUPLED:
+                q_psi = d["q"] - self._ifft(d["qwh"]).real
+            else:
+                q_psi = d["q"]
+            FR = self._fft(d["phi"] * q_psi)                # R = i FR: -0.5 Re(conj(phih) R) = 0.5 Im(conj(phih) FR)
+            out["ke_niw_ref"] = self._bin((phih.conj() * FR).imag * (0.5 / M2), 0)
+        return out
+
     def _calc_ke_qg_decomp(self):   # ref: niwqg/CoupledModel.py:99-113
         d, K = self._d, self._K
         phq = K["mwv2i"] * d["qh"]
@@ -976,16 +1008,22 @@ class QGFamily(object):
     # ---- isotropic spectra (niwqg_amd/spectra.py) -----------------------------------------------
     _bin = KernelFamily._bin
 
+    def _half_weights(self):
+        """spec_var's weights with the mean included: a full-plane sum as a half-plane sum (2 on the interior columns, 1 on
+        the two self-mirrored ones)"""
+        K = self._K
+        if "_svw1" not in K:
+            w = np.full((self.nx, self.nx // 2 + 1), 2.0)
+            w[:, 0] = w[:, -1] = 1.0
+            K["_svw1"] = self._eng.plane(w)
+        return K["_svw1"]
+
     def _spectra(self, names):
         """as KernelFamily._spectra on the half planes of this class: weights w (2 on the interior columns, 1 on the two
         self-mirrored ones) folded into each term; products of a real field's rfft with any half plane are exact there"""
         d, K = self._d, self._K
         M2 = float(self.M) ** 2
-        if "_svw1" not in K:                          # spec_var's weights with the mean included
-            w = np.full((self.nx, self.nx // 2 + 1), 2.0)
-            w[:, 0] = w[:, -1] = 1.0
-            K["_svw1"] = self._eng.plane(w)
-        w1, sv = K["_svw1"], K["svw"]
+        w1, sv = self._half_weights(), K["svw"]
         need = set(names)
         out = {}
         if need & {"ens", "ep_psi"}:
@@ -1014,6 +1052,39 @@ class QGFamily(object):
             if "chi_c" in need:
                 t = w1 * (LC.conj() * (K["wv4"] * ch)) * (2 * self.nu4c) - lc2 * (2 * self.nu) - K["wv2"] * c2 * (2 * self.muc)
                 out["chi_c"] = self._bin(t / M2, 1)
+        return out
+
+    # ---- spectral transfer (niwqg_amd/transfer.py) ----------------------------------------------
+    def _transfer(self, names):
+        """as KernelFamily._transfer on the half planes of this class: weight 2 on the interior columns, 1 on the two
+        self-mirrored ones.  P, Q, C are the rffts of the REAL fields (Hermitian on those columns).  The full plane holds ly
+        with one sign for (nx/2, k) and its mirror (nx/2, -k), and kx with one sign down the column nx/2: those terms cancel in
+        pairs inside a shell, so that row of il and that column of ik enter as zero."""
+        d, K = self._d, self._K
+        M2 = float(self.M) ** 2
+        if "_ik0" not in K:
+            ik0, il0 = np.array(self.ik), np.array(self.il)
+            ik0[:, self.nx // 2] = 0.0
+            il0[self.nx // 2, :] = 0.0
+            K["_ik0"], K["_il0"] = self._eng.plane(ik0), self._eng.plane(il0)
+        w1, ik0, il0 = self._half_weights(), K["_ik0"], K["_il0"]
+        need = set(names)
+        out = {}
+        u, v = self._irfft(K["mil"] * d["ph"]), self._irfft(K["ik"] * d["ph"])
+        if need & {"ke_qg", "ens"}:
+            q = d["q"]
+            Jq = w1 * (ik0 * self._rfft(u * q) + il0 * self._rfft(v * q))
+            if "ke_qg" in need:
+                out["ke_qg"] = self._bin(self._rfft(d["p"]).conj() * Jq / M2, 1)
+            if "ens" in need:
+                out["ens"] = self._bin(self._rfft(q).conj() * Jq * (-1.0 / M2), 1)
+        if need & {"C2", "gradC2"}:
+            c = self._irfft(d["ch"])
+            t = self._rfft(c).conj() * (w1 * (ik0 * self._rfft(u * c) + il0 * self._rfft(v * c))) * (-2.0 / M2)
+            if "C2" in need:
+                out["C2"] = self._bin(t, 1)
+            if "gradC2" in need:
+                out["gradC2"] = self._bin(K["wv2"] * t, 1)
         return out
 
     def _calc_derived_fields(self):     # ref: niwqg/QGModel.py:724-737

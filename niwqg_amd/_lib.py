@@ -30,16 +30,18 @@ COUPLED, UNCOUPLED, QG, YBJ = 0, 1, 2, 3
 
 EXPORTS = ["nq_create", "nq_destroy", "nq_last_error", "nq_set_q", "nq_set_c", "nq_set_phi", "nq_invert", "nq_refresh_grad_phi",
            "nq_step", "nq_profile_stride", "nq_request_stage4_max", "nq_get_stage4_max", "nq_tick_snapshot", "nq_sync", "nq_get_field", "nq_get_qh_passenger", "nq_get_scalar", "nq_fft2", "nq_ifft2", "nq_rfft2",
-           "nq_irfft2", "nq_jacobian_psi_q", "nq_jacobian_psi_c", "nq_jacobian_psi_phi", "nq_jacobian_phic_phi", "nq_products_uq_vq", "nq_refraction", "nq_field_doubles", "nq_get_coeff", "nq_coeff_near_contour", "nq_coeff_patch", "nq_diagnostics", "nq_spectrum_shells", "nq_diagnostics_binned",
+           "nq_irfft2", "nq_jacobian_psi_q", "nq_jacobian_psi_c", "nq_jacobian_psi_phi", "nq_jacobian_phic_phi", "nq_products_uq_vq", "nq_refraction", "nq_field_doubles", "nq_get_coeff", "nq_coeff_near_contour", "nq_coeff_patch", "nq_diagnostics", "nq_spectrum_shells", "nq_diagnostics_binned", "nq_transfer_binned",
            "nq_stream_copy_gbs", "nq_timer_start", "nq_timer_stop", "nq_event_record", "nq_event_elapsed", "nq_profile_enable", "nq_profile_read", "nq_profile_read_all", "nq_group_elems", "nq_create_slab",
            "nq_slab_info", "nq_group_buffers", "nq_upload_spectral", "nq_download_spectral", "nq_phase",
            "nq_reduce_buffer", "nq_reduce_read", "nq_reduce_write", "nq_device_bytes", "nq_stream",
            "nq_comm_probe", "nq_comm_unique_id", "nq_comm_init", "nq_slab_attach_peers", "nq_slab_set_callbacks", "nq_slab_set_null_link", "nq_slab_config", "nq_slab_set_stage_buffers", "nq_slab_spectral", "nq_slab_spectral_read",
-           "nq_slab_step", "nq_slab_put_rows", "nq_slab_commit", "nq_slab_get_rows", "nq_slab_diagnostics", "nq_slab_diagnostics_binned",
+           "nq_slab_step", "nq_slab_put_rows", "nq_slab_commit", "nq_slab_get_rows", "nq_slab_diagnostics", "nq_slab_diagnostics_binned", "nq_slab_transfer_binned",
            "nq_slab_local_max", "nq_slab_counters", "nq_slab_allreduce_ms", "nq_snapshot_begin", "nq_snapshot_end",
            "nq_any_create", "nq_any_destroy", "nq_any_last_error", "nq_any_sync", "nq_any_device_bytes", "nq_any_alloc", "nq_any_free",
            "nq_any_upload", "nq_any_download", "nq_any_fft", "nq_any_ew", "nq_any_reduce", "nq_any_expand_half", "nq_any_take_cols",
            "nq_any_set_elem", "nq_any_bin", "nq_any_etdrk4", "nq_any_etdrk4_patch"]
+
+TRANSFER_ROWS = 6                 # rows of nq_transfer_binned (include/niwqg_amd.h: NQ_TRANSFER_ROWS)
 
 FUSED_SIZES = (64, 128, 256, 512, 1024, 2048, 4096, 8192)       # grids the fused ETDRK4 kernels have a plan for (csrc: NQ_FOR_SIZES)
 
@@ -117,6 +119,7 @@ def lib():
     L.nq_get_scalar.argtypes = [vp, ctypes.c_int, dp]
     L.nq_spectrum_shells.argtypes = [vp]
     L.nq_diagnostics_binned.argtypes = [vp, ctypes.c_int, dp]
+    L.nq_transfer_binned.argtypes = [vp, ctypes.c_int, dp]
     L.nq_get_coeff.argtypes = [vp, ctypes.c_int, ctypes.c_int, dp]
     L.nq_coeff_near_contour.argtypes = [vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     L.nq_coeff_patch.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, dp]
@@ -156,6 +159,7 @@ def lib():
     L.nq_slab_get_rows.argtypes = [vp, ctypes.c_int, dp]
     L.nq_slab_diagnostics.argtypes = [vp, dp]
     L.nq_slab_diagnostics_binned.argtypes = [vp, ctypes.c_int, dp]
+    L.nq_slab_transfer_binned.argtypes = [vp, ctypes.c_int, dp]
     L.nq_slab_local_max.argtypes = [vp, dp]
     L.nq_slab_counters.argtypes = [vp, dp, ctypes.c_int]
     L.nq_slab_allreduce_ms.argtypes = [vp, dp]
@@ -374,6 +378,13 @@ class Context:
         nb = int(self.L.nq_spectrum_shells(self.h))
         out = np.zeros((32, nb))
         self._chk(self.L.nq_diagnostics_binned(self.h, nb, _dptr(out)), "nq_diagnostics_binned")
+        return out
+
+    def transfer_sums_binned(self):
+        """Raw spectral-transfer shell sums, (TRANSFER_ROWS, nb) (include/niwqg_amd.h: nq_transfer_binned)"""
+        nb = int(self.L.nq_spectrum_shells(self.h))
+        out = np.zeros((TRANSFER_ROWS, nb))
+        self._chk(self.L.nq_transfer_binned(self.h, nb, _dptr(out)), "nq_transfer_binned")
         return out
 
     def coeff(self, eq, which):

@@ -119,6 +119,8 @@ struct nq_ctx {
   double *part0W = nullptr, *part0Q = nullptr;    // partials of set_phi / set_q / nq_invert
   double *diag_part = nullptr, *diag_out = nullptr;   // diagnostics tick: workgroup partials, 32 reduced sums
   double *spec_out = nullptr, *spec_r = nullptr;     // isotropic spectra of the tick: 32 x nb shell sums, two real planes
+  double* tr_out = nullptr;                          // spectral transfer: NQ_TRANSFER_ROWS x nb shell sums
+  cd *tr_h = nullptr, *tr_f = nullptr;               // its planes on slab contexts (two half, one full-width; P == 1: scr_*)
   double *carryW = nullptr, *carryQ = nullptr;    // spectral sums of the state at the start of the next step
   double *gradS1 = nullptr, *acc = nullptr;       // stale-aware sum wv2|phih_grad|^2 ; Ke,Pw,Kw increments
   double* bsums = nullptr;                        // [4 stages][11] reduced sums of one step
@@ -739,6 +741,76 @@ struct BinProj {
     const size_t idx = (size_t)l * pitch + kl;
     v[0] += rlap[idx];
     v[3] += rdiss[idx];
+  }
+};
+
+// spectral transfer (nq_transfer_binned) ---------------------------------------------------------
+// Re(conj X * (i kx a + i ly b)) of one half-spectrum element, with a = F[u s], b = F[v s] of a real field s: the co-spectrum of
+// X with the Jacobian J(psi, s) over the FULL plane, weight 2 on the interior columns standing for (l, k) and (-l, -k).  On the
+// two self-mirrored columns every factor is replaced by its Hermitian part (what the real fields' transforms hold) and the
+// weight is 1.  On the column k = N/2 and the row l = N/2 the full plane holds kx (ly) with ONE sign for an element and its
+// mirror, so their kx (ly) terms cancel in pairs inside the shell: those wavenumbers enter as 0.
+__device__ inline cd herm_part(cd x, cd xm) { return cmake(0.5 * (x.x + xm.x), 0.5 * (x.y - xm.y)); }
+struct HalfJac {
+  const cd *fu, *fv;
+  int N, pitch;
+  const double *kk, *ll;
+  // *wt: the element's weight; *x: X at the element (Hermitian part on the self-mirrored columns); returns (Re J, Im J)
+  __device__ cd at(const cd* X, int l, int k, int kl, double* wt, cd* x) const {
+    const size_t idx = (size_t)l * pitch + kl;
+    cd a = fu[idx], b = fv[idx];
+    *x = X[idx];
+    *wt = 2.0;
+    if (k == 0 || k == N / 2) {
+      *wt = 1.0;
+      const size_t im = (size_t)((N - l) % N) * pitch + kl;
+      a = herm_part(a, fu[im]);
+      b = herm_part(b, fv[im]);
+      *x = herm_part(*x, X[im]);
+    }
+    const double kx = (k == N / 2) ? 0.0 : kk[k], ly = (l == N / 2) ? 0.0 : ll[l];
+    return cmake(-(kx * a.y + ly * b.y), kx * a.x + ly * b.x);
+  }
+};
+// rows [0] Re(conj psi-hat Jq), [1] Re(conj q-hat Jq) with Jq = i k F[u q] + i l F[v q] (half spectrum; qh: the q-hat the tick
+// bins, i.e. the mean of the two copies on dual-copy contexts; the passenger row never reaches physical space and is not in it)
+struct BinTrQ {
+  static constexpr int NQ = 2;
+  HalfJac j;
+  const cd *ph, *qh;
+  __device__ void operator()(int l, int k, int kl, double* v) const {
+    double wt;
+    cd p, q;
+    const cd J = j.at(ph, l, k, kl, &wt, &p);
+    j.at(qh, l, k, kl, &wt, &q);
+    v[0] += wt * (p.x * J.x + p.y * J.y);
+    v[1] += wt * (q.x * J.x + q.y * J.y);
+  }
+};
+// rows [4] Re(conj c-hat Jc), [5] wv2 Re(conj c-hat Jc) with Jc = i k F[u c] + i l F[v c] (QGModel's passive scalar)
+struct BinTrC {
+  static constexpr int NQ = 2;
+  HalfJac j;
+  const cd* ch;
+  __device__ void operator()(int l, int k, int kl, double* v) const {
+    double wt;
+    cd c;
+    const cd J = j.at(ch, l, k, kl, &wt, &c);
+    const double kx = j.kk[k], ly = j.ll[l], t = wt * (c.x * J.x + c.y * J.y);
+    v[0] += t;
+    v[1] += (kx * kx + ly * ly) * t;
+  }
+};
+// rows [2] / [3]: Re(conj phi-hat a) of a full plane a (the J plane F[u phix + v phiy], then the R plane i F[phi q_psi])
+struct BinTrW {
+  static constexpr int NQ = 1;
+  const cd *phih, *a;
+  int pitch;
+  __device__ void operator()(int l, int k, int kl, double* v) const {
+    (void)k;
+    const size_t idx = (size_t)l * pitch + kl;
+    const cd z = phih[idx], w = a[idx];
+    v[0] += z.x * w.x + z.y * w.y;
   }
 };
 
@@ -4041,6 +4113,133 @@ int nq_slab_diagnostics_binned(nq_ctx* c, int nb, double* out) {
     HIPCHK(x, hipSetDevice(x->device));
     HIPCHK(x, hipGetLastError());
     HIPCHK(x, hipMemcpyAsync(part.data(), x->spec_out, sizeof(double) * part.size(), hipMemcpyDeviceToHost, x->stream));
+    SLABTRY(nq_sync(x));
+    for (size_t i = 0; i < part.size(); ++i) out[i] += part[i];
+  }
+  return 0;
+}
+
+// ---- spectral transfer -----------------------------------------------------------------------------
+// The tick's two products passes again: the first (c_J = 1, c_R = 0) gives F[u q], F[v q] (F[u c], F[v c] with QGModel's passive
+// scalar) and the J plane, the second (0, 1) the R plane.  Each is B-transformed into a scratch plane and binned against the
+// state's spectrum by k_bin_shells (BinTrQ, BinTrC, BinTrW).  Planes: scr_h0, scr_h1, scr_f0 on one rank (scr_f1: the mean of the
+// two q copies), tr_h, tr_f (scr_h1: the mean) on slab ranks, allocated on the first call.
+struct TrPlanes {
+  cd *h0, *h1, *f;
+  const cd* qh;
+};
+static int transfer_begin(nq_ctx* x, int nb, TrPlanes* t) {
+  const int N = x->N;
+  if (!x->tr_out) ALLOC(x, x->tr_out, (size_t)NQ_TRANSFER_ROWS * nb);
+  HIPCHK(x, hipMemsetAsync(x->tr_out, 0, sizeof(double) * NQ_TRANSFER_ROWS * nb, x->stream));
+  if (x->P == 1) {
+    t->h0 = x->scr_h0;
+    t->h1 = x->scr_h1;
+    t->f = x->scr_f0;
+  } else {
+    if (!x->ybj && !x->tr_h) ALLOC(x, x->tr_h, (size_t)2 * N * x->Ph);
+    if (x->kernel_family && !x->tr_f) ALLOC(x, x->tr_f, (size_t)N * x->Wf);
+    t->h0 = x->tr_h;
+    t->h1 = x->tr_h ? x->tr_h + (size_t)N * x->Ph : nullptr;
+    t->f = x->tr_f;
+  }
+  t->qh = x->q.y[x->q.cur];
+  if (x->dual && !x->ybj) {                           // the q-hat the tick bins: the mean of the two copies
+    if (x->P == 1) {
+      hipLaunchKernelGGL(k_avg_interior, dim3((x->Wh + 63) / 64, N), dim3(64), 0, x->stream, t->qh, (const cd*)x->q2.y[x->q2.cur], x->scr_f1, x->Wh, x->Ph, N);
+      t->qh = x->scr_f1;
+    } else {
+      if (!x->scr_h1) ALLOC(x, x->scr_h1, (size_t)N * x->Ph);
+      if (x->Wh > 0) hipLaunchKernelGGL(k_avg_interior_g, dim3((x->Wh + 63) / 64, N), dim3(64), 0, x->stream, t->qh, (const cd*)x->q2.y[x->q2.cur], x->scr_h1, x->Wh, x->Ph, N, x->kh0);
+      t->qh = x->scr_h1;
+    }
+  }
+  return 0;
+}
+// after the products pass `which` (0: J and the balanced / scalar products, 1: R) and its exchange: A sub-pass, B into the
+// scratch planes, bin into tr_out
+static void transfer_bin_pass(nq_ctx* x, int nb, int which, const TrPlanes& t) {
+  const int N = x->N;
+  const bool waves = x->kernel_family, balanced = !x->ybj, passive = !waves && x->passive;
+  double* d = x->tr_out;
+  if (which == 0) {
+    if (waves && balanced) launch_A_m(x, false, {&x->mUq, &x->mVq, &x->mW});
+    else if (waves) launch_A_m(x, false, {&x->mW});
+    else if (passive) launch_A_m(x, false, {&x->mUq, &x->mVq, &x->mUc, &x->mVc});
+    else launch_A_m(x, false, {&x->mUq, &x->mVq});
+    if (balanced && x->Wh > 0) {
+      launch_B_p(x, false, x->mUq.ys, x->mUq.pitch, t.h0, x->Ph, x->Wh, 1.0);
+      launch_B_p(x, false, x->mVq.ys, x->mVq.pitch, t.h1, x->Ph, x->Wh, 1.0);
+      const BinTrQ bq{HalfJac{t.h0, t.h1, N, x->Ph, x->kk, x->ll}, (const cd*)x->ph, t.qh};
+      hipLaunchKernelGGL(k_bin_shells<BinTrQ>, dim3(nb), dim3(256), 0, x->stream, bq, N, nb, 0, x->kh0, x->Wh, d);
+    }
+    if (passive && x->Wh > 0) {
+      launch_B_p(x, false, x->mUc.ys, x->mUc.pitch, t.h0, x->Ph, x->Wh, 1.0);
+      launch_B_p(x, false, x->mVc.ys, x->mVc.pitch, t.h1, x->Ph, x->Wh, 1.0);
+      const BinTrC bc{HalfJac{t.h0, t.h1, N, x->Ph, x->kk, x->ll}, (const cd*)x->cq.y[x->cq.cur]};
+      hipLaunchKernelGGL(k_bin_shells<BinTrC>, dim3(nb), dim3(256), 0, x->stream, bc, N, nb, 0, x->kh0, x->Wh, d + (size_t)4 * nb);
+    }
+  } else {
+    launch_A_m(x, false, {&x->mW});
+  }
+  if (waves && x->Wf > 0) {
+    launch_B_p(x, false, x->mW.ys, x->mW.pitch, t.f, x->Wf, x->Wf, 1.0);
+    const BinTrW bw{(const cd*)x->w.y[x->w.cur], t.f, x->Wf};
+    hipLaunchKernelGGL(k_bin_shells<BinTrW>, dim3(nb), dim3(256), 0, x->stream, bw, N, nb, 1, x->kf0, x->Wf, d + (size_t)(2 + which) * nb);
+  }
+}
+
+int nq_transfer_binned(nq_ctx* c, int nb, double* out) {
+  NQ_SINGLE_RANK(c, "nq_transfer_binned");
+  if (!out) NQ_FAIL(c, -1, "nq_transfer_binned: null output");
+  if (nb != nq_shell_count(c->N)) NQ_FAIL(c, -1, "nq_transfer_binned: nb = %d, the grid has %d shells", nb, nq_shell_count(c->N));
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool waves = c->kernel_family;
+  if (waves && !c->have_phi) NQ_FAIL(c, -4, "nq_transfer_binned: set_phi has not been called");
+  TrPlanes t;
+  SLABTRY(transfer_begin(c, nb, &t));
+  for (int which = 0; which < (waves ? 2 : 1); ++which) {
+    launch_products(c, which == 0 ? 1.0 : 0.0, which == 0 ? 0.0 : 1.0);
+    transfer_bin_pass(c, nb, which, t);
+  }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, c->tr_out, sizeof(double) * NQ_TRANSFER_ROWS * nb, hipMemcpyDeviceToHost, c->stream));
+  return nq_sync(c);
+}
+
+// collective, as nq_slab_diagnostics_binned: every context bins its own columns, the contexts of this process summed in rank order
+int nq_slab_transfer_binned(nq_ctx* c, int nb, double* out) {
+  if (!c || !out) return -1;
+  if (nb != nq_shell_count(c->N)) NQ_FAIL(c, -1, "nq_slab_transfer_binned: nb = %d, the grid has %d shells", nb, nq_shell_count(c->N));
+  std::vector<nq_ctx*> grp;
+  SLABTRY(slab_group(c, &grp));
+  SLABTRY(slab_settle(grp));
+  const bool waves = grp[0]->kernel_family;
+  std::vector<TrPlanes> t(grp.size());
+  for (size_t r = 0; r < grp.size(); ++r) {
+    nq_ctx* x = grp[r];
+    HIPCHK(x, hipSetDevice(x->device));
+    if (waves && !x->have_phi) NQ_FAIL(x, -4, "nq_slab_transfer_binned: set_phi has not been called");
+    SLABTRY(transfer_begin(x, nb, &t[r]));
+  }
+  for (int which = 0; which < (waves ? 2 : 1); ++which) {
+    for (nq_ctx* x : each(grp)) {
+      set_window(x, 0, 1);
+      launch_products(x, which == 0 ? 1.0 : 0.0, which == 0 ? 0.0 : 1.0);
+    }
+    SLABTRY(exchange_now(grp, 0, true));
+    for (size_t r = 0; r < grp.size(); ++r) {
+      nq_ctx* x = grp[r];
+      HIPCHK(x, hipSetDevice(x->device));
+      transfer_bin_pass(x, nb, which, t[r]);
+    }
+  }
+  std::vector<double> part((size_t)NQ_TRANSFER_ROWS * nb);
+  for (size_t i = 0; i < part.size(); ++i) out[i] = 0.0;
+  for (nq_ctx* x : grp) {                               // rank order
+    HIPCHK(x, hipSetDevice(x->device));
+    HIPCHK(x, hipGetLastError());
+    HIPCHK(x, hipMemcpyAsync(part.data(), x->tr_out, sizeof(double) * part.size(), hipMemcpyDeviceToHost, x->stream));
     SLABTRY(nq_sync(x));
     for (size_t i = 0; i < part.size(); ++i) out[i] += part[i];
   }

@@ -346,6 +346,21 @@ class SlabSimulation(object):
             tot += p
         return tot
 
+    def transfer_binned(self):
+        """nq_slab_transfer_binned, (TRANSFER_ROWS, nb): summed over the ranks in rank order as diagnostics_binned is"""
+        nb = int(self.L.nq_spectrum_shells(self.lead.h))
+        out = np.zeros((_lib.TRANSFER_ROWS, nb))
+        self._lead_chk(self.L.nq_slab_transfer_binned(self.lead.h, nb, _lib._dptr(out)), "nq_slab_transfer_binned")
+        if self.link in ("peers", "null"):
+            return out
+        self.sync()            # the library's streams are drained before torch's communicator runs
+        parts = [None] * self.nranks
+        self.dist.all_gather_object(parts, out)
+        tot = np.zeros_like(out)
+        for p in parts:        # rank order
+            tot += p
+        return tot
+
     def max_over_ranks(self, values):
         """element-wise max over all ranks of the simulation of a small vector this process computed for its ranks"""
         v = np.max(np.asarray(values, float).reshape(len(self.ranks), -1), axis=0)
@@ -548,6 +563,9 @@ class SlabContext(object):
 
     def diagnostic_sums_binned(self):
         return self.sim.diagnostics_binned()
+
+    def transfer_sums_binned(self):
+        return self.sim.transfer_binned()
 
     def diagnostic_sums(self):
         if self._ds is None:
