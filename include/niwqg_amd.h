@@ -228,6 +228,31 @@ int nq_diagnostics_binned(nq_ctx* ctx, int nb, double* out);
 #define NQ_TRANSFER_ROWS 6
 int nq_transfer_binned(nq_ctx* ctx, int nb, double* out);
 
+/* Lagrangian particles, single-rank contexts only (slab contexts refuse every call with -4).
+ * After every step of nq_step the library moves each particle one classical RK4 step through U_tot = (U + u, v), u = -d psi/dy,
+ * v = d psi/dx of the ph the context holds, linear in time between U0 (start of the step) and U1 (after it):
+ *   k1 = U0(x), k2 = (U0 + U1)/2 (x + dt/2 k1), k3 = (U0 + U1)/2 (x + dt/2 k2), k4 = U1(x + dt k3),
+ *   x += dt/6 (k1 + 2 k2 + 2 k3 + k4);      (U0 + U1)/2 (x) is the mean of the two interpolated values.
+ * U0 is formed again after nq_set_q, nq_set_phi, nq_set_c and nq_invert; YBJModel's psi is steady (U1 = U0).  Grid value [j, i]
+ * sits at ((i + 1/2) Lx / nx, (j + 1/2) Ly / nx); values at a particle come from the periodic tensor-product cubic convolution
+ * (Keys, a = -1/2) on the 4 x 4 nearest nodes; coordinates are reduced into [0, L) and node indices modulo nx, so no input
+ * addresses outside a plane; a non-finite position gives NaN and stays NaN.  Positions are kept unwrapped.  No reductions, no
+ * atomics: repeated runs are bit-identical; the particles write only buffers of their own, so every model output is the same as
+ * without them.  Names of values (PT_*): 0 u, 1 v, 2 q, 3 phi (Kernel family only; two columns: real, imaginary part).
+ *
+ * attach: n >= 1 finite coordinates (host arrays); record_every r > 0 writes a record at attach (step 0) and after every r-th step
+ * since, into a ring of `capacity` records of (2 + columns) x n doubles: x, y, then the named values of the state after that
+ * step.  One set per context (-4 while one is attached).  Every allocation is counted by nq_device_bytes and freed by detach.
+ * records: info[0] records written, [1] records held m = min(count, capacity), [2] doubles per particle and record, [3] steps
+ * since attach; with steps / out non-null, the held records oldest first: steps[m] (steps since attach), out[m][2 + cols][n].
+ * sample: out[cols][n], the named values at the current positions from the current state.                                    */
+int nq_particles_attach(nq_ctx* ctx, int n, const double* x, const double* y, double Lx, double Ly, int record_every, int capacity,
+                        int nnames, const int* names);
+int nq_particles_detach(nq_ctx* ctx);
+int nq_particles_get(nq_ctx* ctx, double* x, double* y);
+int nq_particles_sample(nq_ctx* ctx, int nnames, const int* names, double* out);
+int nq_particles_records(nq_ctx* ctx, long long* info4, long long* steps, double* out);
+
 /* copy of one ETDRK4 coefficient plane (0:E 1:Eh 2:Q 3:f0 4:fab 5:fc) of equation eq (0: q, (nx, nx/2+1) complex;
  * 1: phi, (nx, nx) complex; 2: QGModel's passive scalar, (nx, nx/2+1)), without the filter folded in; values as the
  * reference's expch, expch_h, Qh, f0, fab, fc (Kernel.py:417-454, QGModel.py:426-461).                           */
@@ -436,6 +461,12 @@ int nq_any_set_elem(nq_any* eng, void* plane, long long index, double re, double
  * plane (rows, rows/2 + 1); out: nb = round(rows / sqrt 2) + 1 doubles; the integer shell rule and the deterministic kernel of
  * nq_diagnostics_binned (no weights: the caller forms each element's term, half planes with their weight folded in).    */
 int nq_any_bin(nq_any* eng, const void* plane, int rows, int cols, int layout, int nb, double* out);
+/* Lagrangian particles on engine planes (the RK4 step and interpolation of nq_particles_attach above): pos holds n complex
+ * x + i y; U0, U1 and plane are (nx, nx) complex planes, velocity planes as u + i v; out[i] = plane at pos[i] (real and
+ * imaginary parts interpolated each) */
+int nq_any_particles_rk4(nq_any* eng, void* pos, int n, const void* U0, const void* U1, int nx, double Lx, double Ly, double U,
+                         double dt);
+int nq_any_interp(nq_any* eng, void* out, const void* plane, const void* pos, int n, int nx, double Lx, double Ly);
 /* E = exp(c dt), Eh = exp(c dt / 2), Q, f0, fab, fc of the linear operator c(l, k) on a (n, cols) plane, WITHOUT the filter
  * (Kernel.py:417-454, QGModel.py:426-466); eq 0: q of the Kernel family, 1: phi, 2: QGModel's q (beta term), 3: its passive
  * scalar.  The entries within delta of the contour are listed (near_*; at most cap) for the host to recompute exactly as the

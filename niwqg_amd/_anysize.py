@@ -770,6 +770,14 @@ class KernelFamily(object):
         d["phi"] = self._ifft(d["phih"])
 
     def _step_etdrk4(self):
+        P = self.__dict__.get("_particles")          # Lagrangian particles (niwqg_amd/particles.py): U0 before, RK4 after
+        if P is not None:
+            P._before_step()
+        self._step_etdrk4_state()
+        if P is not None:
+            P._after_step()
+
+    def _step_etdrk4_state(self):
         """ref: niwqg/Kernel.py:307-397"""
         if self.model_id == _lib.YBJ:
             self._step_ybj()
@@ -1113,6 +1121,14 @@ class QGFamily(object):
                 - 2 * self.muc * self.gradC2)
 
     def _step_etdrk4(self):
+        P = self.__dict__.get("_particles")          # Lagrangian particles (niwqg_amd/particles.py): U0 before, RK4 after
+        if P is not None:
+            P._before_step()
+        self._step_etdrk4_state()
+        if P is not None:
+            P._after_step()
+
+    def _step_etdrk4_state(self):
         """ref: niwqg/QGModel.py:328-407"""
         d, c, F = self._d, self._coef_q, self._K["F"]
         ps, cc = self.passive_scalar, self._coef_c

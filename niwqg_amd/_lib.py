@@ -20,7 +20,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # NIWQG_AMD_LIB: another build of the same sources (A/B experiments with compile-time knobs, tools/); default: the in-tree library
 LIB_PATH = os.environ.get("NIWQG_AMD_LIB") or os.path.join(HERE, "libniwqg_amd.so")
 SRC = os.path.join(HERE, "csrc", "nq_lib.hip")
-HEADERS = [os.path.join(HERE, "csrc", h) for h in ("nq_fft.hpp", "nq_generic.hpp", "nq_step.hpp", "nq_anysize.hpp")] + [
+HEADERS = [os.path.join(HERE, "csrc", h) for h in ("nq_fft.hpp", "nq_generic.hpp", "nq_step.hpp", "nq_anysize.hpp", "nq_particles.hpp")] + [
     os.path.join(os.path.dirname(HERE), "include", "niwqg_amd.h")]
 
 COUPLED, UNCOUPLED, QG, YBJ = 0, 1, 2, 3
@@ -31,6 +31,7 @@ COUPLED, UNCOUPLED, QG, YBJ = 0, 1, 2, 3
 EXPORTS = ["nq_create", "nq_destroy", "nq_last_error", "nq_set_q", "nq_set_c", "nq_set_phi", "nq_invert", "nq_refresh_grad_phi",
            "nq_step", "nq_profile_stride", "nq_request_stage4_max", "nq_get_stage4_max", "nq_tick_snapshot", "nq_sync", "nq_get_field", "nq_get_qh_passenger", "nq_get_scalar", "nq_fft2", "nq_ifft2", "nq_rfft2",
            "nq_irfft2", "nq_jacobian_psi_q", "nq_jacobian_psi_c", "nq_jacobian_psi_phi", "nq_jacobian_phic_phi", "nq_products_uq_vq", "nq_refraction", "nq_field_doubles", "nq_get_coeff", "nq_coeff_near_contour", "nq_coeff_patch", "nq_diagnostics", "nq_spectrum_shells", "nq_diagnostics_binned", "nq_transfer_binned",
+           "nq_particles_attach", "nq_particles_detach", "nq_particles_get", "nq_particles_sample", "nq_particles_records",
            "nq_stream_copy_gbs", "nq_timer_start", "nq_timer_stop", "nq_event_record", "nq_event_elapsed", "nq_profile_enable", "nq_profile_read", "nq_profile_read_all", "nq_group_elems", "nq_create_slab",
            "nq_slab_info", "nq_group_buffers", "nq_upload_spectral", "nq_download_spectral", "nq_phase",
            "nq_reduce_buffer", "nq_reduce_read", "nq_reduce_write", "nq_device_bytes", "nq_stream",
@@ -39,7 +40,7 @@ EXPORTS = ["nq_create", "nq_destroy", "nq_last_error", "nq_set_q", "nq_set_c", "
            "nq_slab_local_max", "nq_slab_counters", "nq_slab_allreduce_ms", "nq_snapshot_begin", "nq_snapshot_end",
            "nq_any_create", "nq_any_destroy", "nq_any_last_error", "nq_any_sync", "nq_any_device_bytes", "nq_any_alloc", "nq_any_free",
            "nq_any_upload", "nq_any_download", "nq_any_fft", "nq_any_ew", "nq_any_reduce", "nq_any_expand_half", "nq_any_take_cols",
-           "nq_any_set_elem", "nq_any_bin", "nq_any_etdrk4", "nq_any_etdrk4_patch"]
+           "nq_any_set_elem", "nq_any_bin", "nq_any_etdrk4", "nq_any_etdrk4_patch", "nq_any_particles_rk4", "nq_any_interp"]
 
 TRANSFER_ROWS = 6                 # rows of nq_transfer_binned (include/niwqg_amd.h: NQ_TRANSFER_ROWS)
 
@@ -120,6 +121,13 @@ def lib():
     L.nq_spectrum_shells.argtypes = [vp]
     L.nq_diagnostics_binned.argtypes = [vp, ctypes.c_int, dp]
     L.nq_transfer_binned.argtypes = [vp, ctypes.c_int, dp]
+    ip, llp = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_longlong)
+    L.nq_particles_attach.argtypes = [vp, ctypes.c_int, dp, dp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, ip]
+    L.nq_particles_detach.argtypes = [vp]
+    L.nq_particles_get.argtypes = [vp, dp, dp]
+    L.nq_particles_sample.argtypes = [vp, ctypes.c_int, ip, dp]
+    L.nq_particles_records.argtypes = [vp, llp, llp, dp]
     L.nq_get_coeff.argtypes = [vp, ctypes.c_int, ctypes.c_int, dp]
     L.nq_coeff_near_contour.argtypes = [vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     L.nq_coeff_patch.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, dp]
@@ -185,6 +193,9 @@ def lib():
     L.nq_any_take_cols.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.nq_any_set_elem.argtypes = [vp, vp, ctypes.c_longlong, ctypes.c_double, ctypes.c_double]
     L.nq_any_bin.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp]
+    L.nq_any_particles_rk4.argtypes = [vp, vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                       ctypes.c_double]
+    L.nq_any_interp.argtypes = [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double]
     L.nq_any_etdrk4.argtypes = [vp, ctypes.c_int, ctypes.POINTER(Params), dp, dp, dp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp),
                                 ctypes.c_double, ctypes.c_int, ip, ip, ip]
     L.nq_any_etdrk4_patch.argtypes = [vp, ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ip, ip, dp]
@@ -496,3 +507,35 @@ class Context:
 
     def device_bytes(self):
         return int(self.L.nq_device_bytes(self.h))
+
+    # ---- Lagrangian particles (include/niwqg_amd.h: nq_particles_*; niwqg_amd/particles.py) ----------------------------------
+    def particles_attach(self, x, y, Lx, Ly, record_every, capacity, codes):
+        x = np.ascontiguousarray(x, np.float64)
+        y = np.ascontiguousarray(y, np.float64)
+        c = (ctypes.c_int * max(1, len(codes)))(*codes)
+        self._chk(self.L.nq_particles_attach(self.h, len(x), _dptr(x), _dptr(y), float(Lx), float(Ly), int(record_every),
+                                             int(capacity), len(codes), c), "nq_particles_attach")
+
+    def particles_detach(self):
+        self._chk(self.L.nq_particles_detach(self.h), "nq_particles_detach")
+
+    def particles_get(self, n):
+        x, y = np.empty(n), np.empty(n)
+        self._chk(self.L.nq_particles_get(self.h, _dptr(x), _dptr(y)), "nq_particles_get")
+        return x, y
+
+    def particles_sample(self, n, codes, ncols):
+        out = np.empty((ncols, n))
+        c = (ctypes.c_int * max(1, len(codes)))(*codes)
+        self._chk(self.L.nq_particles_sample(self.h, len(codes), c, _dptr(out)), "nq_particles_sample")
+        return out
+
+    def particles_records(self, n):
+        """(steps since attach (m,), records (m, columns, n)) of the records the ring holds, oldest first"""
+        info = (ctypes.c_longlong * 4)()
+        self._chk(self.L.nq_particles_records(self.h, info, None, None), "nq_particles_records")
+        m, w = int(info[1]), int(info[2])
+        steps = (ctypes.c_longlong * max(1, m))()
+        out = np.empty((m, w, n))
+        self._chk(self.L.nq_particles_records(self.h, info, steps, _dptr(out)), "nq_particles_records")
+        return np.array(steps[:m], np.int64), out

@@ -11,6 +11,7 @@
 #include "../../include/niwqg_amd.h"
 #include "nq_step.hpp"
 #include "nq_anysize.hpp"
+#include "nq_particles.hpp"
 
 using namespace nq;
 
@@ -174,7 +175,10 @@ struct nq_ctx {
   bool passive = false;  // QGModel with its passive scalar: state cq, spectrum emitted through the qw slots of G3 / G0
   EqState cq;
   MArr mUc, mVc;      // niwqg.YBJModel: UnCoupled layouts, only phi is stepped (stage graph in do_step_ybj)
+  struct NqParticles* pt = nullptr;   // Lagrangian particles (nq_particles_attach): null when none
+  double pt_L[2] = {0.0, 0.0};       // their domain, Lx and Ly
 };
+static void pt_release(nq_ctx* c);
 
 // Device arrays start at staggered offsets inside their allocations.  hipMalloc hands out large blocks at addresses that
 // differ by multiples of 2 MiB (the 256 MiB planes: by exact multiples of their size), so element idx of every state,
@@ -2530,6 +2534,7 @@ int nq_destroy(nq_ctx* c) {
   if (!c) return 0;
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);
+  pt_release(c);
   for (void* p : c->allocs) hipFree(p);
   for (auto& pt : c->patch) { (void)hipFree(pt.l); (void)hipFree(pt.k); (void)hipFree(pt.v); }
   for (hipEvent_t e : c->prof_ev) hipEventDestroy(e);
@@ -2702,9 +2707,13 @@ int nq_event_elapsed(nq_ctx* c, int slot_a, int slot_b, float* ms) {
   return 0;
 }
 
+// particles: U0 is formed again from the state the next step starts from
+static void pt_mark_stale(nq_ctx* c);
+
 int nq_set_q(nq_ctx* c, const double* q_host) {
   if (!c || !q_host) return -1;
   NQ_SINGLE_RANK(c, "nq_set_q");
+  pt_mark_stale(c);
   const size_t full = (size_t)c->N * c->N;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipMemcpyAsync(c->scr_r, q_host, sizeof(double) * full, hipMemcpyHostToDevice, c->stream));
@@ -2719,6 +2728,7 @@ int nq_set_q(nq_ctx* c, const double* q_host) {
 int nq_set_c(nq_ctx* c, const double* c_host) {
   if (!c || !c_host) return -1;
   NQ_SINGLE_RANK(c, "nq_set_c");
+  pt_mark_stale(c);
   if (!c->passive) NQ_FAIL(c, -4, "nq_set_c: this context has no passive scalar");
   const size_t full = (size_t)c->N * c->N;
   HIPCHK(c, hipSetDevice(c->device));
@@ -2731,6 +2741,7 @@ int nq_set_c(nq_ctx* c, const double* c_host) {
 int nq_set_phi(nq_ctx* c, const double* phi_host) {
   if (!c || !phi_host) return -1;
   NQ_SINGLE_RANK(c, "nq_set_phi");
+  pt_mark_stale(c);
   if (!c->kernel_family) NQ_FAIL(c, -4, "nq_set_phi: QGModel has no wave field");
   const size_t full = (size_t)c->N * c->N;
   HIPCHK(c, hipSetDevice(c->device));
@@ -2748,6 +2759,7 @@ int nq_set_phi(nq_ctx* c, const double* phi_host) {
 int nq_invert(nq_ctx* c) {
   if (!c) return -1;
   NQ_SINGLE_RANK(c, "nq_invert");
+  pt_mark_stale(c);
   HIPCHK(c, hipSetDevice(c->device));
   do_invert_now(c);
   return nq_sync(c);
@@ -2764,6 +2776,8 @@ int nq_refresh_grad_phi(nq_ctx* c) {
   return 0;
 }
 
+static void pt_before_step(nq_ctx* c);
+static int pt_after_step(nq_ctx* c);
 int nq_step(nq_ctx* c, int nsteps) {
   if (!c) return -1;
   NQ_SINGLE_RANK(c, "nq_step");
@@ -2771,7 +2785,12 @@ int nq_step(nq_ctx* c, int nsteps) {
   HIPCHK(c, hipSetDevice(c->device));
   for (int i = 0; i < nsteps; ++i) {
     c->uv4_now = c->want_uv4 && i == nsteps - 1 && c->kernel_family && !c->ybj;
+    if (c->pt) pt_before_step(c);
     do_step(c);
+    if (c->pt) {
+      const int rc = pt_after_step(c);
+      if (rc) return rc;
+    }
   }
   if (nsteps > 0) {
     c->stepped = true;
@@ -2793,6 +2812,259 @@ int nq_get_stage4_max(nq_ctx* c, double* out2) {
   if (!c->have_uv4 || !c->uv4) NQ_FAIL(c, -4, "nq_get_stage4_max: the last step call was not asked to record the fourth stage's maxima");
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipMemcpyAsync(out2, c->uv4, sizeof(double) * 2, hipMemcpyDeviceToHost, c->stream));
+  return nq_sync(c);
+}
+
+// ---- Lagrangian particles ------------------------------------------------------------------------
+// Between calls, Mu and Mp on the x side hold the column-transformed -il psi and psi of the ph the context holds: every step
+// ends with the inversion of its final state (store_aux), set_q / set_c / nq_invert run do_invert_now, the QGModel scalar tick
+// re-runs do_invert_now after its stale inversion, YBJModel's step writes neither, and a dual-q context inverts the mean of its
+// two copies exactly where ph takes it.  So a velocity plane is ONE row kernel (k_x_get_uv) away at any point between steps.
+enum { PT_U = 0, PT_V = 1, PT_Q = 2, PT_PHI = 3 };
+struct NqParticles {
+  int n = 0;
+  double *x = nullptr, *y = nullptr;       // unwrapped positions
+  cd* uv[2] = {nullptr, nullptr};          // velocity planes (u, v) interleaved, ping-pong: uv[cur] is the current state's
+  int cur = 0;
+  bool u0 = false;                         // uv[cur] is the velocity of the state the next step starts from
+  int every = 0, cap = 0, ncol = 0;        // record every `every` steps into a ring of `cap` records of (2 + ncol) x n doubles
+  std::vector<int> names;                  // record columns (PT_*; PT_PHI takes two: real, imaginary part)
+  double* ring = nullptr;
+  std::vector<long long> ring_step;        // steps since attach of each slot
+  long long count = 0, steps = 0;
+  double* qplane = nullptr;                // physical q (PT_Q), allocated when first needed
+  cd* phiplane = nullptr;                  // physical phi (PT_PHI), idem
+  double* samp = nullptr;                  // nq_particles_sample's output columns (4 x n), idem
+  std::vector<void*> mem;
+  long long bytes = 0;
+};
+
+static int pt_alloc_raw(nq_ctx* c, void** out, size_t bytes) {
+  NqParticles* P = c->pt;
+  void* p = nullptr;
+  HIPCHK(c, hipMalloc(&p, bytes));
+  P->mem.push_back(p);
+  P->bytes += (long long)bytes;
+  c->bytes += (long long)bytes;
+  HIPCHK(c, hipMemsetAsync(p, 0, bytes, c->stream));
+  *out = p;
+  return 0;
+}
+#define pt_alloc(c, pptr, count) pt_alloc_raw((c), reinterpret_cast<void**>(pptr), (size_t)(count) * sizeof(**(pptr)))
+static void pt_release(nq_ctx* c) {
+  NqParticles* P = c->pt;
+  if (!P) return;
+  (void)hipSetDevice(c->device);
+  (void)hipStreamSynchronize(c->stream);
+  for (void* p : P->mem) (void)hipFree(p);
+  c->bytes -= P->bytes;
+  delete P;
+  c->pt = nullptr;
+}
+static PtGrid pt_grid(const nq_ctx* c) {
+  PtGrid g;
+  g.n = c->N;
+  g.Lx = c->pt_L[0];
+  g.Ly = c->pt_L[1];
+  g.dx = g.Lx / c->N;
+  g.dy = g.Ly / c->N;
+  return g;
+}
+static int pt_blocks(int n) { return (n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096; }
+
+// the velocity plane of the current ph from Mu, Mp (one row kernel)
+static void pt_form_uv(nq_ctx* c, cd* out) {
+  switch (c->N) {
+#define CASE_(nn, a, b) case nn: { typedef XPlan<nn> X; constexpr bool one = nn >= 8192; \
+    for (int comp = 0; comp < (one ? 2 : 1); ++comp) \
+      hipLaunchKernelGGL((k_x_get_uv<nn, false, one>), dim3((c->N + X::C - 1) / X::C), dim3(X::THREADS), X::LDS_BYTES, c->stream, c->mU, c->mP, out, c->N, c->tw, c->kk, c->kernel_family ? 1 : 0, comp); } break;
+    NQ_FOR_SIZES(CASE_)
+#undef CASE_
+  }
+}
+static void pt_mark_stale(nq_ctx* c) {
+  if (c && c->pt) c->pt->u0 = false;
+}
+static void pt_before_step(nq_ctx* c) {
+  NqParticles* P = c->pt;
+  if (!P->u0) {
+    pt_form_uv(c, P->uv[P->cur]);
+    P->u0 = true;
+  }
+}
+// sample column `name` into o0 (and o1: phi's imaginary part) from the current state; planes allocated on first use
+static int pt_sample_into(nq_ctx* c, int name, double* o0, double* o1) {
+  NqParticles* P = c->pt;
+  const PtGrid g = pt_grid(c);
+  const int nb = pt_blocks(P->n);
+  if (name == PT_U || name == PT_V) {
+    pt_before_step(c);
+    hipLaunchKernelGGL(k_pt_sample<cd>, dim3(nb), dim3(256), 0, c->stream, (const cd*)P->uv[P->cur], (const double*)P->x, (const double*)P->y, P->n, g, name == PT_U ? o0 : nullptr, name == PT_V ? o0 : nullptr);
+  } else if (name == PT_Q) {
+    if (!P->qplane) { int rc = pt_alloc(c, &P->qplane, (size_t)c->N * c->N); if (rc) return rc; }
+    switch (c->N) {      // Mq holds the q the last inversion saw (the mean of the two copies on dual-q contexts): m.q
+#define CASE_(nn, a, b) case nn: { typedef XPlan<nn> X; \
+      hipLaunchKernelGGL((k_x_get_real<nn, false>), dim3((c->N + X::C - 1) / X::C), dim3(X::THREADS), X::LDS_BYTES, c->stream, c->mQ, P->qplane, c->N, c->tw, c->kk, 0, 0); } break;
+      NQ_FOR_SIZES(CASE_)
+#undef CASE_
+    }
+    hipLaunchKernelGGL(k_pt_sample<double>, dim3(nb), dim3(256), 0, c->stream, (const double*)P->qplane, (const double*)P->x, (const double*)P->y, P->n, g, o0, nullptr);
+  } else if (name == PT_PHI) {
+    if (!c->kernel_family) NQ_FAIL(c, -4, "particles: QGModel has no wave field (phi)");
+    if (!P->phiplane) { int rc = pt_alloc(c, &P->phiplane, (size_t)c->N * c->N); if (rc) return rc; }
+    launch_x_c2c(c, true, c->mPhi.xs, P->phiplane, c->mPhi.pitch, c->N, 1.0);         // as nq_get_field(NQ_F_PHI)
+    hipLaunchKernelGGL(k_pt_sample<cd>, dim3(nb), dim3(256), 0, c->stream, (const cd*)P->phiplane, (const double*)P->x, (const double*)P->y, P->n, g, o0, o1);
+  } else {
+    NQ_FAIL(c, -1, "particles: unknown sample name %d", name);
+  }
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+static int pt_record(nq_ctx* c) {
+  NqParticles* P = c->pt;
+  const int slot = (int)(P->count % P->cap);
+  const size_t n = (size_t)P->n;
+  double* r = P->ring + (size_t)slot * (2 + P->ncol) * n;
+  HIPCHK(c, hipMemcpyAsync(r, P->x, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(r + n, P->y, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
+  int col = 2;
+  for (int name : P->names) {
+    const int rc = pt_sample_into(c, name, r + col * n, name == PT_PHI ? r + (col + 1) * n : nullptr);
+    if (rc) return rc;
+    col += name == PT_PHI ? 2 : 1;
+  }
+  P->ring_step[slot] = P->steps;
+  ++P->count;
+  return 0;
+}
+static int pt_after_step(nq_ctx* c) {
+  NqParticles* P = c->pt;
+  const PtGrid g = pt_grid(c);
+  const cd* U0 = P->uv[P->cur];
+  const cd* U1 = U0;                       // YBJModel: psi is steady, U1 = U0 (formed again only after set_q)
+  if (!c->ybj) {
+    pt_form_uv(c, P->uv[P->cur ^ 1]);
+    U1 = P->uv[P->cur ^ 1];
+  }
+  hipLaunchKernelGGL(k_pt_rk4, dim3(pt_blocks(P->n)), dim3(256), 0, c->stream, P->x, P->y, P->n, U0, U1, g, c->p.U, c->p.dt);
+  HIPCHK(c, hipGetLastError());
+  if (!c->ybj) P->cur ^= 1;
+  ++P->steps;
+  if (P->every > 0 && P->steps % P->every == 0) return pt_record(c);
+  return 0;
+}
+
+int nq_particles_attach(nq_ctx* c, int n, const double* x, const double* y, double Lx, double Ly, int record_every, int capacity,
+                        int nnames, const int* names) {
+  NQ_SINGLE_RANK(c, "nq_particles_attach");
+  if (c->pt) NQ_FAIL(c, -4, "nq_particles_attach: particles are attached already (nq_particles_detach first)");
+  if (n < 1 || !x || !y) NQ_FAIL(c, -1, "nq_particles_attach: n = %d (>= 1) and both coordinate arrays", n);
+  if (!(Lx > 0.0) || !(Ly > 0.0) || !std::isfinite(Lx) || !std::isfinite(Ly)) NQ_FAIL(c, -1, "nq_particles_attach: domain %g x %g", Lx, Ly);
+  if (record_every < 0 || (record_every > 0 && capacity < 1)) NQ_FAIL(c, -1, "nq_particles_attach: record_every = %d, capacity = %d", record_every, capacity);
+  if (nnames < 0 || nnames > 4 || (nnames > 0 && !names)) NQ_FAIL(c, -1, "nq_particles_attach: %d record names", nnames);
+  int ncol = 0;
+  for (int i = 0; i < nnames; ++i) {
+    if (names[i] < PT_U || names[i] > PT_PHI) NQ_FAIL(c, -1, "nq_particles_attach: record name %d", names[i]);
+    if (names[i] == PT_PHI && !c->kernel_family) NQ_FAIL(c, -1, "nq_particles_attach: QGModel has no wave field (phi)");
+    ncol += names[i] == PT_PHI ? 2 : 1;
+  }
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(x[i]) || !std::isfinite(y[i])) NQ_FAIL(c, -1, "nq_particles_attach: particle %d has a non-finite coordinate", i);
+  HIPCHK(c, hipSetDevice(c->device));
+  c->pt_L[0] = Lx;
+  c->pt_L[1] = Ly;
+  c->pt = new NqParticles();
+  NqParticles* P = c->pt;
+  P->n = n;
+  P->every = record_every;
+  P->cap = record_every > 0 ? capacity : 0;
+  P->ncol = ncol;
+  P->names.assign(names, names + nnames);
+  const size_t plane = (size_t)c->N * c->N;
+  int rc = pt_alloc(c, &P->x, (size_t)n);
+  if (!rc) rc = pt_alloc(c, &P->y, (size_t)n);
+  if (!rc) rc = pt_alloc(c, &P->uv[0], plane);
+  if (!rc && !c->ybj) rc = pt_alloc(c, &P->uv[1], plane);
+  if (!rc && c->ybj) P->uv[1] = P->uv[0];
+  if (!rc && P->cap > 0) {
+    rc = pt_alloc(c, &P->ring, (size_t)P->cap * (2 + ncol) * n);
+    P->ring_step.assign((size_t)P->cap, 0);
+  }
+  if (rc) {
+    const std::string e = c->err;
+    pt_release(c);
+    NQ_FAIL(c, rc, "%s", e.c_str());
+  }
+  // (hipMemcpy from pageable memory returns once the source is consumed)
+  HIPCHK(c, hipMemcpyAsync(P->x, x, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(P->y, y, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+  if (P->every > 0) {
+    rc = pt_record(c);
+    if (rc) {
+      const std::string e = c->err;
+      pt_release(c);
+      NQ_FAIL(c, rc, "%s", e.c_str());
+    }
+  }
+  return nq_sync(c);
+}
+int nq_particles_detach(nq_ctx* c) {
+  NQ_SINGLE_RANK(c, "nq_particles_detach");
+  if (!c->pt) NQ_FAIL(c, -4, "nq_particles_detach: no particles attached");
+  pt_release(c);
+  return 0;
+}
+int nq_particles_get(nq_ctx* c, double* x, double* y) {
+  NQ_SINGLE_RANK(c, "nq_particles_get");
+  if (!c->pt) NQ_FAIL(c, -4, "nq_particles_get: no particles attached");
+  if (!x || !y) return -1;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(x, c->pt->x, sizeof(double) * c->pt->n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(y, c->pt->y, sizeof(double) * c->pt->n, hipMemcpyDeviceToHost, c->stream));
+  return nq_sync(c);
+}
+int nq_particles_sample(nq_ctx* c, int nnames, const int* names, double* out) {
+  NQ_SINGLE_RANK(c, "nq_particles_sample");
+  NqParticles* P = c->pt;
+  if (!P) NQ_FAIL(c, -4, "nq_particles_sample: no particles attached");
+  if (nnames < 0 || (nnames > 0 && (!names || !out))) return -1;
+  for (int i = 0; i < nnames; ++i) {
+    if (names[i] < PT_U || names[i] > PT_PHI) NQ_FAIL(c, -1, "nq_particles_sample: name %d", names[i]);
+    if (names[i] == PT_PHI && !c->kernel_family) NQ_FAIL(c, -1, "nq_particles_sample: QGModel has no wave field (phi)");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n = (size_t)P->n;
+  if (!P->samp) { int rc = pt_alloc(c, &P->samp, 2 * n); if (rc) return rc; }
+  size_t col = 0;
+  for (int i = 0; i < nnames; ++i) {
+    const int w = names[i] == PT_PHI ? 2 : 1;
+    int rc = pt_sample_into(c, names[i], P->samp, w == 2 ? P->samp + n : nullptr);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(out + col * n, P->samp, sizeof(double) * w * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // (samp is reused by the next name)
+    col += w;
+  }
+  return nq_sync(c);
+}
+int nq_particles_records(nq_ctx* c, long long* info, long long* steps, double* out) {
+  NQ_SINGLE_RANK(c, "nq_particles_records");
+  NqParticles* P = c->pt;
+  if (!P) NQ_FAIL(c, -4, "nq_particles_records: no particles attached");
+  if (!info) return -1;
+  const long long m = P->count < P->cap ? P->count : P->cap;
+  info[0] = P->count;
+  info[1] = m;
+  info[2] = 2 + P->ncol;
+  info[3] = P->steps;
+  if (!steps && !out) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t rec = (size_t)(2 + P->ncol) * P->n;
+  for (long long r = 0; r < m; ++r) {
+    const long long idx = P->count - m + r;
+    const int slot = (int)(idx % P->cap);
+    if (steps) steps[r] = P->ring_step[slot];
+    if (out) HIPCHK(c, hipMemcpyAsync(out + (size_t)r * rec, P->ring + (size_t)slot * rec, sizeof(double) * rec, hipMemcpyDeviceToHost, c->stream));
+  }
   return nq_sync(c);
 }
 
@@ -4746,6 +5018,29 @@ int nq_any_set_elem(nq_any* e, void* plane, long long index, double re, double i
   if (!e || !plane || index < 0) return -1;
   ANYCHK(e, hipSetDevice(e->device));
   hipLaunchKernelGGL(k_any_set_elem, dim3(1), dim3(1), 0, e->stream, reinterpret_cast<cd*>(plane), (size_t)index, re, im);
+  ANYCHK(e, hipGetLastError());
+  return 0;
+}
+// Lagrangian particles on the any-size path: the fused contexts' RK4 step and interpolation on engine
+// planes; pos: n complex x + i y (unwrapped), U0 / U1 / plane: (nx, nx) complex planes (velocity planes: u + i v)
+int nq_any_particles_rk4(nq_any* e, void* pos, int n, const void* U0, const void* U1, int nx, double Lx, double Ly, double Ub,
+                         double dt) {
+  if (!e || !pos || !U0 || !U1 || n < 1 || nx < 1) return -1;
+  if (!(Lx > 0.0) || !(Ly > 0.0)) ANYFAIL(e, -1, "nq_any_particles_rk4: domain %g x %g", Lx, Ly);
+  ANYCHK(e, hipSetDevice(e->device));
+  const PtGrid g{nx, Lx, Ly, Lx / nx, Ly / nx};
+  hipLaunchKernelGGL(k_pt_rk4_c, dim3(pt_blocks(n)), dim3(256), 0, e->stream, reinterpret_cast<cd*>(pos), n, reinterpret_cast<const cd*>(U0),
+                     reinterpret_cast<const cd*>(U1), g, Ub, dt);
+  ANYCHK(e, hipGetLastError());
+  return 0;
+}
+int nq_any_interp(nq_any* e, void* out, const void* plane, const void* pos, int n, int nx, double Lx, double Ly) {
+  if (!e || !out || !plane || !pos || n < 1 || nx < 1) return -1;
+  if (!(Lx > 0.0) || !(Ly > 0.0)) ANYFAIL(e, -1, "nq_any_interp: domain %g x %g", Lx, Ly);
+  ANYCHK(e, hipSetDevice(e->device));
+  const PtGrid g{nx, Lx, Ly, Lx / nx, Ly / nx};
+  hipLaunchKernelGGL(k_pt_interp_c, dim3(pt_blocks(n)), dim3(256), 0, e->stream, reinterpret_cast<cd*>(out), reinterpret_cast<const cd*>(plane),
+                     reinterpret_cast<const cd*>(pos), n, g);
   ANYCHK(e, hipGetLastError());
   return 0;
 }

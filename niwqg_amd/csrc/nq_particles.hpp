@@ -1,0 +1,220 @@
+// Lagrangian particles advected inside the step: the velocity plane of a state, the periodic cubic
+// convolution that interpolates a physical plane at a particle, the RK4 step linear in time, and sampling.
+//
+// Grid value [j, i] of an (n, n) physical plane sits at ((i + 1/2) dx, (j + 1/2) dy) (the reference's _initialize_grid).
+// Interpolation is the tensor product of Keys' cubic convolution kernel (a = -1/2) on the 4 x 4 nearest nodes: exact at the
+// nodes, C^1, third order.  A coordinate is reduced into [0, L) with fmod first; every node index is reduced modulo n in integer
+// arithmetic after the cast, so no input -- NaN and +-inf included -- addresses outside the plane.  A non-finite coordinate
+// gives NaN without any load (its indices and weights are zeroed and pt_gather returns before reading the plane).
+#pragma once
+#include "nq_step.hpp"
+
+namespace nq {
+
+struct PtGrid {
+  int n;             // points per side of the physical plane
+  double Lx, Ly;     // domain lengths
+  double dx, dy;     // Lx / n, Ly / n
+};
+
+// Keys (1981), a = -1/2: weights of the nodes at offsets -1, 0, 1, 2 from the cell's left node, t in [0, 1)
+__device__ __forceinline__ void pt_keys(double t, double w[4]) {
+  w[0] = ((-0.5 * t + 1.0) * t - 0.5) * t;
+  w[1] = (1.5 * t - 2.5) * t * t + 1.0;
+  w[2] = ((-1.5 * t + 2.0) * t + 0.5) * t;
+  w[3] = (0.5 * t - 0.5) * t * t;
+}
+
+// node indices and weights along one axis; false for a non-finite coordinate (indices 0, weights 0)
+__device__ __forceinline__ bool pt_axis(double x, double L, double d, int n, int idx[4], double w[4]) {
+  if (!isfinite(x)) {
+#pragma unroll
+    for (int o = 0; o < 4; ++o) { idx[o] = 0; w[o] = 0.0; }
+    return false;
+  }
+  double r = fmod(x, L);
+  if (r < 0.0) r += L;
+  if (r >= L) r -= L;
+  const double s = r / d - 0.5;                      // in node units: node i at s = i
+  double f = floor(s);
+  if (!(f >= -1.0 && f <= (double)n)) f = 0.0;       // (cannot happen for r in [0, L); keeps the cast defined)
+  const int i0 = (int)f;
+  pt_keys(s - f, w);
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    int m = (i0 - 1 + o) % n;
+    if (m < 0) m += n;
+    idx[o] = m;
+  }
+  return true;
+}
+
+__device__ __forceinline__ void pt_madd(double& acc, double w, double v) { acc += w * v; }
+__device__ __forceinline__ void pt_madd(cd& acc, double w, cd v) { acc.x += w * v.x; acc.y += w * v.y; }
+__device__ __forceinline__ void pt_zero(double& a) { a = 0.0; }
+__device__ __forceinline__ void pt_zero(cd& a) { a = make_double2(0.0, 0.0); }
+__device__ __forceinline__ void pt_nan(double& a) { a = __builtin_nan(""); }
+__device__ __forceinline__ void pt_nan(cd& a) { a = make_double2(__builtin_nan(""), __builtin_nan("")); }
+
+struct PtStencil {
+  int ix[4], iy[4];
+  double wx[4], wy[4];
+  bool ok;
+};
+__device__ __forceinline__ PtStencil pt_stencil(const PtGrid& g, double x, double y) {
+  PtStencil s;
+  const bool okx = pt_axis(x, g.Lx, g.dx, g.n, s.ix, s.wx);
+  const bool oky = pt_axis(y, g.Ly, g.dy, g.n, s.iy, s.wy);
+  s.ok = okx && oky;
+  return s;
+}
+// sum_j wy[j] (sum_i wx[i] plane[iy[j], ix[i]]): the row sums first, in this order (the numpy restatement of the tests
+// follows it)
+template <typename T>
+__device__ __forceinline__ T pt_gather(const T* __restrict__ plane, const PtGrid& g, const PtStencil& s) {
+  T acc;
+  if (!s.ok) {
+    pt_nan(acc);
+    return acc;
+  }
+  pt_zero(acc);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const T* row = plane + (size_t)s.iy[j] * g.n;
+    T r;
+    pt_zero(r);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) pt_madd(r, s.wx[i], row[s.ix[i]]);
+    pt_madd(acc, s.wy[j], r);
+  }
+  return acc;
+}
+
+// One RK4 step of every particle from t to t + dt through the velocity (Ub + u, v), u + i v interpolated from U0 (start of the
+// step) and U1 (end), linear in time between them: k2, k3 take the mean of the two interpolated values.  U0 == U1: a steady
+// velocity (one gather per stage).  One particle per thread, in the caller's order: each stencil is 4 rows x 64 B of a
+// double2 plane; neighbouring particles of a wave share lines only as far as the caller ordered them.
+__device__ __forceinline__ cd pt_vel(const cd* __restrict__ U0, const cd* __restrict__ U1, const PtGrid& g, double x, double y,
+                                     int which, double Ub) {
+  // which 0: U0, 1: U1, 2: (U0 + U1) / 2
+  const PtStencil s = pt_stencil(g, x, y);
+  cd v;
+  if (which == 0) v = pt_gather(U0, g, s);
+  else if (which == 1) v = pt_gather(U1, g, s);
+  else if (U0 == U1) v = pt_gather(U0, g, s);
+  else {
+    const cd a = pt_gather(U0, g, s), b = pt_gather(U1, g, s);
+    v = make_double2(0.5 * (a.x + b.x), 0.5 * (a.y + b.y));
+  }
+  v.x += Ub;
+  return v;
+}
+__device__ __forceinline__ void pt_rk4(const cd* __restrict__ U0, const cd* __restrict__ U1, const PtGrid& g, double Ub, double dt,
+                                       double& x, double& y) {
+  const double x0 = x, y0 = y, h = 0.5 * dt;
+  const cd k1 = pt_vel(U0, U1, g, x0, y0, 0, Ub);
+  const cd k2 = pt_vel(U0, U1, g, x0 + h * k1.x, y0 + h * k1.y, 2, Ub);
+  const cd k3 = pt_vel(U0, U1, g, x0 + h * k2.x, y0 + h * k2.y, 2, Ub);
+  const cd k4 = pt_vel(U0, U1, g, x0 + dt * k3.x, y0 + dt * k3.y, 1, Ub);
+  x = x0 + dt / 6.0 * (k1.x + 2.0 * k2.x + 2.0 * k3.x + k4.x);
+  y = y0 + dt / 6.0 * (k1.y + 2.0 * k2.y + 2.0 * k3.y + k4.y);
+}
+
+// fused contexts: positions in two arrays (unwrapped)
+__global__ void __launch_bounds__(256) k_pt_rk4(double* __restrict__ px, double* __restrict__ py, int n, const cd* U0, const cd* U1,
+                                                PtGrid g, double Ub, double dt) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    double x = px[i], y = py[i];
+    pt_rk4(U0, U1, g, Ub, dt, x, y);
+    px[i] = x;
+    py[i] = y;
+  }
+}
+// any-size engine: positions as one complex array x + i y
+__global__ void __launch_bounds__(256) k_pt_rk4_c(cd* __restrict__ pos, int n, const cd* U0, const cd* U1, PtGrid g, double Ub,
+                                                  double dt) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    double x = pos[i].x, y = pos[i].y;
+    pt_rk4(U0, U1, g, Ub, dt, x, y);
+    pos[i] = make_double2(x, y);
+  }
+}
+
+// values of a physical plane at the particles: T = double (out0), T = cd (out0 = real part, out1 = imaginary part; either may be
+// null)
+template <typename T>
+__device__ __forceinline__ void pt_store(const T& v, double* o0, double* o1, int i);
+template <>
+__device__ __forceinline__ void pt_store<double>(const double& v, double* o0, double* o1, int i) { (void)o1; o0[i] = v; }
+template <>
+__device__ __forceinline__ void pt_store<cd>(const cd& v, double* o0, double* o1, int i) {
+  if (o0) o0[i] = v.x;
+  if (o1) o1[i] = v.y;
+}
+template <typename T>
+__global__ void __launch_bounds__(256) k_pt_sample(const T* __restrict__ plane, const double* __restrict__ px,
+                                                   const double* __restrict__ py, int n, PtGrid g, double* o0, double* o1) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    pt_store<T>(pt_gather(plane, g, pt_stencil(g, px[i], py[i])), o0, o1, i);
+}
+// any-size engine: out[i] = the complex plane interpolated at pos[i] = x + i y (real and imaginary parts each)
+__global__ void __launch_bounds__(256) k_pt_interp_c(cd* __restrict__ out, const cd* __restrict__ plane, const cd* __restrict__ pos,
+                                                     int n, PtGrid g) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    out[i] = pt_gather(plane, g, pt_stencil(g, pos[i].x, pos[i].y));
+}
+
+// the velocity plane (u, v) of the fields the last inversion emitted (Hu = column-transformed -il psi, Hp = psi on the x side):
+// k_x_get_real's two finishes (u: mode 0; v: mode 1, i kk, column N/2 dropped for the Kernel family) of one row, written
+// interleaved so that one gather fetches both components.  ONE = true (8192-point rows, where holding u across the second
+// transform spills): one launch per component `comp`, each writing its half of the double2 elements.
+template <int N, bool SLAB, bool ONE>
+__global__ void __launch_bounds__(XPlan<N>::THREADS)
+k_x_get_uv(MArr hu, MArr hp, cd* __restrict__ rows, int nrows, const cd* __restrict__ tw, const double* __restrict__ kk,
+           int zero_nyq, int comp) {
+  typedef XPlan<N> X;
+  constexpr int P = X::P, T = X::T;
+  const int j = threadIdx.x % T, c = threadIdx.x / T;
+  const int row = blockIdx.x * X::C + c;
+  cd* lds = reinterpret_cast<cd*>(nq_smem);
+  typename X::F::Tw twr;
+  X::F::load_tw(twr, j, tw, 1);
+  cd r[P];
+  double u[ONE ? 1 : P];
+  const bool ok = row < nrows;
+#pragma unroll
+  for (int pass = 0; pass < (ONE ? 1 : 2); ++pass) {
+    const int which = ONE ? comp : pass;
+    const XRowT<SLAB> src = xrow<SLAB>(which == 0 ? hu : hp, (size_t)(ok ? row : 0));
+#pragma unroll
+    for (int t = 0; t < P; ++t) {
+      const int kx = j + t * T;
+      cd v = cmake(0, 0);
+      if (ok) {
+        const int m = kx <= N / 2 ? kx : N - kx;
+        v = *src.at(m);
+        if (which == 1) v = cscale(cmul_i(v), kk[m]);
+        if (m == 0 || m == N / 2) v.y = 0.0;
+        if (which == 1 && zero_nyq && m == N / 2) v.x = 0.0;
+        if (kx > N / 2) v = cconj(v);
+      }
+      r[t] = v;
+    }
+    if (pass == 1) __syncthreads();           // the first transform's last LDS reads are done before the second writes
+    X::F::template run<true>(r, j, c, lds, twr);
+    if (!ONE && pass == 0) {
+#pragma unroll
+      for (int t = 0; t < P; ++t) u[t] = r[t].x;
+    }
+  }
+  if (ok) {
+#pragma unroll
+    for (int t = 0; t < P; ++t) {
+      const size_t at = (size_t)row * N + j + t * T;
+      if constexpr (ONE) reinterpret_cast<double*>(rows)[2 * at + comp] = r[t].x;
+      else rows[at] = make_double2(u[ONE ? 0 : t], r[t].x);
+    }
+  }
+}
+
+}  // namespace nq

@@ -1,0 +1,323 @@
+"""Lagrangian particles advected on the device inside the step.
+
+    from niwqg_amd import particles
+    P = particles.attach(m, x, y, record_every=0, capacity=1024, record=())
+    m.run()                                   # the particles move inside every step, batched or not
+    x, y = P.positions()                      # unwrapped coordinates
+    s = P.sample(("u", "v", "q", "phi"))      # {name: array(n)} at the current positions, from the current state
+    tr = P.trajectory()                       # .step (T,), .t (T,), .x / .y (T, n), .values {name: (T, n)}
+    P.detach()
+
+A particle moves through U_tot = (m.U + u, v), u = -d psi/dy, v = d psi/dx of the psi-hat the model holds (``m.ph``): in the
+coupled model the Lagrangian-mean flow; the wave signal is what ``"phi"`` records.  One step from t to t + dt is classical RK4,
+linear in time between the velocity U0 of the state the step starts from and U1 of the state after it:
+
+    k1 = U0(x), k2 = (U0 + U1)/2 (x + dt/2 k1), k3 = (U0 + U1)/2 (x + dt/2 k2), k4 = U1(x + dt k3)
+    x += dt/6 (k1 + 2 k2 + 2 k3 + k4)
+
+Values at a particle come from the periodic tensor-product cubic convolution (Keys, a = -1/2) on the 4 x 4 nearest nodes, grid
+value [j, i] sitting at ((i + 1/2) dx, (j + 1/2) dy).  ``interpolate`` below is the same rule in numpy.  The particles write
+only buffers of their own: every model output is bit-identical to a run without them.
+"""
+import numpy as np
+
+from . import _lib
+
+NAMES = ("u", "v", "q", "phi")
+_CODES = dict(u=0, v=1, q=2, phi=3)
+
+
+def _is_qg(m):
+    from .QGModel import Model as QG
+    return isinstance(m, QG)
+
+
+def available(m):
+    """names ``record`` and ``sample`` accept for this model ("phi": the Kernel family only)"""
+    return ["u", "v", "q"] if _is_qg(m) else list(NAMES)
+
+
+def _names(m, names, what):
+    names = [names] if isinstance(names, str) else list(names)
+    valid = available(m)
+    bad = [n for n in names if n not in valid]
+    if bad:
+        raise ValueError("particles.%s: %s not available for %s; valid names: %s"
+                         % (what, ", ".join(map(repr, bad)), type(m).__name__, ", ".join(valid)))
+    return names
+
+
+def _coords(x, y):
+    x = np.asarray(x)
+    y = np.asarray(y)
+    if x.ndim != 1 or y.ndim != 1:
+        raise ValueError("particles.attach: x and y must be 1-D (got %d-D and %d-D)" % (x.ndim, y.ndim))
+    if x.shape != y.shape:
+        raise ValueError("particles.attach: x and y differ in length (%d, %d)" % (x.size, y.size))
+    if x.size < 1:
+        raise ValueError("particles.attach: no particles (x and y are empty)")
+    try:
+        x = np.array(x, np.float64)
+        y = np.array(y, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("particles.attach: x and y must be real numbers")
+    if not (np.all(np.isfinite(x)) and np.all(np.isfinite(y))):
+        raise ValueError("particles.attach: non-finite coordinates")
+    return x, y
+
+
+# ---- the interpolation rule in numpy (the device kernels' restatement; tests use it) --------------------------------------
+def keys_weights(t):
+    """Keys' cubic convolution weights (a = -1/2) of the nodes at offsets -1, 0, 1, 2; t in [0, 1)"""
+    t = np.asarray(t, np.float64)
+    return (((-0.5 * t + 1.0) * t - 0.5) * t, (1.5 * t - 2.5) * t * t + 1.0, ((-1.5 * t + 2.0) * t + 0.5) * t, (0.5 * t - 0.5) * t * t)
+
+
+def _axis(x, L, n):
+    x = np.asarray(x, np.float64)
+    ok = np.isfinite(x)
+    xs = np.where(ok, x, 0.0)
+    r = np.fmod(xs, L)
+    r = np.where(r < 0, r + L, r)
+    r = np.where(r >= L, r - L, r)
+    s = r / (L / n) - 0.5
+    f = np.floor(s)
+    i0 = f.astype(np.int64)
+    w = keys_weights(s - f)
+    idx = [np.mod(i0 - 1 + o, n) for o in range(4)]
+    return ok, idx, w
+
+
+def interpolate(plane, x, y, L, W=None):
+    """plane (n, n) (real or complex) at the points (x, y): the library's rule; NaN for non-finite points"""
+    plane = np.asarray(plane)
+    n = plane.shape[0]
+    W = L if W is None else W
+    okx, ix, wx = _axis(x, L, n)
+    oky, iy, wy = _axis(y, W, n)
+    acc = np.zeros(np.shape(x), plane.dtype)
+    for j in range(4):
+        r = np.zeros(np.shape(x), plane.dtype)
+        for i in range(4):
+            r = r + wx[i] * plane[iy[j], ix[i]]
+        acc = acc + wy[j] * r
+    return np.where(okx & oky, acc, np.nan)
+
+
+# ---- the public object -------------------------------------------------------------------------------------------------
+class Trajectory(object):
+    """records oldest first: step (T,), t (T,), x, y (T, n), values {name: (T, n)}"""
+
+    def __init__(self, step, t, x, y, values):
+        self.step, self.t, self.x, self.y, self.values = step, t, x, y, values
+
+    def __repr__(self):
+        return "Trajectory(T=%d, n=%d, names=%s)" % (self.x.shape[0], self.x.shape[1], sorted(self.values))
+
+
+class Particles(object):
+    """A particle set attached to one model (``attach``); see the module's doc"""
+
+    def __init__(self, m, n, record_every, capacity, record):
+        self.m, self.n = m, n
+        self.record_every, self.capacity, self.record = record_every, capacity, tuple(record)
+        self.tc0, self.t0 = m.tc, m.t
+
+    def _check(self):
+        if self.m is None:
+            raise RuntimeError("particles: detached")
+
+    def positions(self):
+        """(x, y): the unwrapped coordinates (host copies)"""
+        self._check()
+        return self._positions()
+
+    def sample(self, names=None):
+        """{name: array(n)} at the current positions from the current state ("phi": complex); names: a subset of
+        available(m) (default: all of them)"""
+        self._check()
+        names = available(self.m) if names is None else _names(self.m, names, "sample")
+        return self._sample(names)
+
+    def _times(self, offsets):
+        t, out, k = self.t0, np.empty(len(offsets)), 0
+        for i, s in enumerate(offsets):          # the reference's float clock t += dt, from the time of attach
+            while k < s:
+                t += self.m.dt
+                k += 1
+            out[i] = t
+        return out
+
+    def trajectory(self):
+        """the last min(count, capacity) records, oldest first (record_every > 0)"""
+        self._check()
+        if self.record_every <= 0:
+            raise RuntimeError("particles.trajectory: attached with record_every = 0")
+        offsets, x, y, vals = self._records()
+        order = np.argsort(offsets, kind="stable")
+        assert np.all(order == np.arange(len(order)))
+        return Trajectory(offsets + self.tc0, self._times(offsets), x, y, vals)
+
+    def detach(self):
+        """frees every device buffer the set allocated"""
+        if self.m is None:
+            return
+        try:
+            self._detach()
+        finally:
+            self.m.__dict__.pop("_particles", None)
+            self.m = None
+
+    @staticmethod
+    def _split(names, cols):
+        out, c = {}, 0
+        for nm in names:
+            if nm == "phi":
+                out[nm] = cols[c] + 1j * cols[c + 1]
+                c += 2
+            else:
+                out[nm] = cols[c]
+                c += 1
+        return out
+
+
+class _Fused(Particles):
+    """fused contexts: positions, velocity planes and records live in the library (nq_particles_*)"""
+
+    def __init__(self, m, x, y, record_every, capacity, record):
+        Particles.__init__(self, m, len(x), record_every, capacity, record)
+        self.ctx = m._ctx
+        self.ctx.particles_attach(x, y, m.L, m.W, record_every, capacity, [_CODES[r] for r in record])
+
+    def _positions(self):
+        return self.ctx.particles_get(self.n)
+
+    def _sample(self, names):
+        ncols = sum(2 if nm == "phi" else 1 for nm in names)
+        return self._split(names, self.ctx.particles_sample(self.n, [_CODES[nm] for nm in names], ncols))
+
+    def _records(self):
+        steps, out = self.ctx.particles_records(self.n)
+        vals = self._split(self.record, [out[:, 2 + c, :] for c in range(out.shape[1] - 2)])
+        return steps, out[:, 0, :].copy(), out[:, 1, :].copy(), vals
+
+    def _detach(self):
+        self.ctx.particles_detach()
+
+
+class _AnySize(Particles):
+    """any-size path: positions (x + i y), velocity planes (u + i v) and records are engine planes; the model's _step_etdrk4 calls
+    _before_step / _after_step (nq_any_particles_rk4); U0, U1 are formed from m.ph with the Plane operations"""
+
+    def __init__(self, m, x, y, record_every, capacity, record):
+        from ._anysize import Plane
+        Particles.__init__(self, m, len(x), record_every, capacity, record)
+        self.eng = m._eng
+        self.pos = self.eng.plane((x + 1j * y).reshape(1, -1), real=False)
+        self.U, self.src = None, None       # velocity plane of the state src (the psi-hat Plane it was formed from)
+        self.ring = [None] * (capacity if record_every > 0 else 0)
+        self.count, self.steps = 0, 0
+        self._Plane = Plane
+        if record_every > 0:
+            self._record()
+
+    def _velocity(self):
+        m = self.m
+        d, K = m._d, m._K
+        ph = d["ph"]
+        if _is_qg(m):
+            u, v = m._irfft(K["mil"] * ph), m._irfft(K["ik"] * ph)
+        else:
+            u, v = m._ifft(K["mil"] * ph).real, m._ifft(K["ik"] * ph).real
+        return u + v * 1j, ph
+
+    def _current_U(self):
+        if self.U is None or self.src is not self.m._d["ph"]:
+            self.U, self.src = self._velocity()
+        return self.U
+
+    def _interp(self, plane):
+        e = self.eng
+        out = self._Plane(e, (1, self.n))
+        m = self.m
+        e.chk(e.L.nq_any_interp(e.h, out.ptr, plane.ptr, self.pos.ptr, self.n, m.nx, float(m.L), float(m.W)), "nq_any_interp")
+        return out
+
+    def _planes(self, names):
+        d, out = self.m._d, {}
+        for nm in names:
+            if nm in ("u", "v"):
+                uv = self._interp(self._current_U())
+                out[nm] = uv.real if nm == "u" else uv.imag
+            else:
+                out[nm] = self._interp(d[nm])
+        return out
+
+    def _record(self):
+        if not self.ring:
+            return
+        self.ring[self.count % len(self.ring)] = (self.steps, self.pos.copy(), self._planes(self.record))
+        self.count += 1
+
+    def _before_step(self):
+        self.U0 = self._current_U()
+
+    def _after_step(self):
+        e, m = self.eng, self.m
+        U1 = self._current_U()
+        e.chk(e.L.nq_any_particles_rk4(e.h, self.pos.ptr, self.n, self.U0.ptr, U1.ptr, m.nx, float(m.L), float(m.W), float(m.U),
+                                       float(m.dt)), "nq_any_particles_rk4")
+        self.U0 = None
+        self.steps += 1
+        if self.record_every > 0 and self.steps % self.record_every == 0:
+            self._record()
+
+    def _positions(self):
+        p = self.pos.get().reshape(-1)
+        return p.real.copy(), p.imag.copy()
+
+    def _sample(self, names):
+        pl = self._planes(names)
+        return {nm: (pl[nm].get().reshape(-1) if nm == "phi" else pl[nm].get().reshape(-1).real.copy()) for nm in names}
+
+    def _records(self):
+        m = min(self.count, len(self.ring))
+        recs = [self.ring[(self.count - m + r) % len(self.ring)] for r in range(m)]
+        steps = np.array([r[0] for r in recs], np.int64)
+        pos = np.array([r[1].get().reshape(-1) for r in recs]).reshape(m, self.n)
+        vals = {}
+        for nm in self.record:
+            a = np.array([r[2][nm].get().reshape(-1) for r in recs]).reshape(m, self.n)
+            vals[nm] = a if nm == "phi" else a.real.copy()
+        return steps, pos.real.copy(), pos.imag.copy(), vals
+
+    def _detach(self):
+        self.pos = self.U = self.src = self.U0 = None
+        self.ring = []
+        self.eng.sync()
+
+
+def attach(m, x, y, record_every=0, capacity=1024, record=()):
+    """Attach n particles at (x, y) to model m (one set per model); see the module's doc.  Argument errors raise ValueError
+    before the device is touched; slab-decomposed models raise NotImplementedError."""
+    x, y = _coords(x, y)
+    if isinstance(record_every, bool) or int(record_every) != record_every or record_every < 0:
+        raise ValueError("particles.attach: record_every = %r (an integer >= 0)" % (record_every,))
+    record_every = int(record_every)
+    if record_every > 0 and (int(capacity) != capacity or capacity < 1):
+        raise ValueError("particles.attach: capacity = %r (>= 1 while recording)" % (capacity,))
+    capacity = int(capacity) if record_every > 0 else 0
+    record = tuple(_names(m, record, "attach"))
+    if len(set(record)) != len(record):
+        raise ValueError("particles.attach: a name appears twice in record: %s" % (record,))
+    if m.__dict__.get("_particles") is not None:
+        raise RuntimeError("particles.attach: this model has particles attached already (detach them first)")
+    if getattr(m, "_any_size", False):
+        P = _AnySize(m, x, y, record_every, capacity, record)
+    elif isinstance(m._ctx, _lib.Context):
+        P = _Fused(m, x, y, record_every, capacity, record)
+    else:
+        raise NotImplementedError("particles.attach: slab-decomposed models have no particles yet (they need the interpolation "
+                                  "partials exchanged between the ranks at every stage; DESIGN.md section 7)")
+    m.__dict__["_particles"] = P
+    return P
