@@ -269,6 +269,18 @@ int nq_get_coeff(nq_ctx* ctx, int eq, int which, double* out_cplx);
 int nq_coeff_near_contour(nq_ctx* ctx, int eq, double delta, int cap, int* l_out, int* k_out);
 int nq_coeff_patch(nq_ctx* ctx, int eq, int n, const int* l, const int* k, const double* vals_cplx);
 
+/* ---- the q update beside the wave-PV row kernel (single rank, CoupledModel) ----------
+ * At 4096^2 the step runs the q update (memory-bound) on a second stream beside the wave-PV row kernel (bound by its
+ * transforms), whose persistent grid leaves some CUs free for it.  NIWQG_AMD_OVERLAP_CUS is read once, by nq_create: unset =
+ * the measured default, 0 = the serial step, n > 0 = free about n CUs (also honoured at 8192^2, where the default is the serial
+ * step).  Results are bit-identical either way.  nq_overlap_grid is pure host arithmetic: the smallest persistent grid for nb
+ * row blocks that needs no more rounds than `cus` workgroups would.  nq_overlap_default_cus: the default for an nx^2 grid
+ * (0 = serial).  nq_overlap_info: out3 = {CUs left free, wave-PV grid, CUs of the device} of this context, all 0 when its
+ * step is the serial one.                                                                                                 */
+int nq_overlap_grid(int nb, int cus);
+int nq_overlap_default_cus(int nx);
+int nq_overlap_info(const nq_ctx* ctx, int* out3);
+
 /* ---- 1-D slab decomposition over nranks GPUs (one process per GPU) -----------------
  * Rows of the mixed-space planes are split over ranks on the "x side" (row kernels), columns on the "y side"
  * (spectral kernels).  Arrays that cross together form an exchange group g = 0..3; each group has an x-side

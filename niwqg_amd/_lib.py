@@ -32,7 +32,7 @@ EXPORTS = ["nq_create", "nq_destroy", "nq_last_error", "nq_set_q", "nq_set_c", "
            "nq_step", "nq_profile_stride", "nq_request_stage4_max", "nq_get_stage4_max", "nq_tick_snapshot", "nq_sync", "nq_get_field", "nq_get_qh_passenger", "nq_get_scalar", "nq_fft2", "nq_ifft2", "nq_rfft2",
            "nq_irfft2", "nq_jacobian_psi_q", "nq_jacobian_psi_c", "nq_jacobian_psi_phi", "nq_jacobian_phic_phi", "nq_products_uq_vq", "nq_refraction", "nq_field_doubles", "nq_get_coeff", "nq_coeff_near_contour", "nq_coeff_patch", "nq_diagnostics", "nq_spectrum_shells", "nq_diagnostics_binned", "nq_transfer_binned",
            "nq_particles_attach", "nq_particles_detach", "nq_particles_get", "nq_particles_sample", "nq_particles_records",
-           "nq_stream_copy_gbs", "nq_timer_start", "nq_timer_stop", "nq_event_record", "nq_event_elapsed", "nq_profile_enable", "nq_profile_read", "nq_profile_read_all", "nq_group_elems", "nq_create_slab",
+           "nq_stream_copy_gbs", "nq_timer_start", "nq_timer_stop", "nq_event_record", "nq_event_elapsed", "nq_profile_enable", "nq_profile_read", "nq_profile_read_all", "nq_group_elems", "nq_overlap_grid", "nq_overlap_default_cus", "nq_overlap_info", "nq_create_slab",
            "nq_slab_info", "nq_group_buffers", "nq_upload_spectral", "nq_download_spectral", "nq_phase",
            "nq_reduce_buffer", "nq_reduce_read", "nq_reduce_write", "nq_device_bytes", "nq_stream",
            "nq_comm_probe", "nq_comm_unique_id", "nq_comm_init", "nq_slab_attach_peers", "nq_slab_set_callbacks", "nq_slab_set_null_link", "nq_slab_config", "nq_slab_set_stage_buffers", "nq_slab_spectral", "nq_slab_spectral_read",
@@ -140,6 +140,9 @@ def lib():
     L.nq_profile_read_all.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float)]
     L.nq_group_elems.argtypes = [ctypes.POINTER(Params), ctypes.c_int, ctypes.c_int]
     L.nq_group_elems.restype = ctypes.c_longlong
+    L.nq_overlap_grid.argtypes = [ctypes.c_int, ctypes.c_int]
+    L.nq_overlap_default_cus.argtypes = [ctypes.c_int]
+    L.nq_overlap_info.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
     L.nq_create_slab.argtypes = [ctypes.POINTER(Params), dp, dp, dp, dp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                  ctypes.POINTER(vp), vp, ctypes.POINTER(vp)]
     L.nq_slab_info.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]

@@ -145,10 +145,11 @@ struct nq_ctx {
   hipEvent_t ev_snap = nullptr;
   bool snap_busy = false;
   // single-rank CoupledModel: the q update (memory-bound) runs on a second stream beside the wave-PV row kernel
-  // (transform-engine bound), which then leaves `overlap_cus` CUs free for it (0 = off)
+  // (transform-engine bound), whose persistent grid shrinks to `overlap_grid` workgroups and so leaves
+  // `overlap_cus` = num_cu - overlap_grid CUs free for it (0 = off: the serial step); DESIGN.md section 8
   hipStream_t stream2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  int overlap_cus = 0;
+  int overlap_cus = 0, overlap_grid = 0;
   // ---- slab step inside the library: how the exchange groups cross between the ranks
   int link = 0;                        // LINK_*: 0 none, 1 peers in this process, 2 RCCL, 3 caller's callbacks, 4 nothing on the wire (nq_slab_set_null_link)
   std::vector<nq_ctx*> peers;          // LINK_PEERS: every rank's context (index = rank), the same list on all of them
@@ -1175,7 +1176,7 @@ static void launch_wavepv_t(nq_ctx* c) {
     case 8192:
       {                                               // even / odd samples as two 4096-point problems (no spills)
         typedef XPlan<4096> X;
-        const int ncu = c->num_cu - c->reserve_cus, nb = c->nrows, grid = nb < ncu ? nb : ncu;
+        const int ncu = (c->stream2 ? c->overlap_grid : c->num_cu) - c->reserve_cus, nb = c->nrows, grid = nb < ncu ? nb : ncu;
         const size_t ldsb = X::LDS_BYTES + (size_t)4096 * sizeof(cd) ;          // + the 64 KB of thread-private park slots
         hipLaunchKernelGGL((k_x_wavepv_eo<8192, SLAB>), dim3(grid), dim3(X::THREADS), ldsb, c->stream, mPhi, mPhiy, mA, mB, c->twx_half, c->tw, c->kk, nb);
       }
@@ -1183,7 +1184,7 @@ static void launch_wavepv_t(nq_ctx* c) {
     case 4096: {                                      // long rows: two transforms in flight, no spills
       typedef XPlan<4096> X;
       const size_t ldsb = X::LDS_BYTES + X::F::LDS_ELEMS * sizeof(cd);
-      int grid = c->num_cu - (c->stream2 ? c->overlap_cus : 0) - c->reserve_cus;   // one persistent workgroup per CU
+      int grid = (c->stream2 ? c->overlap_grid : c->num_cu) - c->reserve_cus;      // one persistent workgroup per CU
       const int nb = c->nrows / X::C;
       if (grid > nb) grid = nb;
       hipLaunchKernelGGL((k_x_wavepv2<4096, SLAB>), dim3(grid), dim3(X::THREADS), ldsb, c->stream, mPhi, mPhiy, mA, mB, c->twx, c->kk, nb);
@@ -1412,8 +1413,11 @@ static const cd* stage_qh_out(nq_ctx* c, int stage) {
   const int cur = c->q.cur;
   return c->q.y[(stage == 0) ? (cur + 1) % 3 : (stage == 3 ? cur : (cur + 2) % 3)];
 }
-static void phase_invert_y(nq_ctx* c, const cd* qh, bool store_aux, double* part, const cd* q_bud, const cd* c_hat = nullptr) {
+// join: recorded by another stream once qh is complete (do_step_overlap); the forward columns of a, b do not read qh
+static void phase_invert_y(nq_ctx* c, const cd* qh, bool store_aux, double* part, const cd* q_bud, const cd* c_hat = nullptr,
+                           hipEvent_t join = nullptr) {
   if (c->p.model == NQ_MODEL_COUPLED) launch_A_m(c, false, {&c->mA, &c->mB});
+  if (join) (void)hipStreamWaitEvent(c->stream, join, 0);
   launch_invert(c, qh, store_aux, part, q_bud, c_hat);
   if (c->p.model == NQ_MODEL_COUPLED || c->passive) launch_A_m(c, true, {&c->mU, &c->mP, &c->mQ, &c->mQw});
   else launch_A_m(c, true, {&c->mU, &c->mP, &c->mQ});
@@ -1453,8 +1457,8 @@ static void phase_update(nq_ctx* c, int s) {
   }
 }
 static void phase_wavepv(nq_ctx* c) { launch_wavepv(c); }
-static void phase_invert(nq_ctx* c, int s) {      // Coupled only
-  phase_invert_y(c, stage_qh_out(c, s), s == 3, c->partQ + (size_t)s * c->nwq * 3, nullptr);
+static void phase_invert(nq_ctx* c, int s, hipEvent_t join = nullptr) {      // Coupled only
+  phase_invert_y(c, stage_qh_out(c, s), s == 3, c->partQ + (size_t)s * c->nwq * 3, nullptr, nullptr, join);
 }
 static void phase_budget_sums(nq_ctx* c) {
   if (c->bud) hipLaunchKernelGGL(k_budget_sums, dim3(44), dim3(1024), 0, c->stream, budget_acc(c), c->bsums);
@@ -1518,9 +1522,40 @@ static void do_step_ybj(nq_ctx* c) {
   }
 }
 
+// A persistent row kernel walks nb row blocks with g workgroups in ceil(nb / g) rounds, and the last round is as long as
+// the others however few blocks it holds.  Of all grids that fit into `cus` CUs this is the SMALLEST one that needs no more
+// rounds than `cus` itself would: the row kernel loses nothing against `cus`, the CUs it gives up go to the other stream,
+// and the idle share of its last round, rounds * g / nb - 1, is below rounds / nb (nb = 4096: 171 -> 171 in 24 rounds,
+// 0.2 %; 160 -> 158 in 26 rounds, 0.3 %).
+#define NQ_OVERLAP_CUS_DEFAULT 128     /* 4096^2: wave-PV grid 128 = 32 full rounds; from the sweep in DESIGN.md section 8 */
+int nq_overlap_grid(int nb, int cus) {
+  if (nb < 1 || cus < 1) return 0;
+  if (cus >= nb) return nb;
+  const int rounds = (nb + cus - 1) / cus;
+  return (nb + rounds - 1) / rounds;
+}
+
+int nq_overlap_default_cus(int nx) { return nx == 4096 ? NQ_OVERLAP_CUS_DEFAULT : 0; }
+int nq_overlap_info(const nq_ctx* c, int* out3) {
+  if (!c || !out3) return -1;
+  out3[0] = c->stream2 ? c->overlap_cus : 0;
+  out3[1] = c->stream2 ? c->overlap_grid : 0;
+  out3[2] = c->stream2 ? c->num_cu : 0;
+  return 0;
+}
+
 // CoupledModel, one rank: same kernels as do_step, but the q update waits until the wave-PV row kernel starts and
-// runs beside it on a second stream.  k_x_wavepv2 is bound by its row transforms and uses a persistent grid of
-// (CUs - overlap_cus) workgroups; the spectral q kernels need 34 KB of LDS, which only the CUs it left free can give.
+// runs beside it on a second stream.  The wave-PV kernel is bound by its row transforms and uses a persistent grid of
+// overlap_grid workgroups; the spectral q kernels need 34 KB of LDS, which only the CUs it left free can give.
+// The fork is recorded after the inverse columns of phi, phiy and the wait is queued on stream2 BEFORE the host reaches
+// launch_wavepv, so both branches become ready at the same moment: beside k_s_phi or k_y_A (memory-bound as well) the
+// q branch would gain nothing.
+// The join sits as late as the data allow: k_s_invert is the first reader of the new qh, the forward columns of a, b before it
+// touch neither qh nor uq, vq, and whichever branch ends first no longer leaves its CUs idle until the other one is done.
+// Invariant of the join: the main stream waits for ev_join before k_s_invert of the SAME stage, so after every stage
+// and when do_step_overlap returns, all work of stream2 is ordered before whatever the main stream runs next.  Every reader
+// of the state (set_q / set_phi, the getters, diagnostics, nq_tick_snapshot, the particles' sampling before and after a
+// step, stage4_uv_max after stage 2, the next step's fork) is issued on the main stream and needs no second wait.
 static void do_step_overlap(nq_ctx* c) {
   hipStream_t main_stream = c->stream;
   for (int s = 0; s < 4; ++s) {
@@ -1541,8 +1576,7 @@ static void do_step_overlap(nq_ctx* c) {
     (void)hipEventRecord(c->ev_join, c->stream2);
     c->stream = main_stream;
     phase_wavepv(c);
-    (void)hipStreamWaitEvent(main_stream, c->ev_join, 0);
-    phase_invert(c, s);
+    phase_invert(c, s, c->ev_join);                           // joins between the forward columns of a, b and k_s_invert
     if (s == 2 && c->uv4_now) (void)stage4_uv_max(c);
   }
   phase_budget_sums(c);
@@ -1551,7 +1585,7 @@ static void do_step_overlap(nq_ctx* c) {
 
 static void do_step(nq_ctx* c) {      // P == 1
   if (c->ybj) return do_step_ybj(c);
-  if (c->stream2 && c->p.model == NQ_MODEL_COUPLED && c->N == 4096 && !c->dual) return do_step_overlap(c);
+  if (c->stream2) return do_step_overlap(c);       // nq_create made stream2 only where this step applies
   for (int s = 0; s < 4; ++s) {
     phase_products(c, s);
     phase_update(c, s);
@@ -2461,10 +2495,15 @@ static int create_impl(const nq_params* p_in, const double* kk, const double* ll
       c->mUc = make_marr(sg, c->G[0].bx, c->G[0].by, 0, 2, true);
       c->mVc = make_marr(sg, c->G[0].bx, c->G[0].by, 0, 3, true);
     }
-    if (P == 1 && p->model == NQ_MODEL_COUPLED && N == 4096) {
+    if (P == 1 && p->model == NQ_MODEL_COUPLED && !c->dual && (N == 4096 || N == 8192)) {
+      // NIWQG_AMD_OVERLAP_CUS: unset = the measured default (4096^2 only), 0 = the serial step,
+      // n > 0 = leave about n CUs to the q branch (the wave-PV grid is nq_overlap_grid of the rest, which may free a few more)
       const char* e = getenv("NIWQG_AMD_OVERLAP_CUS");
-      c->overlap_cus = e ? atoi(e) : 0;
-      if (c->overlap_cus > 0 && c->overlap_cus < c->num_cu) {
+      const int want = e ? atoi(e) : nq_overlap_default_cus(N);
+      if (want > 0 && want < c->num_cu) {
+        const int nb = N == 4096 ? N / XPlan<4096>::C : N;
+        c->overlap_grid = nq_overlap_grid(nb, c->num_cu - want);
+        c->overlap_cus = c->num_cu - c->overlap_grid;
         HIPCHK(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
         HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
@@ -2560,7 +2599,10 @@ int nq_destroy(nq_ctx* c) {
     if (e) hipEventDestroy(e);
   for (hipEvent_t e : c->xev) hipEventDestroy(e);
   if (c->mstream) hipStreamDestroy(c->mstream);
-  if (c->stream2) hipStreamDestroy(c->stream2);
+  if (c->stream2) {
+    hipStreamSynchronize(c->stream2);
+    hipStreamDestroy(c->stream2);
+  }
   if (c->ev_fork) hipEventDestroy(c->ev_fork);
   if (c->ev_join) hipEventDestroy(c->ev_join);
   if (c->stream && c->own_stream) hipStreamDestroy(c->stream);
