@@ -228,6 +228,33 @@ int nq_diagnostics_binned(nq_ctx* ctx, int nb, double* out);
 #define NQ_TRANSFER_ROWS 6
 int nq_transfer_binned(nq_ctx* ctx, int nb, double* out);
 
+/* PDFs and joint PDFs of the physical fields: COUNTS of the values the tick's physical sums [16..23] see.
+ * Fields: NQ_PDF_Q q, NQ_PDF_QPSI q_psi = q - q_w (= q without the wave feedback), NQ_PDF_PHI2 |phi|^2 of the last inversion's rows
+ * (Kernel family; dual_q contexts: the mean of the two q-hat copies); QGModel: NQ_PDF_Q and, with its passive scalar, NQ_PDF_C of
+ * the current spectra.  Bin rule (fp64, the same __device__ function everywhere): s = bins / (hi - lo) formed once on the host;
+ * x != x -> NaN; x < lo -> below; x > hi -> above; else i = min((int) floor((x - lo) * s), bins - 1), so x == hi is in the last bin.
+ *
+ * nq_field_minmax: out[2 i], out[2 i + 1] = exact minimum and maximum of fields[i] (both NaN when any value is), one device pass.
+ * nq_field_hist:   bins the listed fields (1 to 3, each once) over [lo[i], hi[i]] (finite, lo < hi) into `bins` (1..1024) bins
+ *   each; joint_a, joint_b >= 0: also ONE table of joint_bins (1..128) bins per axis over the same ranges for that pair of the
+ *   list (joint_a = joint_b = -1: none).  accumulate = 0 zeroes the device tables first; 1 adds to what they hold and needs the
+ *   fields, ranges and bin counts of the call that zeroed them.  Nothing is copied to the host.
+ * nq_field_hist_read: the tables of the last nq_field_hist configuration as 64-bit counts: per field of its list bins + 3
+ *   (the bins, below, above, NaN), then, with a joint table, joint_bins^2 + 1: [index of b][index of a], then the points with
+ *   either value out of range or NaN.
+ * Integer counters only (32-bit in LDS per workgroup, 64-bit in global memory): bit-reproducible.  The Kernel family writes no
+ * physical plane; QGModel goes through the scratch planes of nq_get_field.  The first call allocates the tables of the largest
+ * configuration and the min/max partials, NQ_PDF_DEVICE_BYTES in all (counted by nq_device_bytes, freed with the context).
+ * Reads the state, writes only these buffers.  Single-rank contexts (-4 on slab contexts).                                    */
+enum { NQ_PDF_Q = 0, NQ_PDF_QPSI = 1, NQ_PDF_PHI2 = 2, NQ_PDF_C = 3 };
+#define NQ_PDF_MAX_BINS 1024
+#define NQ_PDF_MAX_JOINT_BINS 128
+#define NQ_PDF_DEVICE_BYTES ((3 * (NQ_PDF_MAX_BINS + 3) + NQ_PDF_MAX_JOINT_BINS * NQ_PDF_MAX_JOINT_BINS + 1) * 8 + 6 * 8192 * 8)
+int nq_field_minmax(nq_ctx* ctx, int nfields, const int* fields, double* out);
+int nq_field_hist(nq_ctx* ctx, int nfields, const int* fields, const double* lo, const double* hi, int bins, int joint_a,
+                  int joint_b, int joint_bins, int accumulate);
+int nq_field_hist_read(nq_ctx* ctx, unsigned long long* out);
+
 /* Lagrangian particles, single-rank contexts only (slab contexts refuse every call with -4).
  * After every step of nq_step the library moves each particle one classical RK4 step through U_tot = (U + u, v), u = -d psi/dy,
  * v = d psi/dx of the ph the context holds, linear in time between U0 (start of the step) and U1 (after it):
@@ -473,6 +500,14 @@ int nq_any_set_elem(nq_any* eng, void* plane, long long index, double re, double
  * plane (rows, rows/2 + 1); out: nb = round(rows / sqrt 2) + 1 doubles; the integer shell rule and the deterministic kernel of
  * nq_diagnostics_binned (no weights: the caller forms each element's term, half planes with their weight folded in).    */
 int nq_any_bin(nq_any* eng, const void* plane, int rows, int cols, int layout, int nb, double* out);
+/* PDFs on engine planes (nq_field_hist's bin rule and counting kernel): what 0 = Re of the plane, 1 = |a|^2, over `elems` complex
+ * values.  nq_any_hist: out[bins + 3] = the bins (1..1024), below, above, NaN.  nq_any_hist2, the joint form: bins (1..128) per
+ * axis, lo2 / hi2 the ranges of a and b, out[bins^2 + 1] = [index of b][index of a], then the points with either value out of
+ * range or NaN.  nq_any_minmax: out2 = exact minimum and maximum (both NaN when any value is).  Synchronous, like nq_any_bin. */
+int nq_any_hist(nq_any* eng, const void* plane, long long elems, int what, double lo, double hi, int bins, unsigned long long* out);
+int nq_any_hist2(nq_any* eng, const void* plane_a, const void* plane_b, long long elems, int what_a, int what_b, const double* lo2,
+                 const double* hi2, int bins, unsigned long long* out);
+int nq_any_minmax(nq_any* eng, const void* plane, long long elems, int what, double* out2);
 /* Lagrangian particles on engine planes (the RK4 step and interpolation of nq_particles_attach above): pos holds n complex
  * x + i y; U0, U1 and plane are (nx, nx) complex planes, velocity planes as u + i v; out[i] = plane at pos[i] (real and
  * imaginary parts interpolated each) */

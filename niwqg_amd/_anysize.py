@@ -685,6 +685,20 @@ class KernelFamily(object):
                     out["xi_a"] = self._bin(diss.conj() * R * (0.5 / M2f), 0)
         return out
 
+    # ---- PDFs of the physical fields (niwqg_amd/pdfs.py) ------------------------------------------
+    def _pdf_planes(self, names):
+        """{name: (plane, what)} for nq_any_hist (what 0: Re, 1: |a|^2): q, phi are the planes this path holds, q_psi is formed
+        locally as _spectra does; nothing this path keeps is written"""
+        d, out = self._d, {}
+        for n in names:
+            if n == "q":
+                out[n] = (d["q"], 0)
+            elif n == "q_psi":
+                out[n] = (d["q"] - self._ifft(d["qwh"]).real if self.model_id == _lib.COUPLED else d["q"], 0)
+            elif n == "phi2":
+                out[n] = (d["phi"], 1)
+        return out
+
     # ---- spectral transfer (niwqg_amd/transfer.py; DESIGN.md section 5f) ----------------------------------------------
     def _transfer(self, names):
         """the named transfer spectra of the current state: the full-plane co-spectra of the definitions (psi-hat, q-hat, phi-hat
@@ -1094,6 +1108,11 @@ class QGFamily(object):
             if "gradC2" in need:
                 out["gradC2"] = self._bin(K["wv2"] * t, 1)
         return out
+
+    # ---- PDFs of the physical fields (niwqg_amd/pdfs.py) ------------------------------------------
+    def _pdf_planes(self, names):
+        """{name: (plane, what)} for nq_any_hist: q and c are the real planes this path holds (current after every step)"""
+        return {n: (self._d[n], 0) for n in names}
 
     def _calc_derived_fields(self):     # ref: niwqg/QGModel.py:724-737
         if self.passive_scalar:

@@ -20,7 +20,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # NIWQG_AMD_LIB: another build of the same sources (A/B experiments with compile-time knobs, tools/); default: the in-tree library
 LIB_PATH = os.environ.get("NIWQG_AMD_LIB") or os.path.join(HERE, "libniwqg_amd.so")
 SRC = os.path.join(HERE, "csrc", "nq_lib.hip")
-HEADERS = [os.path.join(HERE, "csrc", h) for h in ("nq_fft.hpp", "nq_generic.hpp", "nq_step.hpp", "nq_anysize.hpp", "nq_particles.hpp")] + [
+HEADERS = [os.path.join(HERE, "csrc", h) for h in ("nq_fft.hpp", "nq_generic.hpp", "nq_step.hpp", "nq_anysize.hpp", "nq_particles.hpp", "nq_hist.hpp")] + [
     os.path.join(os.path.dirname(HERE), "include", "niwqg_amd.h")]
 
 COUPLED, UNCOUPLED, QG, YBJ = 0, 1, 2, 3
@@ -40,7 +40,12 @@ EXPORTS = ["nq_create", "nq_destroy", "nq_last_error", "nq_set_q", "nq_set_c", "
            "nq_slab_local_max", "nq_slab_counters", "nq_slab_allreduce_ms", "nq_snapshot_begin", "nq_snapshot_end",
            "nq_any_create", "nq_any_destroy", "nq_any_last_error", "nq_any_sync", "nq_any_device_bytes", "nq_any_alloc", "nq_any_free",
            "nq_any_upload", "nq_any_download", "nq_any_fft", "nq_any_ew", "nq_any_reduce", "nq_any_expand_half", "nq_any_take_cols",
+           "nq_field_minmax", "nq_field_hist", "nq_field_hist_read", "nq_any_hist", "nq_any_hist2", "nq_any_minmax",
            "nq_any_set_elem", "nq_any_bin", "nq_any_etdrk4", "nq_any_etdrk4_patch", "nq_any_particles_rk4", "nq_any_interp"]
+
+(PDF_Q, PDF_QPSI, PDF_PHI2, PDF_C) = range(4)      # fields of nq_field_hist (include/niwqg_amd.h: NQ_PDF_*)
+PDF_MAX_BINS, PDF_MAX_JOINT_BINS = 1024, 128
+PDF_DEVICE_BYTES = (3 * (PDF_MAX_BINS + 3) + PDF_MAX_JOINT_BINS ** 2 + 1) * 8 + 6 * 8192 * 8     # NQ_PDF_DEVICE_BYTES
 
 TRANSFER_ROWS = 6                 # rows of nq_transfer_binned (include/niwqg_amd.h: NQ_TRANSFER_ROWS)
 
@@ -196,6 +201,13 @@ def lib():
     L.nq_any_take_cols.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.nq_any_set_elem.argtypes = [vp, vp, ctypes.c_longlong, ctypes.c_double, ctypes.c_double]
     L.nq_any_bin.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp]
+    ullp = ctypes.POINTER(ctypes.c_ulonglong)
+    L.nq_field_minmax.argtypes = [vp, ctypes.c_int, ip, dp]
+    L.nq_field_hist.argtypes = [vp, ctypes.c_int, ip, dp, dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    L.nq_field_hist_read.argtypes = [vp, ullp]
+    L.nq_any_hist.argtypes = [vp, vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, ullp]
+    L.nq_any_hist2.argtypes = [vp, vp, vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, dp, dp, ctypes.c_int, ullp]
+    L.nq_any_minmax.argtypes = [vp, vp, ctypes.c_longlong, ctypes.c_int, dp]
     L.nq_any_particles_rk4.argtypes = [vp, vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                        ctypes.c_double]
     L.nq_any_interp.argtypes = [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double]
@@ -542,3 +554,26 @@ class Context:
         out = np.empty((m, w, n))
         self._chk(self.L.nq_particles_records(self.h, info, steps, _dptr(out)), "nq_particles_records")
         return np.array(steps[:m], np.int64), out
+
+    # ---- PDFs of the physical fields (include/niwqg_amd.h: nq_field_hist; niwqg_amd/pdfs.py) --------------------------------
+    def field_minmax(self, codes):
+        """[(min, max)] of the listed fields (PDF_*), exact, from one device pass"""
+        out = np.empty((len(codes), 2))
+        c = (ctypes.c_int * len(codes))(*codes)
+        self._chk(self.L.nq_field_minmax(self.h, len(codes), c, _dptr(out)), "nq_field_minmax")
+        return [(float(a), float(b)) for a, b in out]
+
+    def field_hist(self, codes, lo, hi, bins, joint=None, joint_bins=0, accumulate=False):
+        """bin the listed fields on the device (nothing comes back: field_hist_read)"""
+        c = (ctypes.c_int * len(codes))(*codes)
+        lo, hi = np.ascontiguousarray(lo, np.float64), np.ascontiguousarray(hi, np.float64)
+        ja, jb = joint if joint is not None else (-1, -1)
+        self._chk(self.L.nq_field_hist(self.h, len(codes), c, _dptr(lo), _dptr(hi), int(bins), int(ja), int(jb), int(joint_bins),
+                                       int(bool(accumulate))), "nq_field_hist")
+
+    def field_hist_read(self, nfields, bins, joint_bins=0):
+        """(counts (nfields, bins + 3) uint64 [bins, below, above, nan], joint (joint_bins^2 + 1,) uint64 or None)"""
+        n1 = nfields * (bins + 3)
+        out = np.zeros(n1 + (joint_bins * joint_bins + 1 if joint_bins else 0), np.uint64)
+        self._chk(self.L.nq_field_hist_read(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong))), "nq_field_hist_read")
+        return out[:n1].reshape(nfields, bins + 3), (out[n1:] if joint_bins else None)

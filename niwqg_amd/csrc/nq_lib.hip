@@ -12,6 +12,7 @@
 #include "nq_step.hpp"
 #include "nq_anysize.hpp"
 #include "nq_particles.hpp"
+#include "nq_hist.hpp"
 
 using namespace nq;
 
@@ -121,6 +122,11 @@ struct nq_ctx {
   double *diag_part = nullptr, *diag_out = nullptr;   // diagnostics tick: workgroup partials, 32 reduced sums
   double *spec_out = nullptr, *spec_r = nullptr;     // isotropic spectra of the tick: 32 x nb shell sums, two real planes
   double* tr_out = nullptr;                          // spectral transfer: NQ_TRANSFER_ROWS x nb shell sums
+  // PDFs of the physical fields (nq_field_hist): 64-bit tables of the largest configuration and the min/max partials,
+  // allocated by the first call; the configuration of the last binning call (what nq_field_hist_read copies out)
+  unsigned long long* hist_tab = nullptr;
+  double* hist_part = nullptr;
+  struct HistCfg { int nf = 0, fields[4] = {0, 0, 0, 0}, bins = 0, jbins = 0, ja = -1, jb = -1; double lo[4] = {}, hi[4] = {}; } hist_cfg;
   cd *tr_h = nullptr, *tr_f = nullptr;               // its planes on slab contexts (two half, one full-width; P == 1: scr_*)
   double *carryW = nullptr, *carryQ = nullptr;    // spectral sums of the state at the start of the next step
   double *gradS1 = nullptr, *acc = nullptr;       // stale-aware sum wv2|phih_grad|^2 ; Ke,Pw,Kw increments
@@ -2115,6 +2121,23 @@ static int xdiag_blocks(const nq_ctx* c) {
   }
   return 0;
 }
+
+// PDFs of the physical fields (csrc/nq_hist.hpp): the tick's row pass with the binning (or the min/max) in place of the sums
+template <int MODE, bool SLAB, bool MINMAX>
+static void launch_xhist_t(nq_ctx* c, const HistArgs& h, double* part) {
+  const int words = MINMAX ? 0 : hist_words(h.bins, h.jbins);
+  switch (c->N) {
+#define CASE_(n, a, b) case n: { typedef XPlan<n> X; hipLaunchKernelGGL((k_x_hist<n, MODE, SLAB, MINMAX>), dim3(c->Nloc / X::C), dim3(X::THREADS), hist_lds_bytes<n>(words), c->stream, c->mQ, c->mQw, c->mPhi, c->twx, c->kk, h, part); } break;
+    NQ_FOR_SIZES(CASE_)
+#undef CASE_
+  }
+}
+template <bool MINMAX>
+static void launch_xhist(nq_ctx* c, const HistArgs& h, double* part) {
+  if (c->p.model == NQ_MODEL_COUPLED) launch_xhist_t<MODE_COUPLED, false, MINMAX>(c, h, part);
+  else launch_xhist_t<MODE_UNCOUPLED, false, MINMAX>(c, h, part);
+}
+static int hist_plane_grid(size_t n) { return (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024); }
 
 // 1 read + 1 write stream copy, 16 B per lane: the rate a copy kernel reaches on THIS device, the second denominator of
 // bench.py's roofline fractions.  Three shapes are timed and the best is reported (tools/copy_shape_bench.hip
@@ -4321,6 +4344,183 @@ int nq_diagnostics(nq_ctx* c, double* out) {
   return nq_sync(c);
 }
 
+// ---- PDFs and joint PDFs of the physical fields (csrc/nq_hist.hpp) -----------------------------------
+// slot of a public field id in the tables and the kernels: Kernel family q, q_psi, |phi|^2 -> 0, 1, 2; QGModel q, c -> 0, 1
+static int hist_slot(const nq_ctx* c, int field) {
+  if (c->kernel_family) return (field >= NQ_PDF_Q && field <= NQ_PDF_PHI2) ? field : -1;
+  if (field == NQ_PDF_Q) return 0;
+  return (field == NQ_PDF_C && c->passive) ? 1 : -1;
+}
+static int hist_check_fields(nq_ctx* c, const char* what, int nfields, const int* fields) {
+  NQ_SINGLE_RANK(c, "nq_field_hist");
+  if (!fields || nfields < 1 || nfields > HIST_SLOTS) NQ_FAIL(c, -1, "%s: %d fields (1 to %d)", what, nfields, HIST_SLOTS);
+  for (int i = 0; i < nfields; ++i) {
+    if (hist_slot(c, fields[i]) < 0)
+      NQ_FAIL(c, -1, "%s: field %d is not available here (Kernel family: NQ_PDF_Q, NQ_PDF_QPSI, NQ_PDF_PHI2; QGModel: NQ_PDF_Q, with its passive scalar NQ_PDF_C)", what, fields[i]);
+    for (int k = 0; k < i; ++k)
+      if (fields[k] == fields[i]) NQ_FAIL(c, -1, "%s: field %d listed twice", what, fields[i]);
+  }
+  if (c->kernel_family && !c->have_phi) NQ_FAIL(c, -4, "%s: set_phi has not been called", what);
+  return 0;
+}
+static int hist_alloc(nq_ctx* c) {
+  if (!c->hist_tab) {
+    ALLOC(c, c->hist_tab, (size_t)HIST_MAX_WORDS);
+    ALLOC(c, c->hist_part, (size_t)6 * HIST_PART_BLOCKS);
+  }
+  return 0;
+}
+// QGModel: q (and c) of the current state as real planes, by the transforms nq_get_field uses (scratch planes of the downloads)
+static void hist_qg_planes(nq_ctx* c, int mask, const double** a, const double** b) {
+  *a = *b = nullptr;
+  if (mask & 1) {
+    inv2d_half(c, c->q.y[c->q.cur], c->scr_r, c->scr_h0);
+    *a = c->scr_r;
+  }
+  if (mask & 2) {
+    inv2d_half(c, c->cq.y[c->cq.cur], reinterpret_cast<double*>(c->scr_f0), c->scr_h0);
+    *b = reinterpret_cast<const double*>(c->scr_f0);
+  }
+}
+
+int nq_field_minmax(nq_ctx* c, int nfields, const int* fields, double* out) {
+  {
+    const int rc = hist_check_fields(c, "nq_field_minmax", nfields, fields);
+    if (rc) return rc;
+  }
+  if (!out) NQ_FAIL(c, -1, "nq_field_minmax: null output");
+  HIPCHK(c, hipSetDevice(c->device));
+  {
+    const int rc = hist_alloc(c);
+    if (rc) return rc;
+  }
+  int nblk, per;
+  if (c->kernel_family) {
+    HistArgs h = {};
+    nblk = xdiag_blocks(c);
+    per = 6;
+    launch_xhist<true>(c, h, c->hist_part);
+  } else {
+    int mask = 0;
+    for (int i = 0; i < nfields; ++i) mask |= 1 << hist_slot(c, fields[i]);
+    const double *a, *b;
+    hist_qg_planes(c, mask, &a, &b);
+    const size_t n = (size_t)c->N * c->N;
+    nblk = hist_plane_grid(n);
+    per = 4;
+    hipLaunchKernelGGL(k_minmax_plane, dim3(nblk), dim3(256), 0, c->stream, a, b, n, 1, 0, 0, c->hist_part);
+  }
+  HIPCHK(c, hipGetLastError());
+  std::vector<double> part((size_t)nblk * per);
+  HIPCHK(c, hipMemcpyAsync(part.data(), c->hist_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, c->stream));
+  {
+    const int rc = nq_sync(c);
+    if (rc) return rc;
+  }
+  for (int i = 0; i < nfields; ++i) {
+    const int s = hist_slot(c, fields[i]);
+    double lo = part[2 * s], hi = part[2 * s + 1];
+    for (int k = 1; k < nblk; ++k) {                    // NaN in any workgroup's slot stays (min and max: order is irrelevant)
+      const double a = part[(size_t)k * per + 2 * s], b = part[(size_t)k * per + 2 * s + 1];
+      lo = (lo != lo || lo < a) ? lo : a;
+      hi = (hi != hi || hi > b) ? hi : b;
+    }
+    out[2 * i] = lo;
+    out[2 * i + 1] = hi;
+  }
+  return 0;
+}
+
+int nq_field_hist(nq_ctx* c, int nfields, const int* fields, const double* lo, const double* hi, int bins, int joint_a,
+                  int joint_b, int joint_bins, int accumulate) {
+  {
+    const int rc = hist_check_fields(c, "nq_field_hist", nfields, fields);
+    if (rc) return rc;
+  }
+  if (!lo || !hi) NQ_FAIL(c, -1, "nq_field_hist: null ranges");
+  if (bins < 1 || bins > HIST_MAX_BINS) NQ_FAIL(c, -1, "nq_field_hist: bins = %d (1 to %d: the LDS tables of a workgroup)", bins, HIST_MAX_BINS);
+  const bool joint = joint_a >= 0 || joint_b >= 0;
+  int ja = -1, jb = -1;
+  if (joint) {
+    if (joint_bins < 1 || joint_bins > HIST_MAX_JBINS)
+      NQ_FAIL(c, -1, "nq_field_hist: joint_bins = %d (1 to %d: the LDS tables of a workgroup)", joint_bins, HIST_MAX_JBINS);
+    for (int i = 0; i < nfields; ++i) {
+      if (fields[i] == joint_a) ja = i;
+      if (fields[i] == joint_b) jb = i;
+    }
+    if (ja < 0 || jb < 0 || ja == jb) NQ_FAIL(c, -1, "nq_field_hist: the joint pair (%d, %d) is not two different fields of the list", joint_a, joint_b);
+  }
+  for (int i = 0; i < nfields; ++i)
+    if (!std::isfinite(lo[i]) || !std::isfinite(hi[i]) || !(lo[i] < hi[i]))
+      NQ_FAIL(c, -1, "nq_field_hist: range [%g, %g] of field %d (finite, lo < hi)", lo[i], hi[i], fields[i]);
+  nq_ctx::HistCfg cfg;
+  cfg.nf = nfields;
+  cfg.bins = bins;
+  cfg.jbins = joint ? joint_bins : 0;
+  cfg.ja = ja;
+  cfg.jb = jb;
+  for (int i = 0; i < nfields; ++i) {
+    cfg.fields[i] = fields[i];
+    cfg.lo[i] = lo[i];
+    cfg.hi[i] = hi[i];
+  }
+  if (accumulate) {
+    const nq_ctx::HistCfg& o = c->hist_cfg;
+    bool same = c->hist_tab && o.nf == cfg.nf && o.bins == cfg.bins && o.jbins == cfg.jbins && o.ja == cfg.ja && o.jb == cfg.jb;
+    for (int i = 0; same && i < nfields; ++i) same = o.fields[i] == cfg.fields[i] && o.lo[i] == cfg.lo[i] && o.hi[i] == cfg.hi[i];
+    if (!same) NQ_FAIL(c, -1, "nq_field_hist: accumulate = 1 needs the fields, ranges and bin counts of the call that zeroed the tables");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  {
+    const int rc = hist_alloc(c);
+    if (rc) return rc;
+  }
+  HistArgs h = {};
+  h.bins = bins;
+  h.jbins = cfg.jbins;
+  h.tab = c->hist_tab;
+  for (int i = 0; i < nfields; ++i) {
+    const int s = hist_slot(c, fields[i]);
+    h.mask |= 1 << s;
+    h.lo[s] = lo[i];
+    h.hi[s] = hi[i];
+    h.s[s] = (double)bins / (hi[i] - lo[i]);
+  }
+  if (joint) {
+    h.ja = hist_slot(c, joint_a);
+    h.jb = hist_slot(c, joint_b);
+    h.js[0] = (double)joint_bins / (hi[ja] - lo[ja]);
+    h.js[1] = (double)joint_bins / (hi[jb] - lo[jb]);
+  }
+  const int words = hist_words(h.bins, h.jbins);
+  if (!accumulate) HIPCHK(c, hipMemsetAsync(c->hist_tab, 0, sizeof(unsigned long long) * words, c->stream));
+  if (c->kernel_family) {
+    launch_xhist<false>(c, h, nullptr);
+  } else {
+    const double *a, *b;
+    hist_qg_planes(c, h.mask, &a, &b);
+    const size_t n = (size_t)c->N * c->N;
+    hipLaunchKernelGGL(k_hist_plane, dim3(hist_plane_grid(n)), dim3(256), sizeof(unsigned) * words, c->stream, a, b, n, 1, 0, 0, h);
+  }
+  HIPCHK(c, hipGetLastError());
+  c->hist_cfg = cfg;
+  return 0;
+}
+
+int nq_field_hist_read(nq_ctx* c, unsigned long long* out) {
+  NQ_SINGLE_RANK(c, "nq_field_hist_read");
+  if (!out) NQ_FAIL(c, -1, "nq_field_hist_read: null output");
+  const nq_ctx::HistCfg& g = c->hist_cfg;
+  if (!c->hist_tab || g.nf == 0) NQ_FAIL(c, -4, "nq_field_hist_read: no nq_field_hist call yet");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t per = (size_t)g.bins + 3;
+  for (int i = 0; i < g.nf; ++i)
+    HIPCHK(c, hipMemcpyAsync(out + i * per, c->hist_tab + hist_slot(c, g.fields[i]) * per, sizeof(unsigned long long) * per, hipMemcpyDeviceToHost, c->stream));
+  if (g.jbins)
+    HIPCHK(c, hipMemcpyAsync(out + g.nf * per, c->hist_tab + HIST_SLOTS * per, sizeof(unsigned long long) * ((size_t)g.jbins * g.jbins + 1), hipMemcpyDeviceToHost, c->stream));
+  return nq_sync(c);
+}
+
 // ---- isotropic spectra of the diagnostics tick ----------------------------------------------------
 int nq_spectrum_shells(const nq_ctx* c) { return c ? nq_shell_count(c->N) : -1; }
 
@@ -5055,6 +5255,99 @@ int nq_any_bin(nq_any* e, const void* plane, int rows, int cols, int layout, int
   ANYCHK(e, hipGetLastError());
   ANYCHK(e, hipMemcpyAsync(out, d, sizeof(double) * nb, hipMemcpyDeviceToHost, e->stream));
   return nq_any_sync(e);
+}
+// PDFs on engine planes: counts of Re(plane) (what = 0) or |plane|^2 (what = 1) over `elems` complex values,
+// the bin rule and the kernels of nq_field_hist; out: bins + 3 counts (bins, below, above, NaN)
+static int any_hist_range(nq_any* e, const char* what, double lo, double hi) {
+  if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)) ANYFAIL(e, -1, "%s: range [%g, %g] (finite, lo < hi)", what, lo, hi);
+  return 0;
+}
+int nq_any_hist(nq_any* e, const void* plane, long long elems, int what, double lo, double hi, int bins, unsigned long long* out) {
+  if (!e || !plane || !out || elems <= 0) return -1;
+  if (what != 0 && what != 1) ANYFAIL(e, -1, "nq_any_hist: what = %d (0: Re, 1: |a|^2)", what);
+  if (bins < 1 || bins > HIST_MAX_BINS) ANYFAIL(e, -1, "nq_any_hist: bins = %d (1 to %d: the LDS tables of a workgroup)", bins, HIST_MAX_BINS);
+  {
+    const int rc = any_hist_range(e, "nq_any_hist", lo, hi);
+    if (rc) return rc;
+  }
+  ANYCHK(e, hipSetDevice(e->device));
+  HistArgs h = {};
+  h.bins = bins;
+  h.mask = 1;
+  h.lo[0] = lo;
+  h.hi[0] = hi;
+  h.s[0] = (double)bins / (hi - lo);
+  const int words = hist_words(bins, 0);
+  AnyScratch tmp;
+  ANYCHK(e, tmp.get(&h.tab, (size_t)words));
+  ANYCHK(e, hipMemsetAsync(h.tab, 0, sizeof(unsigned long long) * words, e->stream));
+  const size_t n = (size_t)elems;
+  hipLaunchKernelGGL(k_hist_plane, dim3(hist_plane_grid(n)), dim3(256), sizeof(unsigned) * words, e->stream,
+                     reinterpret_cast<const double*>(plane), (const double*)nullptr, n, 2, what, 0, h);
+  ANYCHK(e, hipGetLastError());
+  ANYCHK(e, hipMemcpyAsync(out, h.tab, sizeof(unsigned long long) * (bins + 3), hipMemcpyDeviceToHost, e->stream));
+  return nq_any_sync(e);
+}
+// the joint form: out[ib * bins + ia] over the pair (what_a of plane_a, what_b of plane_b), then out[bins^2] = the points
+// with either value out of its range or NaN; lo2 / hi2: the two ranges
+int nq_any_hist2(nq_any* e, const void* plane_a, const void* plane_b, long long elems, int what_a, int what_b, const double* lo2,
+                 const double* hi2, int bins, unsigned long long* out) {
+  if (!e || !plane_a || !plane_b || !lo2 || !hi2 || !out || elems <= 0) return -1;
+  if ((what_a != 0 && what_a != 1) || (what_b != 0 && what_b != 1)) ANYFAIL(e, -1, "nq_any_hist2: what = %d, %d (0: Re, 1: |a|^2)", what_a, what_b);
+  if (bins < 1 || bins > HIST_MAX_JBINS) ANYFAIL(e, -1, "nq_any_hist2: bins = %d (1 to %d per axis: the LDS tables of a workgroup)", bins, HIST_MAX_JBINS);
+  for (int i = 0; i < 2; ++i) {
+    const int rc = any_hist_range(e, "nq_any_hist2", lo2[i], hi2[i]);
+    if (rc) return rc;
+  }
+  ANYCHK(e, hipSetDevice(e->device));
+  HistArgs h = {};
+  h.bins = 1;                       // (the 1-D tables are not counted: mask = 0)
+  h.jbins = bins;
+  h.ja = 0;
+  h.jb = 1;
+  for (int i = 0; i < 2; ++i) {
+    h.lo[i] = lo2[i];
+    h.hi[i] = hi2[i];
+    h.js[i] = (double)bins / (hi2[i] - lo2[i]);
+  }
+  const int words = hist_words(h.bins, h.jbins), j0 = HIST_SLOTS * (h.bins + 3);
+  AnyScratch tmp;
+  ANYCHK(e, tmp.get(&h.tab, (size_t)words));
+  ANYCHK(e, hipMemsetAsync(h.tab, 0, sizeof(unsigned long long) * words, e->stream));
+  const size_t n = (size_t)elems;
+  hipLaunchKernelGGL(k_hist_plane, dim3(hist_plane_grid(n)), dim3(256), sizeof(unsigned) * words, e->stream,
+                     reinterpret_cast<const double*>(plane_a), reinterpret_cast<const double*>(plane_b), n, 2, what_a, what_b, h);
+  ANYCHK(e, hipGetLastError());
+  ANYCHK(e, hipMemcpyAsync(out, h.tab + j0, sizeof(unsigned long long) * ((size_t)bins * bins + 1), hipMemcpyDeviceToHost, e->stream));
+  return nq_any_sync(e);
+}
+// out2 = exact minimum and maximum of Re(plane) or |plane|^2; NaN (both) when any value is NaN
+int nq_any_minmax(nq_any* e, const void* plane, long long elems, int what, double* out2) {
+  if (!e || !plane || !out2 || elems <= 0) return -1;
+  if (what != 0 && what != 1) ANYFAIL(e, -1, "nq_any_minmax: what = %d (0: Re, 1: |a|^2)", what);
+  ANYCHK(e, hipSetDevice(e->device));
+  const size_t n = (size_t)elems;
+  const int grid = hist_plane_grid(n);
+  double* part = nullptr;
+  AnyScratch tmp;
+  ANYCHK(e, tmp.get(&part, (size_t)4 * grid));
+  hipLaunchKernelGGL(k_minmax_plane, dim3(grid), dim3(256), 0, e->stream, reinterpret_cast<const double*>(plane), (const double*)nullptr, n, 2, what, 0, part);
+  ANYCHK(e, hipGetLastError());
+  std::vector<double> host((size_t)4 * grid);
+  ANYCHK(e, hipMemcpyAsync(host.data(), part, sizeof(double) * host.size(), hipMemcpyDeviceToHost, e->stream));
+  {
+    const int rc = nq_any_sync(e);
+    if (rc) return rc;
+  }
+  double lo = host[0], hi = host[1];
+  for (int k = 1; k < grid; ++k) {
+    const double a = host[(size_t)4 * k], b = host[(size_t)4 * k + 1];
+    lo = (lo != lo || lo < a) ? lo : a;
+    hi = (hi != hi || hi > b) ? hi : b;
+  }
+  out2[0] = lo;
+  out2[1] = hi;
+  return 0;
 }
 int nq_any_set_elem(nq_any* e, void* plane, long long index, double re, double im) {
   if (!e || !plane || index < 0) return -1;
