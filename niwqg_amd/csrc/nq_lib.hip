@@ -337,14 +337,15 @@ __global__ void k_spec_mul(const cd* __restrict__ in, cd* __restrict__ out, int 
   out[idx] = o;
 }
 
-// out = a on the self-mirrored columns, (a + b)/2 on the interior columns (dual-copy q-hat -> Hermitian part)
+// out = a on the self-mirrored columns, (a + b)/2 on the interior columns (dual-copy q-hat -> Hermitian part); the planes are
+// column slabs whose first column is global column k0 (0 on one rank)
 __global__ void k_avg_interior(const cd* __restrict__ a, const cd* __restrict__ b, cd* __restrict__ out, int width,
-                               int pitch, int N) {
+                               int pitch, int N, int k0) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x, l = blockIdx.y;
   if (k >= width) return;
   const size_t idx = (size_t)l * pitch + k;
   cd v = a[idx];
-  if (k > 0 && k < N / 2) {
+  if (k0 + k > 0 && k0 + k < N / 2) {
     const cd w = b[idx];
     v = cmake(0.5 * (v.x + w.x), 0.5 * (v.y + w.y));
   }
@@ -391,20 +392,6 @@ __global__ void k_expand_half(const cd* __restrict__ f1, const cd* __restrict__ 
     a = cmake(-(kx * a.y + ly * b.y), kx * a.x + ly * b.x);
   }
   out[(size_t)l * wout + k] = a;
-}
-
-// the same on a column slab whose first column is global column k0
-__global__ void k_avg_interior_g(const cd* __restrict__ a, const cd* __restrict__ b, cd* __restrict__ out, int width,
-                                 int pitch, int N, int k0) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x, l = blockIdx.y;
-  if (k >= width) return;
-  const size_t idx = (size_t)l * pitch + k;
-  cd v = a[idx];
-  if (k0 + k > 0 && k0 + k < N / 2) {
-    const cd w = b[idx];
-    v = cmake(0.5 * (v.x + w.x), 0.5 * (v.y + w.y));
-  }
-  out[idx] = v;
 }
 
 // reductions: sum over a real/complex plane of a pointwise expression; result in out[0..] via atomics
@@ -1893,6 +1880,7 @@ static double* red_ptr(nq_ctx* c, int which, int* n) {
   }
 }
 static int slab_allreduce(std::vector<nq_ctx*>& grp, int which) {
+  if (grp.size() == 1 && grp[0]->P == 1) return 0;      // one rank: its sums are the sums (as exchange_now)
   nq_ctx* c0 = grp[0];
   int n = 0;
   if (!red_ptr(c0, which, &n)) NQ_FAIL(c0, -1, "slab_allreduce: which = %d", which);
@@ -2088,6 +2076,41 @@ static void launch_project(nq_ctx* c, double* part) {
 #define CALL_(s, clx) launch_project_s<s, clx>(c, part)
   NQ_S1_SWITCH(c, CALL_)
 #undef CALL_
+}
+// the passive scalar's Gamma_c projection: B-fft of Muc, Mvc against c-hat; one partial per workgroup, their count returned
+static int launch_project_c(nq_ctx* x, const cd* ch, double* part) {
+  const YGeom g = geom_half(x);
+  if (g.width <= 0) return 0;
+#define CALL_(sz, clx) hipLaunchKernelGGL((k_s_project_c<sz, clx>), dim3((g.width + clx - 1) / clx, x->S2), dim3((YPlanT<sz, clx>::THREADS)), (YPlanT<sz, clx>::LDS_BYTES), x->stream, x->mUc, x->mVc, ch, g, x->kk, x->ll, x->tw, 1, part)
+  NQ_S1_SWITCH(x, CALL_)
+#undef CALL_
+  return ((g.width + x->CLy - 1) / x->CLy) * x->S2;
+}
+// the tick's two products passes: which = 0 leaves J = u phix + v phiy in Mw (c_J = 1, c_R = 0), which = 1 i phi q_psi (0, 1)
+static void launch_products_pass(nq_ctx* x, int which) { launch_products(x, which == 0 ? 1.0 : 0.0, which == 0 ? 0.0 : 1.0); }
+// Physical space sees the mean of the two copies of q-hat: formed in a scratch plane (scr_f1 on one rank, where scr_h1 is a
+// plane of the transfer; a lazily allocated scr_h1 on a slab rank) that *qh then names.  One copy: *qh is left alone.
+static int mean_qh(nq_ctx* x, const cd** qh) {
+  if (!x->dual) return 0;
+  if (x->P > 1 && !x->scr_h1) ALLOC(x, x->scr_h1, (size_t)x->N * x->Ph);
+  cd* mean = x->P > 1 ? x->scr_h1 : x->scr_f1;
+  if (x->Wh > 0) hipLaunchKernelGGL(k_avg_interior, dim3((x->Wh + 63) / 64, x->N), dim3(64), 0, x->stream, *qh, (const cd*)x->q2.y[x->q2.cur], mean, x->Wh, x->Ph, x->N, x->kh0);
+  *qh = mean;
+  return 0;
+}
+// out <- the sum, in rank order on the host, of the `count` doubles every context of the group holds at x->*sums: the first
+// rank's are copied (a -0.0 shell sum of a single rank stays -0.0), the others added
+static int sum_ranks_on_host(std::vector<nq_ctx*>& grp, double* nq_ctx::*sums, size_t count, double* out) {
+  std::vector<double> part(grp.size() > 1 ? count : 0);
+  for (nq_ctx* x : each(grp)) {
+    double* dst = x == grp[0] ? out : part.data();
+    HIPCHK(x, hipGetLastError());
+    HIPCHK(x, hipMemcpyAsync(dst, x->*sums, sizeof(double) * count, hipMemcpyDeviceToHost, x->stream));
+    SLABTRY(nq_sync(x));
+    if (dst != out)
+      for (size_t i = 0; i < count; ++i) out[i] += part[i];
+  }
+  return 0;
 }
 template <int S, int CLX>
 static void launch_project_bin_s(nq_ctx* c, double* rlap, double* rdiss) {
@@ -3562,121 +3585,6 @@ int nq_slab_get_rows(nq_ctx* c, int id, double* out) {
   return nq_sync(c);
 }
 
-// Diagnostics tick of a slab-decomposed simulation: the 32 sums of nq_diagnostics, every rank's part summed over the ranks
-// (two all-reduces: the spectral half gives the two means the physical half is centred with).  Collective.
-int nq_slab_diagnostics(nq_ctx* c, double* out) {
-  if (!c || !out) return -1;
-  std::vector<nq_ctx*> grp;
-  SLABTRY(slab_group(c, &grp));
-  SLABTRY(slab_settle(grp));
-  nq_ctx* c0 = grp[0];
-  const int N = c0->N, NB = 1024;
-  const double M = (double)N * N;
-  const bool waves = c0->kernel_family, coupled = c0->p.model == NQ_MODEL_COUPLED;
-  for (nq_ctx* x : each(grp)) {
-    HIPCHK(x, hipSetDevice(x->device));
-    const int nxb = xdiag_blocks(x), nww = (x->Wf / x->CLy) * x->S2;
-    if (!x->diag_part) {
-      size_t need = (size_t)NB * 9;
-      if ((size_t)nxb * 8 > need) need = (size_t)nxb * 8;
-      if ((size_t)nww * 4 > need) need = (size_t)nww * 4;
-      ALLOC(x, x->diag_part, need);
-      ALLOC(x, x->diag_out, (size_t)40);
-    }
-    double* d = x->diag_out;
-    HIPCHK(x, hipMemsetAsync(d, 0, sizeof(double) * 40, x->stream));
-    const cd* qh = x->q.y[x->q.cur];
-    if (x->dual) {                                  // physical space sees the mean of the two copies
-      if (!x->scr_h1) ALLOC(x, x->scr_h1, (size_t)N * x->Ph);
-      if (x->Wh > 0) hipLaunchKernelGGL(k_avg_interior_g, dim3((x->Wh + 63) / 64, N), dim3(64), 0, x->stream, qh, (const cd*)x->q2.y[x->q2.cur], x->scr_h1, x->Wh, x->Ph, N, x->kh0);
-      qh = x->scr_h1;
-    }
-    if (waves) {
-      const cd* phih = x->w.y[x->w.cur];
-      hipLaunchKernelGGL(k_diag_phi, dim3(NB), dim3(256), 0, x->stream, phih, N, x->Wf, x->Wf, x->kf0, x->kk, x->ll, x->diag_part);
-      hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, x->stream, x->diag_part, NB, 4, 4, d);
-      if (x->kf0 == 0) HIPCHK(x, hipMemcpyAsync(d + 4, phih, sizeof(cd), hipMemcpyDeviceToDevice, x->stream));
-    }
-    if (x->Wh > 0) {
-      hipLaunchKernelGGL(k_diag_q, dim3(NB), dim3(256), 0, x->stream, qh, (const cd*)(coupled ? x->qwh : nullptr), (const cd*)x->ph, N, x->Wh, x->Ph, x->kh0, x->kk, x->ll, x->diag_part,
-                         (const cd*)(x->dual ? x->q.y[x->q.cur] : nullptr), (const cd*)(x->dual ? x->q2.y[x->q2.cur] : nullptr),
-                         (const double*)(x->dual ? x->filt_h : nullptr), (const double*)(x->dual ? x->filt_m : nullptr),
-                         (const cd*)(x->pass ? x->qp.y[x->qp.cur] : nullptr));
-      hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, x->stream, x->diag_part, NB, 9, 9, d + 6);
-    }
-    if (x->kh0 == 0) {                              // [15] <- Re(qh - qwh)[0,0] (the owner of column 0 contributes it)
-      HIPCHK(x, hipMemcpyAsync(d + 15, qh, sizeof(double), hipMemcpyDeviceToDevice, x->stream));
-      if (coupled) {
-        HIPCHK(x, hipMemcpyAsync(d + 32, x->qwh, sizeof(double), hipMemcpyDeviceToDevice, x->stream));
-        hipLaunchKernelGGL(k_axpy1, dim3(1), dim3(1), 0, x->stream, d + 15, d + 32, -1.0);
-      }
-    }
-  }
-  SLABTRY(slab_allreduce(grp, 4));
-  double h[16];
-  HIPCHK(c0, hipSetDevice(c0->device));
-  HIPCHK(c0, hipMemcpyAsync(h, c0->diag_out, sizeof(double) * 16, hipMemcpyDeviceToHost, c0->stream));
-  SLABTRY(nq_sync(c0));
-  for (int i = 0; i < 15; ++i) out[i] = h[i];
-  for (int i = 15; i < 32; ++i) out[i] = 0.0;
-  const double qbar = h[15] / M, abar = h[0] / (M * M);
-  out[15] = qbar;
-  if (!waves && c0->passive) {
-    // as in nq_diagnostics: [16..19] the |c-hat|^2 sums, [20] the Gamma_c projection with the u, v of the fourth stage
-    for (nq_ctx* x : each(grp)) {
-      const cd* ch = x->cq.y[x->cq.cur];
-      if (x->Wh > 0) {
-        hipLaunchKernelGGL(k_diag_c, dim3(NB), dim3(256), 0, x->stream, ch, N, x->Wh, x->Ph, x->kh0, x->kk, x->ll, x->diag_part);
-        hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, x->stream, x->diag_part, NB, 4, 4, x->diag_out + 16);
-      }
-      const cd* qh4 = x->stepped ? x->q.y[(x->q.cur + 2) % 3] : x->q.y[x->q.cur];
-      phase_invert_y(x, qh4, false, x->part0Q, nullptr, ch);
-    }
-    SLABTRY(exchange_now(grp, 3, false));
-    for (nq_ctx* x : each(grp)) launch_products(x);
-    SLABTRY(exchange_now(grp, 0, true));
-    for (nq_ctx* x : each(grp)) {
-      launch_A_m(x, false, {&x->mUc, &x->mVc});
-      const YGeom g = geom_half(x);
-      if (g.width <= 0) continue;
-      const int nwc = ((g.width + x->CLy - 1) / x->CLy) * x->S2;
-#define CALL_(sz, clx) hipLaunchKernelGGL((k_s_project_c<sz, clx>), dim3((g.width + clx - 1) / clx, x->S2), dim3((YPlanT<sz, clx>::THREADS)), (YPlanT<sz, clx>::LDS_BYTES), x->stream, x->mUc, x->mVc, x->cq.y[x->cq.cur], g, x->kk, x->ll, x->tw, 1, x->diag_part)
-      NQ_S1_SWITCH(x, CALL_)
-#undef CALL_
-      hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, x->stream, x->diag_part, nwc, 1, 1, x->diag_out + 20);
-    }
-    for (nq_ctx* x : each(grp))                           // the mixed-space rows of the CURRENT state again, for the next step
-      phase_invert_y(x, x->q.y[x->q.cur], true, x->part0Q, nullptr, x->cq.y[x->cq.cur]);
-    SLABTRY(exchange_now(grp, 3, false));
-    SLABTRY(slab_allreduce(grp, 5));
-    HIPCHK(c0, hipSetDevice(c0->device));
-    HIPCHK(c0, hipMemcpyAsync(out + 16, c0->diag_out + 16, sizeof(double) * 5, hipMemcpyDeviceToHost, c0->stream));
-    SLABTRY(slab_settle(grp));
-    for (nq_ctx* x : each(grp)) SLABTRY(nq_sync(x));
-    return 0;
-  }
-  if (!waves) return 0;
-  for (nq_ctx* x : each(grp)) {
-    if (coupled) launch_xdiag_m<MODE_COUPLED>(x, qbar, abar, x->diag_part);
-    else launch_xdiag_m<MODE_UNCOUPLED>(x, qbar, abar, x->diag_part);
-    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, x->stream, x->diag_part, xdiag_blocks(x), 8, 8, x->diag_out + 16);
-  }
-  for (int which = 0; which < 2; ++which) {
-    for (nq_ctx* x : each(grp)) launch_products(x, which == 0 ? 1.0 : 0.0, which == 0 ? 0.0 : 1.0);
-    SLABTRY(exchange_now(grp, 0, true));
-    for (nq_ctx* x : each(grp)) {
-      const int nww = (x->Wf / x->CLy) * x->S2;
-      launch_A_m(x, false, {&x->mW});
-      launch_project(x, x->diag_part);
-      hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, x->stream, x->diag_part, nww, 4, 4, x->diag_out + 24 + 4 * which);
-    }
-  }
-  SLABTRY(slab_allreduce(grp, 5));
-  HIPCHK(c0, hipSetDevice(c0->device));
-  HIPCHK(c0, hipMemcpyAsync(out + 16, c0->diag_out + 16, sizeof(double) * 16, hipMemcpyDeviceToHost, c0->stream));
-  for (nq_ctx* x : each(grp)) SLABTRY(nq_sync(x));
-  return 0;
-}
 // Spectra the whole-plane calls of the class API need on a slab model (fft seam, the three Jacobians): the row kernel of
 // the current state (or the rows uploaded by nq_slab_put_rows), exchange, column transform into a scratch column slab.
 //   what 0 / 1: F[u q] / F[v q]                 half-spectrum slab (Kernel.py:471-486, QGModel.py:469-481)
@@ -3819,10 +3727,7 @@ int nq_snapshot_begin(nq_ctx* c, int with_phi) {
     if (!c->snap_hphi) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->snap_hphi), sizeof(cd) * full, hipHostMallocDefault));
   }
   const cd* qh = c->q.y[c->q.cur];
-  if (c->dual) {
-    hipLaunchKernelGGL(k_avg_interior, dim3((c->Wh + 63) / 64, c->N), dim3(64), 0, c->stream, qh, (const cd*)c->q2.y[c->q2.cur], c->scr_f1, c->Wh, c->Ph, c->N);
-    qh = c->scr_f1;
-  }
+  SLABTRY(mean_qh(c, &qh));
   inv2d_half(c, qh, c->snap_q, c->scr_h0);
   if (with_phi) launch_x_c2c(c, true, c->mPhi.xs, c->snap_phi, c->mPhi.pitch, c->N, 1.0);
   HIPCHK(c, hipEventRecord(c->ev_snap, c->stream));
@@ -3967,17 +3872,11 @@ int nq_get_field(nq_ctx* c, int id, double* host) {
       if (c->p.model != NQ_MODEL_COUPLED) NQ_FAIL(c, -4, "qwh exists only in the coupled model");
       return get_half_spec(c, c->qwh, host);
     case NQ_F_Q:
-      if (c->dual) {
-        hipLaunchKernelGGL(k_avg_interior, dim3((c->Wh + 63) / 64, c->N), dim3(64), 0, c->stream, qh, (const cd*)c->q2.y[c->q2.cur], c->scr_f1, c->Wh, c->Ph, c->N);
-        return get_real_from_half(c, c->scr_f1, 0, host);
-      }
+      SLABTRY(mean_qh(c, &qh));
       return get_real_from_half(c, qh, 0, host);
     case NQ_F_QPSI: {
       const cd* src = qh;
-      if (c->dual) {
-        hipLaunchKernelGGL(k_avg_interior, dim3((c->Wh + 63) / 64, c->N), dim3(64), 0, c->stream, qh, (const cd*)c->q2.y[c->q2.cur], c->scr_f1, c->Wh, c->Ph, c->N);
-        src = c->scr_f1;
-      }
+      SLABTRY(mean_qh(c, &src));
       if (c->p.model == NQ_MODEL_COUPLED && !c->ybj) {
         hipLaunchKernelGGL(k_sub_half, dim3((c->Wh + 63) / 64, c->N), dim3(64), 0, c->stream, src, (const cd*)c->qwh, c->scr_f1, c->Wh, c->Ph);
         src = c->scr_f1;
@@ -4258,90 +4157,137 @@ int nq_jacobian_psi_phi(nq_ctx* c, double* out_cplx) {
   return nq_sync(c);
 }
 // ---- diagnostics tick on the device (ref Diagnostics.py:41-58, Kernel.py:613-706, :718-868, CoupledModel.py:99-136) --
-int nq_diagnostics(nq_ctx* c, double* out) {
-  NQ_SINGLE_RANK(c, "nq_diagnostics");
-  if (!out) NQ_FAIL(c, -1, "nq_diagnostics: null output");
-  HIPCHK(c, hipSetDevice(c->device));
-  const int N = c->N, NB = 1024;
+// One body per tick call (this one, tick_binned and tick_transfer below), written for a group of contexts: a slab entry
+// hands over slab_group's contexts, a single-rank entry a group of just its own.  For that group of one exchange_now and
+// slab_allreduce return at once and slab_settle finds nothing pending, so a plain context gets no exchange stream and its
+// link stays LINK_NONE.  fn: the public function that was called, for the messages.
+static int tick_need_phi(std::vector<nq_ctx*>& grp, const char* fn) {
+  for (nq_ctx* x : grp)
+    if (x->kernel_family && !x->have_phi) NQ_FAIL(x, -4, "%s: set_phi has not been called", fn);
+  return 0;
+}
+// the 32 sums of include/niwqg_amd.h, every rank's part summed over the ranks (two all-reduces: the spectral half gives the
+// two means the physical half is centred with)
+static int tick_scalar(std::vector<nq_ctx*>& grp, double* out) {
+  SLABTRY(slab_settle(grp));
+  nq_ctx* c0 = grp[0];
+  const int N = c0->N, NB = 1024;
   const double M = (double)N * N;
-  const bool waves = c->kernel_family;
-  if (waves && !c->have_phi) NQ_FAIL(c, -4, "nq_diagnostics: set_phi has not been called");
-  const int nxb = xdiag_blocks(c), nww = (c->Wf / c->CLy) * c->S2;
-  if (!c->diag_part) {
-    size_t need = (size_t)NB * 9;
-    if ((size_t)nxb * 8 > need) need = (size_t)nxb * 8;
-    if ((size_t)nww * 4 > need) need = (size_t)nww * 4;
-    ALLOC(c, c->diag_part, need);
-    ALLOC(c, c->diag_out, (size_t)40);
-  }
-  double* d = c->diag_out;
-  HIPCHK(c, hipMemsetAsync(d, 0, sizeof(double) * 32, c->stream));
-  const cd* qh = c->q.y[c->q.cur];
-  if (c->dual) {                                      // physical space sees the mean of the two copies
-    hipLaunchKernelGGL(k_avg_interior, dim3((c->Wh + 63) / 64, N), dim3(64), 0, c->stream, qh, (const cd*)c->q2.y[c->q2.cur], c->scr_f1, c->Wh, c->Ph, N);
-    qh = c->scr_f1;
-  }
-  const cd* phih = waves ? c->w.y[c->w.cur] : nullptr;
+  const bool waves = c0->kernel_family, coupled = c0->p.model == NQ_MODEL_COUPLED;
   // spectral sums: [0,4) S0..S3, [4,6) phih[0,0], [6,15) the nine half-spectrum sums, [15] Re(qh - qwh)[0,0]
-  if (waves) {
-    hipLaunchKernelGGL(k_diag_phi, dim3(NB), dim3(256), 0, c->stream, phih, N, c->Wf, c->Wf, c->kf0, c->kk, c->ll, c->diag_part);
-    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, c->stream, c->diag_part, NB, 4, 4, d);
-    HIPCHK(c, hipMemcpyAsync(d + 4, phih, sizeof(cd), hipMemcpyDeviceToDevice, c->stream));
+  for (nq_ctx* x : each(grp)) {
+    const int nxb = xdiag_blocks(x), nww = (x->Wf / x->CLy) * x->S2;
+    if (!x->diag_part) {
+      size_t need = (size_t)NB * 9;
+      if ((size_t)nxb * 8 > need) need = (size_t)nxb * 8;
+      if ((size_t)nww * 4 > need) need = (size_t)nww * 4;
+      ALLOC(x, x->diag_part, need);
+      ALLOC(x, x->diag_out, (size_t)40);
+    }
+    double* d = x->diag_out;
+    HIPCHK(x, hipMemsetAsync(d, 0, sizeof(double) * 40, x->stream));
+    const cd* qh = x->q.y[x->q.cur];
+    SLABTRY(mean_qh(x, &qh));
+    if (waves) {
+      const cd* phih = x->w.y[x->w.cur];
+      hipLaunchKernelGGL(k_diag_phi, dim3(NB), dim3(256), 0, x->stream, phih, N, x->Wf, x->Wf, x->kf0, x->kk, x->ll, x->diag_part);
+      hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, x->stream, x->diag_part, NB, 4, 4, d);
+      if (x->kf0 == 0) HIPCHK(x, hipMemcpyAsync(d + 4, phih, sizeof(cd), hipMemcpyDeviceToDevice, x->stream));
+    }
+    if (x->Wh > 0) {
+      hipLaunchKernelGGL(k_diag_q, dim3(NB), dim3(256), 0, x->stream, qh, (const cd*)(coupled ? x->qwh : nullptr), (const cd*)x->ph, N, x->Wh, x->Ph, x->kh0, x->kk, x->ll, x->diag_part,
+                         (const cd*)(x->dual ? x->q.y[x->q.cur] : nullptr), (const cd*)(x->dual ? x->q2.y[x->q2.cur] : nullptr),
+                         (const double*)(x->dual ? x->filt_h : nullptr), (const double*)(x->dual ? x->filt_m : nullptr),
+                         (const cd*)(x->pass ? x->qp.y[x->qp.cur] : nullptr));
+      hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, x->stream, x->diag_part, NB, 9, 9, d + 6);
+    }
+    if (x->kh0 == 0) {                              // [15] <- Re(qh - qwh)[0,0] (the owner of column 0 contributes it)
+      HIPCHK(x, hipMemcpyAsync(d + 15, qh, sizeof(double), hipMemcpyDeviceToDevice, x->stream));
+      if (coupled) {
+        HIPCHK(x, hipMemcpyAsync(d + 32, x->qwh, sizeof(double), hipMemcpyDeviceToDevice, x->stream));
+        hipLaunchKernelGGL(k_axpy1, dim3(1), dim3(1), 0, x->stream, d + 15, d + 32, -1.0);
+      }
+    }
   }
-  hipLaunchKernelGGL(k_diag_q, dim3(NB), dim3(256), 0, c->stream, qh, (const cd*)(c->p.model == NQ_MODEL_COUPLED ? c->qwh : nullptr), (const cd*)c->ph, N, c->Wh, c->Ph, 0, c->kk, c->ll, c->diag_part,
-                     (const cd*)(c->dual ? c->q.y[c->q.cur] : nullptr), (const cd*)(c->dual ? c->q2.y[c->q2.cur] : nullptr),
-                     (const double*)(c->dual ? c->filt_h : nullptr), (const double*)(c->dual ? c->filt_m : nullptr),
-                     (const cd*)(c->pass ? c->qp.y[c->qp.cur] : nullptr));
-  hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, c->stream, c->diag_part, NB, 9, 9, d + 6);
-  double h[32];
-  HIPCHK(c, hipMemcpyAsync(h, d, sizeof(double) * 32, hipMemcpyDeviceToHost, c->stream));
-  cd q00 = make_double2(0.0, 0.0), w00 = make_double2(0.0, 0.0);
-  HIPCHK(c, hipMemcpyAsync(&q00, qh, sizeof(cd), hipMemcpyDeviceToHost, c->stream));
-  if (c->p.model == NQ_MODEL_COUPLED) HIPCHK(c, hipMemcpyAsync(&w00, c->qwh, sizeof(cd), hipMemcpyDeviceToHost, c->stream));
-  {
-    const int rc = nq_sync(c);
-    if (rc) return rc;
-  }
+  SLABTRY(slab_allreduce(grp, 4));
+  double h[16];
+  HIPCHK(c0, hipSetDevice(c0->device));
+  HIPCHK(c0, hipMemcpyAsync(h, c0->diag_out, sizeof(double) * 16, hipMemcpyDeviceToHost, c0->stream));
+  SLABTRY(nq_sync(c0));
   for (int i = 0; i < 15; ++i) out[i] = h[i];
   for (int i = 15; i < 32; ++i) out[i] = 0.0;
-  const double qbar = (q00.x - w00.x) / M, abar = h[0] / (M * M);
+  const double qbar = h[15] / M, abar = h[0] / (M * M);
   out[15] = qbar;
-  if (!waves && c->passive) {
+  if (!waves && c0->passive) {
     // QGModel's passive scalar (ref QGModel.py:724-737, :595-604): [16..19] the four |c-hat|^2 sums, [20] the Gamma_c projection
-    const cd* ch = c->cq.y[c->cq.cur];
-    hipLaunchKernelGGL(k_diag_c, dim3(NB), dim3(256), 0, c->stream, ch, N, c->Wh, c->Ph, 0, c->kk, c->ll, c->diag_part);
-    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, c->stream, c->diag_part, NB, 4, 4, d + 16);
-    // jacobian_psi_c with the u, v the reference still holds at a tick: those of the state at which the last step evaluated
-    // its fourth stage (QGModel.py:375 vs :396); before any step, those of the current state
-    const cd* qh4 = c->stepped ? c->q.y[(c->q.cur + 2) % 3] : c->q.y[c->q.cur];
-    phase_invert_y(c, qh4, false, c->part0Q, nullptr, ch);
-    launch_products(c);
-    launch_A_m(c, false, {&c->mUc, &c->mVc});
-    const YGeom g = geom_half(c);
-    const int nwc = ((g.width + c->CLy - 1) / c->CLy) * c->S2;
-#define CALL_(sz, clx) hipLaunchKernelGGL((k_s_project_c<sz, clx>), dim3((g.width + clx - 1) / clx, c->S2), dim3((YPlanT<sz, clx>::THREADS)), (YPlanT<sz, clx>::LDS_BYTES), c->stream, c->mUc, c->mVc, ch, g, c->kk, c->ll, c->tw, 1, c->diag_part)
-    NQ_S1_SWITCH(c, CALL_)
-#undef CALL_
-    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, c->stream, c->diag_part, nwc, 1, 1, d + 20);
-    do_invert_now(c);                                 // the mixed-space rows of the CURRENT state again, for the next step
-    HIPCHK(c, hipMemcpyAsync(out + 16, d + 16, sizeof(double) * 5, hipMemcpyDeviceToHost, c->stream));
-    return nq_sync(c);
+    for (nq_ctx* x : each(grp)) {
+      const cd* ch = x->cq.y[x->cq.cur];
+      if (x->Wh > 0) {
+        hipLaunchKernelGGL(k_diag_c, dim3(NB), dim3(256), 0, x->stream, ch, N, x->Wh, x->Ph, x->kh0, x->kk, x->ll, x->diag_part);
+        hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, x->stream, x->diag_part, NB, 4, 4, x->diag_out + 16);
+      }
+      // jacobian_psi_c with the u, v the reference still holds at a tick: those of the state at which the last step evaluated
+      // its fourth stage (QGModel.py:375 vs :396); before any step, those of the current state
+      const cd* qh4 = x->stepped ? x->q.y[(x->q.cur + 2) % 3] : x->q.y[x->q.cur];
+      phase_invert_y(x, qh4, false, x->part0Q, nullptr, ch);
+    }
+    SLABTRY(exchange_now(grp, 3, false));
+    for (nq_ctx* x : each(grp)) launch_products(x);
+    SLABTRY(exchange_now(grp, 0, true));
+    for (nq_ctx* x : each(grp)) {
+      launch_A_m(x, false, {&x->mUc, &x->mVc});
+      const int nwc = launch_project_c(x, x->cq.y[x->cq.cur], x->diag_part);
+      if (nwc > 0) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, x->stream, x->diag_part, nwc, 1, 1, x->diag_out + 20);
+    }
+    for (nq_ctx* x : each(grp))                           // the mixed-space rows of the CURRENT state again, for the next step
+      phase_invert_y(x, x->q.y[x->q.cur], true, x->part0Q, nullptr, x->cq.y[x->cq.cur]);
+    SLABTRY(exchange_now(grp, 3, false));
+    SLABTRY(slab_allreduce(grp, 5));
+    HIPCHK(c0, hipSetDevice(c0->device));
+    HIPCHK(c0, hipMemcpyAsync(out + 16, c0->diag_out + 16, sizeof(double) * 5, hipMemcpyDeviceToHost, c0->stream));
+    SLABTRY(slab_settle(grp));
+    for (nq_ctx* x : each(grp)) SLABTRY(nq_sync(x));
+    return 0;
   }
   if (!waves) return 0;
   // physical-space statistics: [16,24)
-  if (c->p.model == NQ_MODEL_COUPLED) launch_xdiag_m<MODE_COUPLED>(c, qbar, abar, c->diag_part);
-  else launch_xdiag_m<MODE_UNCOUPLED>(c, qbar, abar, c->diag_part);
-  hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, c->stream, c->diag_part, nxb, 8, 8, d + 16);
+  for (nq_ctx* x : each(grp)) {
+    if (coupled) launch_xdiag_m<MODE_COUPLED>(x, qbar, abar, x->diag_part);
+    else launch_xdiag_m<MODE_UNCOUPLED>(x, qbar, abar, x->diag_part);
+    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, x->stream, x->diag_part, xdiag_blocks(x), 8, 8, x->diag_out + 16);
+  }
   // projections of F[u phix + v phiy] ([24,28)) and of i F[phi q_psi] ([28,32)) on lap_h and diss_h; u, v, q_psi are
   // those of the last inversion, phix / phiy as last refreshed (UnCoupled: quirk Q1), like ref Kernel.py:680-700
   for (int which = 0; which < 2; ++which) {
-    launch_products(c, which == 0 ? 1.0 : 0.0, which == 0 ? 0.0 : 1.0);
-    launch_A_m(c, false, {&c->mW});
-    launch_project(c, c->diag_part);
-    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, c->stream, c->diag_part, nww, 4, 4, d + 24 + 4 * which);
+    for (nq_ctx* x : each(grp)) launch_products_pass(x, which);
+    SLABTRY(exchange_now(grp, 0, true));
+    for (nq_ctx* x : each(grp)) {
+      const int nww = (x->Wf / x->CLy) * x->S2;
+      launch_A_m(x, false, {&x->mW});
+      launch_project(x, x->diag_part);
+      hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, x->stream, x->diag_part, nww, 4, 4, x->diag_out + 24 + 4 * which);
+    }
   }
-  HIPCHK(c, hipMemcpyAsync(out + 16, d + 16, sizeof(double) * 16, hipMemcpyDeviceToHost, c->stream));
-  return nq_sync(c);
+  SLABTRY(slab_allreduce(grp, 5));
+  HIPCHK(c0, hipSetDevice(c0->device));
+  HIPCHK(c0, hipMemcpyAsync(out + 16, c0->diag_out + 16, sizeof(double) * 16, hipMemcpyDeviceToHost, c0->stream));
+  for (nq_ctx* x : each(grp)) SLABTRY(nq_sync(x));
+  return 0;
+}
+int nq_diagnostics(nq_ctx* c, double* out) {
+  NQ_SINGLE_RANK(c, "nq_diagnostics");
+  if (!out) NQ_FAIL(c, -1, "nq_diagnostics: null output");
+  std::vector<nq_ctx*> grp(1, c);
+  SLABTRY(tick_need_phi(grp, "nq_diagnostics"));
+  return tick_scalar(grp, out);
+}
+// the tick of a slab-decomposed simulation.  Collective.  It runs before set_phi too: a slab model's set_q reads ke_qg from
+// these sums (slab.py: scalar), as Kernel.set_q does before the wave field exists.
+int nq_slab_diagnostics(nq_ctx* c, double* out) {
+  if (!c || !out) return -1;
+  std::vector<nq_ctx*> grp;
+  SLABTRY(slab_group(c, &grp));
+  return tick_scalar(grp, out);
 }
 
 // ---- PDFs and joint PDFs of the physical fields (csrc/nq_hist.hpp) -----------------------------------
@@ -4537,16 +4483,7 @@ static int bin_local_spectral(nq_ctx* x, int nb) {
   double* d = x->spec_out;
   HIPCHK(x, hipMemsetAsync(d, 0, sizeof(double) * 32 * nb, x->stream));
   const cd* qh = x->q.y[x->q.cur];
-  if (x->dual) {                                      // as the tick: the mean of the two copies
-    if (x->P == 1) {
-      hipLaunchKernelGGL(k_avg_interior, dim3((x->Wh + 63) / 64, N), dim3(64), 0, x->stream, qh, (const cd*)x->q2.y[x->q2.cur], x->scr_f1, x->Wh, x->Ph, N);
-      qh = x->scr_f1;
-    } else {
-      if (!x->scr_h1) ALLOC(x, x->scr_h1, (size_t)N * x->Ph);
-      if (x->Wh > 0) hipLaunchKernelGGL(k_avg_interior_g, dim3((x->Wh + 63) / 64, N), dim3(64), 0, x->stream, qh, (const cd*)x->q2.y[x->q2.cur], x->scr_h1, x->Wh, x->Ph, N, x->kh0);
-      qh = x->scr_h1;
-    }
-  }
+  SLABTRY(mean_qh(x, &qh));                           // as the tick
   if (waves && x->Wf > 0) {
     const BinPhi t{(const cd*)x->w.y[x->w.cur], x->Wf, x->kk, x->ll};
     hipLaunchKernelGGL(k_bin_shells<BinPhi>, dim3(nb), dim3(256), 0, x->stream, t, N, nb, 1, x->kf0, x->Wf, d);
@@ -4572,48 +4509,16 @@ static void bin_local_project(nq_ctx* x, int nb, int which) {
   hipLaunchKernelGGL(k_bin_shells<BinProj>, dim3(nb), dim3(256), 0, x->stream, t, x->N, nb, 1, x->kf0, x->Wf, x->spec_out + (size_t)(24 + 4 * which) * nb);
 }
 
-int nq_diagnostics_binned(nq_ctx* c, int nb, double* out) {
-  NQ_SINGLE_RANK(c, "nq_diagnostics_binned");
-  if (!out) NQ_FAIL(c, -1, "nq_diagnostics_binned: null output");
-  if (nb != nq_shell_count(c->N)) NQ_FAIL(c, -1, "nq_diagnostics_binned: nb = %d, the grid has %d shells", nb, nq_shell_count(c->N));
-  HIPCHK(c, hipSetDevice(c->device));
-  const bool waves = c->kernel_family;
-  if (waves && !c->have_phi) NQ_FAIL(c, -4, "nq_diagnostics_binned: set_phi has not been called");
-  {
-    const int rc = bin_local_spectral(c, nb);
-    if (rc) return rc;
-  }
-  if (waves) {
+// every context bins its own columns, the products passes exchange as the tick's do, and the contexts are summed in rank order
+// on the host
+static int tick_binned(std::vector<nq_ctx*>& grp, const char* fn, int nb, double* out) {
+  SLABTRY(tick_need_phi(grp, fn));
+  SLABTRY(slab_settle(grp));
+  for (nq_ctx* x : each(grp)) SLABTRY(bin_local_spectral(x, nb));
+  if (grp[0]->kernel_family) {
     // [24], [27] from F[u phix + v phiy], [28], [31] from i F[phi q_psi]: the tick's two products passes
     for (int which = 0; which < 2; ++which) {
-      launch_products(c, which == 0 ? 1.0 : 0.0, which == 0 ? 0.0 : 1.0);
-      launch_A_m(c, false, {&c->mW});
-      bin_local_project(c, nb, which);
-    }
-  }
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(out, c->spec_out, sizeof(double) * 32 * nb, hipMemcpyDeviceToHost, c->stream));
-  return nq_sync(c);
-}
-
-// the same on a slab-decomposed simulation (collective, like nq_slab_diagnostics): every context of this process bins its own
-// columns, the products passes exchange as the tick's do, and the contexts of this process are summed in rank order on the host
-// (peers: all ranks -- the whole result; one rank per process: that rank's part, which the caller gathers and sums in rank order)
-int nq_slab_diagnostics_binned(nq_ctx* c, int nb, double* out) {
-  if (!c || !out) return -1;
-  if (nb != nq_shell_count(c->N)) NQ_FAIL(c, -1, "nq_slab_diagnostics_binned: nb = %d, the grid has %d shells", nb, nq_shell_count(c->N));
-  std::vector<nq_ctx*> grp;
-  SLABTRY(slab_group(c, &grp));
-  SLABTRY(slab_settle(grp));
-  const bool waves = grp[0]->kernel_family;
-  for (nq_ctx* x : each(grp)) {
-    HIPCHK(x, hipSetDevice(x->device));
-    if (waves && !x->have_phi) NQ_FAIL(x, -4, "nq_slab_diagnostics_binned: set_phi has not been called");
-    SLABTRY(bin_local_spectral(x, nb));
-  }
-  if (waves) {
-    for (int which = 0; which < 2; ++which) {
-      for (nq_ctx* x : each(grp)) launch_products(x, which == 0 ? 1.0 : 0.0, which == 0 ? 0.0 : 1.0);
+      for (nq_ctx* x : each(grp)) launch_products_pass(x, which);
       SLABTRY(exchange_now(grp, 0, true));
       for (nq_ctx* x : each(grp)) {
         launch_A_m(x, false, {&x->mW});
@@ -4621,16 +4526,23 @@ int nq_slab_diagnostics_binned(nq_ctx* c, int nb, double* out) {
       }
     }
   }
-  std::vector<double> part((size_t)32 * nb);
-  for (size_t i = 0; i < part.size(); ++i) out[i] = 0.0;
-  for (nq_ctx* x : grp) {                               // rank order
-    HIPCHK(x, hipSetDevice(x->device));
-    HIPCHK(x, hipGetLastError());
-    HIPCHK(x, hipMemcpyAsync(part.data(), x->spec_out, sizeof(double) * part.size(), hipMemcpyDeviceToHost, x->stream));
-    SLABTRY(nq_sync(x));
-    for (size_t i = 0; i < part.size(); ++i) out[i] += part[i];
-  }
-  return 0;
+  return sum_ranks_on_host(grp, &nq_ctx::spec_out, (size_t)32 * nb, out);
+}
+int nq_diagnostics_binned(nq_ctx* c, int nb, double* out) {
+  NQ_SINGLE_RANK(c, "nq_diagnostics_binned");
+  if (!out) NQ_FAIL(c, -1, "nq_diagnostics_binned: null output");
+  if (nb != nq_shell_count(c->N)) NQ_FAIL(c, -1, "nq_diagnostics_binned: nb = %d, the grid has %d shells", nb, nq_shell_count(c->N));
+  std::vector<nq_ctx*> grp(1, c);
+  return tick_binned(grp, "nq_diagnostics_binned", nb, out);
+}
+// the same on a slab-decomposed simulation (collective, like nq_slab_diagnostics): the contexts of this process are summed
+// (peers: all ranks -- the whole result; one rank per process: that rank's part, which the caller gathers and sums in rank order)
+int nq_slab_diagnostics_binned(nq_ctx* c, int nb, double* out) {
+  if (!c || !out) return -1;
+  if (nb != nq_shell_count(c->N)) NQ_FAIL(c, -1, "nq_slab_diagnostics_binned: nb = %d, the grid has %d shells", nb, nq_shell_count(c->N));
+  std::vector<nq_ctx*> grp;
+  SLABTRY(slab_group(c, &grp));
+  return tick_binned(grp, "nq_slab_diagnostics_binned", nb, out);
 }
 
 // ---- spectral transfer -----------------------------------------------------------------------------
@@ -4658,16 +4570,7 @@ static int transfer_begin(nq_ctx* x, int nb, TrPlanes* t) {
     t->f = x->tr_f;
   }
   t->qh = x->q.y[x->q.cur];
-  if (x->dual && !x->ybj) {                           // the q-hat the tick bins: the mean of the two copies
-    if (x->P == 1) {
-      hipLaunchKernelGGL(k_avg_interior, dim3((x->Wh + 63) / 64, N), dim3(64), 0, x->stream, t->qh, (const cd*)x->q2.y[x->q2.cur], x->scr_f1, x->Wh, x->Ph, N);
-      t->qh = x->scr_f1;
-    } else {
-      if (!x->scr_h1) ALLOC(x, x->scr_h1, (size_t)N * x->Ph);
-      if (x->Wh > 0) hipLaunchKernelGGL(k_avg_interior_g, dim3((x->Wh + 63) / 64, N), dim3(64), 0, x->stream, t->qh, (const cd*)x->q2.y[x->q2.cur], x->scr_h1, x->Wh, x->Ph, N, x->kh0);
-      t->qh = x->scr_h1;
-    }
-  }
+  if (!x->ybj) SLABTRY(mean_qh(x, &t->qh));           // the q-hat the tick bins
   return 0;
 }
 // after the products pass `which` (0: J and the balanced / scalar products, 1: R) and its exchange: A sub-pass, B into the
@@ -4703,61 +4606,41 @@ static void transfer_bin_pass(nq_ctx* x, int nb, int which, const TrPlanes& t) {
   }
 }
 
+static int tick_transfer(std::vector<nq_ctx*>& grp, const char* fn, int nb, double* out) {
+  SLABTRY(tick_need_phi(grp, fn));
+  SLABTRY(slab_settle(grp));
+  std::vector<TrPlanes> t(grp.size());
+  for (size_t r = 0; r < grp.size(); ++r) {
+    HIPCHK(grp[r], hipSetDevice(grp[r]->device));
+    SLABTRY(transfer_begin(grp[r], nb, &t[r]));
+  }
+  for (int which = 0; which < (grp[0]->kernel_family ? 2 : 1); ++which) {
+    for (nq_ctx* x : each(grp)) {
+      set_window(x, 0, 1);
+      launch_products_pass(x, which);
+    }
+    SLABTRY(exchange_now(grp, 0, true));
+    for (size_t r = 0; r < grp.size(); ++r) {
+      HIPCHK(grp[r], hipSetDevice(grp[r]->device));
+      transfer_bin_pass(grp[r], nb, which, t[r]);
+    }
+  }
+  return sum_ranks_on_host(grp, &nq_ctx::tr_out, (size_t)NQ_TRANSFER_ROWS * nb, out);
+}
 int nq_transfer_binned(nq_ctx* c, int nb, double* out) {
   NQ_SINGLE_RANK(c, "nq_transfer_binned");
   if (!out) NQ_FAIL(c, -1, "nq_transfer_binned: null output");
   if (nb != nq_shell_count(c->N)) NQ_FAIL(c, -1, "nq_transfer_binned: nb = %d, the grid has %d shells", nb, nq_shell_count(c->N));
-  HIPCHK(c, hipSetDevice(c->device));
-  const bool waves = c->kernel_family;
-  if (waves && !c->have_phi) NQ_FAIL(c, -4, "nq_transfer_binned: set_phi has not been called");
-  TrPlanes t;
-  SLABTRY(transfer_begin(c, nb, &t));
-  for (int which = 0; which < (waves ? 2 : 1); ++which) {
-    launch_products(c, which == 0 ? 1.0 : 0.0, which == 0 ? 0.0 : 1.0);
-    transfer_bin_pass(c, nb, which, t);
-  }
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(out, c->tr_out, sizeof(double) * NQ_TRANSFER_ROWS * nb, hipMemcpyDeviceToHost, c->stream));
-  return nq_sync(c);
+  std::vector<nq_ctx*> grp(1, c);
+  return tick_transfer(grp, "nq_transfer_binned", nb, out);
 }
-
 // collective, as nq_slab_diagnostics_binned: every context bins its own columns, the contexts of this process summed in rank order
 int nq_slab_transfer_binned(nq_ctx* c, int nb, double* out) {
   if (!c || !out) return -1;
   if (nb != nq_shell_count(c->N)) NQ_FAIL(c, -1, "nq_slab_transfer_binned: nb = %d, the grid has %d shells", nb, nq_shell_count(c->N));
   std::vector<nq_ctx*> grp;
   SLABTRY(slab_group(c, &grp));
-  SLABTRY(slab_settle(grp));
-  const bool waves = grp[0]->kernel_family;
-  std::vector<TrPlanes> t(grp.size());
-  for (size_t r = 0; r < grp.size(); ++r) {
-    nq_ctx* x = grp[r];
-    HIPCHK(x, hipSetDevice(x->device));
-    if (waves && !x->have_phi) NQ_FAIL(x, -4, "nq_slab_transfer_binned: set_phi has not been called");
-    SLABTRY(transfer_begin(x, nb, &t[r]));
-  }
-  for (int which = 0; which < (waves ? 2 : 1); ++which) {
-    for (nq_ctx* x : each(grp)) {
-      set_window(x, 0, 1);
-      launch_products(x, which == 0 ? 1.0 : 0.0, which == 0 ? 0.0 : 1.0);
-    }
-    SLABTRY(exchange_now(grp, 0, true));
-    for (size_t r = 0; r < grp.size(); ++r) {
-      nq_ctx* x = grp[r];
-      HIPCHK(x, hipSetDevice(x->device));
-      transfer_bin_pass(x, nb, which, t[r]);
-    }
-  }
-  std::vector<double> part((size_t)NQ_TRANSFER_ROWS * nb);
-  for (size_t i = 0; i < part.size(); ++i) out[i] = 0.0;
-  for (nq_ctx* x : grp) {                               // rank order
-    HIPCHK(x, hipSetDevice(x->device));
-    HIPCHK(x, hipGetLastError());
-    HIPCHK(x, hipMemcpyAsync(part.data(), x->tr_out, sizeof(double) * part.size(), hipMemcpyDeviceToHost, x->stream));
-    SLABTRY(nq_sync(x));
-    for (size_t i = 0; i < part.size(); ++i) out[i] += part[i];
-  }
-  return 0;
+  return tick_transfer(grp, "nq_slab_transfer_binned", nb, out);
 }
 
 // fft(phi * q_psi), (ny, nx): the refraction source of ref Kernel.py:332, :350, :367, :385 before its -0.5j factor,
