@@ -945,9 +945,6 @@ __global__ void __launch_bounds__(1024) k_budget_small(BudgetAcc b, double* __re
 
 // ---------------------------------------------------------------------------------------------
 // size dispatch
-#define M_SMALL(M) M(64, 8, 8) M(128, 8, 16) M(256, 16, 16) M(512, 16, 32) M(1024, 32, 32) M(2048, 32, 64)
-// sizes whose fused row kernels run one transform per row (8192-point rows: the even/odd kernels, k_x_products_eo / k_x_wavepv_eo)
-#define NQ_FOR_ROW_SIZES(M) M_SMALL(M) M(4096, 64, 64)
 #define NQ_FOR_SIZES(M) M(64, 8, 8) M(128, 8, 16) M(256, 16, 16) M(512, 16, 32) M(1024, 32, 32) M(2048, 32, 64) M(4096, 64, 64) M(8192, 64, 128)
 
 static bool plan_for(int N, int* S1, int* S2) {
@@ -956,6 +953,48 @@ static bool plan_for(int N, int* S1, int* S2) {
 #undef CASE_
   return false;
 }
+// The three visitors below are the only places where a run-time size becomes a template argument: f is a generic lambda
+// that reads the value from its argument's type (constexpr int N = decltype(n)::value).  A site that has kernels for
+// some sizes only says so with `if constexpr` on N inside the lambda: the discarded branch instantiates nothing.
+// false: the size is not in the table and f was not called.
+template <int V>
+struct Int { static constexpr int value = V; };
+// row length: f(Int<n>) for the n of NQ_FOR_SIZES
+template <class F>
+static bool with_row_size(int N, F&& f) {
+  switch (N) {
+#define CASE_(n, a, b) case n: f(Int<n>{}); return true;
+    NQ_FOR_SIZES(CASE_)
+#undef CASE_
+  }
+  return false;
+}
+// y plan: f(Int<S1>, Int<CLy>); S1 = one radix of the two-pass transform (tiles of CL columns) or, with single-pass
+// columns, N itself (tiles of CLS columns for N >= 128)
+template <class F>
+static bool with_col_plan(const nq_ctx* c, F&& f) {
+#define CALL_(s, clx) case s: f(Int<s>{}, Int<clx>{}); return true;
+  if (c->CLy == CL) {
+    switch (c->S1) { CALL_(8, CL) CALL_(16, CL) CALL_(32, CL) CALL_(64, CL) }
+  } else {
+    switch (c->S1) { CALL_(128, CLS) CALL_(256, CLS) CALL_(512, CLS) }
+  }
+#undef CALL_
+  return false;
+}
+// radix of the A sub-pass: f(Int<S2>)
+template <class F>
+static bool with_a_radix(int S2, F&& f) {
+  switch (S2) {
+#define CASE_(s) case s: f(Int<s>{}); return true;
+    CASE_(8) CASE_(16) CASE_(32) CASE_(64) CASE_(128)
+#undef CASE_
+  }
+  return false;
+}
+// grid of a row kernel that takes XPlan::C rows per workgroup, the last one possibly partly filled
+template <class X>
+static dim3 rows_grid(int rows) { return dim3((rows + X::C - 1) / X::C); }
 
 // per-kernel event profiling ---------------------------------------------------------------------
 enum { PK_PRODUCTS = 0, PK_WAVEPV = 1, PK_SQ = 2, PK_SPHI = 3, PK_INVERT = 4, PK_A = 5 };
@@ -984,53 +1023,41 @@ struct ProfScope {
 };
 
 // generic launches -----------------------------------------------------------------------------
-template <int N>
-static void launch_x_c2c_n(nq_ctx* c, bool inv, const cd* in, cd* out, int pin, int pout, int nrows, double scale, int mul_ik) {
-  typedef XPlan<N> X;
-  dim3 grid((nrows + X::C - 1) / X::C), block(X::THREADS);
-  if (inv) hipLaunchKernelGGL((k_x_c2c<N, true>), grid, block, X::LDS_BYTES, c->stream, in, out, pin, pout, nrows, scale, c->tw, c->kk, mul_ik);
-  else hipLaunchKernelGGL((k_x_c2c<N, false>), grid, block, X::LDS_BYTES, c->stream, in, out, pin, pout, nrows, scale, c->tw, c->kk, mul_ik);
-}
 static void launch_x_c2c(nq_ctx* c, bool inv, const cd* in, cd* out, int pin, int pout, double scale, int mul_ik = 0) {
-  switch (c->N) {
-#define CASE_(n, a, b) case n: launch_x_c2c_n<n>(c, inv, in, out, pin, pout, c->N, scale, mul_ik); break;
-    NQ_FOR_SIZES(CASE_)
-#undef CASE_
-  }
+  with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    typedef XPlan<N> X;
+    const dim3 grid = rows_grid<X>(c->N), block(X::THREADS);
+    if (inv) hipLaunchKernelGGL((k_x_c2c<N, true>), grid, block, X::LDS_BYTES, c->stream, in, out, pin, pout, c->N, scale, c->tw, c->kk, mul_ik);
+    else hipLaunchKernelGGL((k_x_c2c<N, false>), grid, block, X::LDS_BYTES, c->stream, in, out, pin, pout, c->N, scale, c->tw, c->kk, mul_ik);
+  });
 }
 static void launch_x_r2c(nq_ctx* c, const double* in, cd* out) {
-  switch (c->N) {
-#define CASE_(n, a, b) case n: { typedef XPlan<n> X; hipLaunchKernelGGL((k_x_r2c<n>), dim3((c->N + X::C - 1) / X::C), dim3(X::THREADS), X::LDS_BYTES, c->stream, in, out, c->N, c->Ph, c->N, c->tw); } break;
-    NQ_FOR_SIZES(CASE_)
-#undef CASE_
-  }
+  with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    typedef XPlan<N> X;
+    hipLaunchKernelGGL((k_x_r2c<N>), rows_grid<X>(c->N), dim3(X::THREADS), X::LDS_BYTES, c->stream, in, out, c->N, c->Ph, c->N, c->tw);
+  });
 }
 static void launch_x_c2r(nq_ctx* c, const cd* in, double* out, double scale) {
-  switch (c->N) {
-#define CASE_(n, a, b) case n: { typedef XPlan<n> X; hipLaunchKernelGGL((k_x_c2r<n>), dim3((c->N + X::C - 1) / X::C), dim3(X::THREADS), X::LDS_BYTES, c->stream, in, out, c->Ph, c->N, c->N, scale, c->tw); } break;
-    NQ_FOR_SIZES(CASE_)
-#undef CASE_
-  }
+  with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    typedef XPlan<N> X;
+    hipLaunchKernelGGL((k_x_c2r<N>), rows_grid<X>(c->N), dim3(X::THREADS), X::LDS_BYTES, c->stream, in, out, c->Ph, c->N, c->N, scale, c->tw);
+  });
 }
 
-template <int S, typename AL>
-static void launch_A_s(nq_ctx* c, bool inv, const AL& al, int n, int maxw) {
-  typedef YPlan<S> Y;
-  dim3 grid((maxw + CL - 1) / CL, c->S1, n), block(Y::THREADS);
-  if (inv) hipLaunchKernelGGL((k_y_A<S, true, AL>), grid, block, Y::LDS_BYTES, c->stream, al, c->S1, c->tw, 1);
-  else hipLaunchKernelGGL((k_y_A<S, false, AL>), grid, block, Y::LDS_BYTES, c->stream, al, c->S1, c->tw, 1);
-}
 template <typename AL>
 static void launch_A_list(nq_ctx* c, bool inv, const AL& al, int n, int maxw) {
   if (c->S2 == 1) return;                  // single-pass columns: the B sub-pass is the whole y transform
   ProfScope ps(c, PK_A);
-  switch (c->S2) {
-    case 8: launch_A_s<8>(c, inv, al, n, maxw); break;
-    case 16: launch_A_s<16>(c, inv, al, n, maxw); break;
-    case 32: launch_A_s<32>(c, inv, al, n, maxw); break;
-    case 64: launch_A_s<64>(c, inv, al, n, maxw); break;
-    case 128: launch_A_s<128>(c, inv, al, n, maxw); break;
-  }
+  with_a_radix(c->S2, [&](auto s2) {
+    constexpr int S = decltype(s2)::value;
+    typedef YPlan<S> Y;
+    const dim3 grid((maxw + CL - 1) / CL, c->S1, n), block(Y::THREADS);
+    if (inv) hipLaunchKernelGGL((k_y_A<S, true, AL>), grid, block, Y::LDS_BYTES, c->stream, al, c->S1, c->tw, 1);
+    else hipLaunchKernelGGL((k_y_A<S, false, AL>), grid, block, Y::LDS_BYTES, c->stream, al, c->S1, c->tw, 1);
+  });
 }
 // A sub-pass on plain arrays (generic path, P == 1): half-spectrum or full-plane geometry
 static void launch_A(nq_ctx* c, bool inv, std::initializer_list<cd*> arrs, bool half) {
@@ -1071,34 +1098,14 @@ static void launch_A_m(nq_ctx* c, bool inv, std::initializer_list<const MArr*> a
   if (c->redir_now) launch_A_list(c, inv, al, n, maxw);                               // (see ArrayListR)
   else launch_A_list(c, inv, static_cast<const ArrayList&>(al), n, maxw);
 }
-template <int S, int CLX = CL>
-static void launch_B_s(nq_ctx* c, bool inv, const cd* in, int pin, cd* out, int pout, int width, double scale) {
-  typedef YPlanT<S, CLX> Y;
-  dim3 grid((width + CLX - 1) / CLX, c->S2), block(Y::THREADS);
-  if (inv) hipLaunchKernelGGL((k_y_B<S, true, CLX>), grid, block, Y::LDS_BYTES, c->stream, in, out, width, pin, pout, c->S2, scale, c->tw, 1);
-  else hipLaunchKernelGGL((k_y_B<S, false, CLX>), grid, block, Y::LDS_BYTES, c->stream, in, out, width, pin, pout, c->S2, scale, c->tw, 1);
-}
-// dispatch on the y plan: S1 = one radix of the two-pass transform (tiles of CL columns) or, with single-pass columns, N
-// itself (tiles of CLS columns for N >= 128)
-#define NQ_S1_SWITCH(c, CALL)                 \
-  if ((c)->CLy == CL) {                       \
-    switch ((c)->S1) {                        \
-      case 8: CALL(8, CL); break;             \
-      case 16: CALL(16, CL); break;           \
-      case 32: CALL(32, CL); break;           \
-      case 64: CALL(64, CL); break;           \
-    }                                         \
-  } else {                                    \
-    switch ((c)->S1) {                        \
-      case 128: CALL(128, CLS); break;        \
-      case 256: CALL(256, CLS); break;        \
-      case 512: CALL(512, CLS); break;        \
-    }                                         \
-  }
 static void launch_B_p(nq_ctx* c, bool inv, const cd* in, int pin, cd* out, int pout, int width, double scale) {
-#define CALL_(s, clx) launch_B_s<s, clx>(c, inv, in, pin, out, pout, width, scale)
-  NQ_S1_SWITCH(c, CALL_)
-#undef CALL_
+  with_col_plan(c, [&](auto s1, auto cly) {
+    constexpr int S = decltype(s1)::value, CLX = decltype(cly)::value;
+    typedef YPlanT<S, CLX> Y;
+    const dim3 grid((width + CLX - 1) / CLX, c->S2), block(Y::THREADS);
+    if (inv) hipLaunchKernelGGL((k_y_B<S, true, CLX>), grid, block, Y::LDS_BYTES, c->stream, in, out, width, pin, pout, c->S2, scale, c->tw, 1);
+    else hipLaunchKernelGGL((k_y_B<S, false, CLX>), grid, block, Y::LDS_BYTES, c->stream, in, out, width, pin, pout, c->S2, scale, c->tw, 1);
+  });
 }
 static void launch_B(nq_ctx* c, bool inv, const cd* in, cd* out, bool half, double scale) {
   const int width = half ? c->Wh : c->N, pitch = half ? c->Ph : c->N;
@@ -1164,27 +1171,25 @@ static MArr rw(const nq_ctx* c, const MArr& m) {
 template <bool SLAB>
 static void launch_wavepv_t(nq_ctx* c) {
   const MArr mPhi = rw(c, c->mPhi), mPhiy = rw(c, c->mPhiy), mA = rw(c, c->mA), mB = rw(c, c->mB);
-  switch (c->N) {
-#define CASE_(n, a, b) case n: { typedef XPlan1<n> X; hipLaunchKernelGGL((k_x_wavepv<n, SLAB>), dim3(c->nrows / X::C), dim3(X::THREADS), X::LDS_BYTES, c->stream, mPhi, mPhiy, mA, mB, c->twx1, c->kk); } break;
-    case 8192:
-      {                                               // even / odd samples as two 4096-point problems (no spills)
-        typedef XPlan<4096> X;
-        const int ncu = (c->stream2 ? c->overlap_grid : c->num_cu) - c->reserve_cus, nb = c->nrows, grid = nb < ncu ? nb : ncu;
-        const size_t ldsb = X::LDS_BYTES + (size_t)4096 * sizeof(cd) ;          // + the 64 KB of thread-private park slots
-        hipLaunchKernelGGL((k_x_wavepv_eo<8192, SLAB>), dim3(grid), dim3(X::THREADS), ldsb, c->stream, mPhi, mPhiy, mA, mB, c->twx_half, c->tw, c->kk, nb);
-      }
-      break;
-    case 4096: {                                      // long rows: two transforms in flight, no spills
+  with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    if constexpr (N == 8192) {                        // even / odd samples as two 4096-point problems (no spills)
+      typedef XPlan<4096> X;
+      const int ncu = (c->stream2 ? c->overlap_grid : c->num_cu) - c->reserve_cus, nb = c->nrows, grid = nb < ncu ? nb : ncu;
+      const size_t ldsb = X::LDS_BYTES + (size_t)4096 * sizeof(cd);           // + the 64 KB of thread-private park slots
+      hipLaunchKernelGGL((k_x_wavepv_eo<8192, SLAB>), dim3(grid), dim3(X::THREADS), ldsb, c->stream, mPhi, mPhiy, mA, mB, c->twx_half, c->tw, c->kk, nb);
+    } else if constexpr (N == 4096) {                 // long rows: two transforms in flight, no spills
       typedef XPlan<4096> X;
       const size_t ldsb = X::LDS_BYTES + X::F::LDS_ELEMS * sizeof(cd);
       int grid = (c->stream2 ? c->overlap_grid : c->num_cu) - c->reserve_cus;      // one persistent workgroup per CU
       const int nb = c->nrows / X::C;
       if (grid > nb) grid = nb;
       hipLaunchKernelGGL((k_x_wavepv2<4096, SLAB>), dim3(grid), dim3(X::THREADS), ldsb, c->stream, mPhi, mPhiy, mA, mB, c->twx, c->kk, nb);
-    } break;
-    M_SMALL(CASE_)
-#undef CASE_
-  }
+    } else {
+      typedef XPlan1<N> X;
+      hipLaunchKernelGGL((k_x_wavepv<N, SLAB>), dim3(c->nrows / X::C), dim3(X::THREADS), X::LDS_BYTES, c->stream, mPhi, mPhiy, mA, mB, c->twx1, c->kk);
+    }
+  });
 }
 // one rank: the row kernels address their rows without the block arithmetic of the slab layout (XRowT<false>)
 static void launch_wavepv(nq_ctx* c) {
@@ -1198,27 +1203,26 @@ static void launch_products_t(nq_ctx* c, double cj, double cr, bool fresh_grad) 
   const MArr mU = rw(c, c->mU), mP = rw(c, c->mP), mQ = rw(c, c->mQ), mQw = rw(c, c->mQw), mPhi = rw(c, c->mPhi);
   const MArr mUq = rw(c, c->mUq), mVq = rw(c, c->mVq), mW = rw(c, c->mW), mPhiy = rw(c, c->mPhiy);
   const MArr mGx = rw(c, c->mGx), mGy = rw(c, c->mGy), mUc = rw(c, c->mUc), mVc = rw(c, c->mVc);
-  if (c->N == 8192 && c->twx_half) {
-    // rows too long for the register budget as one transform: even / odd samples as two 4096-point problems
-    typedef XPlan<4096> X;
-    const MArr& gx8 = (MODE == MODE_QGC) ? mUc : ((MODE == MODE_UNCOUPLED && !fresh_grad) ? mGx : mPhi);
-    const MArr& gy8 = (MODE == MODE_QGC) ? mVc : ((MODE == MODE_UNCOUPLED && !fresh_grad) ? mGy : mPhiy);
-    const int ncu = c->num_cu - c->reserve_cus, nb = c->nrows, grid = nb < ncu ? nb : ncu;
-    const size_t ldsb = X::LDS_BYTES + (size_t)4096 * sizeof(cd) ;            // + the 64 KB of thread-private park slots
-    hipLaunchKernelGGL((k_x_products_eo<8192, MODE, SLAB>), dim3(grid), dim3(X::THREADS), ldsb, c->stream, mU, mP, mQ, mQw, mPhi, gx8, gy8, mUq, mVq, mW, c->twx_half, c->tw, c->kk, vz, cj, cr, nb);
-    return;
-  }
   const MArr& gx = (MODE == MODE_QGC) ? mUc : ((MODE == MODE_UNCOUPLED && !fresh_grad) ? mGx : mPhi);
   const MArr& gy = (MODE == MODE_QGC) ? mVc : ((MODE == MODE_UNCOUPLED && !fresh_grad) ? mGy : mPhiy);
-  switch (c->N) {
-#define CASE_(n, a, b) case n: { typedef XPlan<n> X; const int nb = c->nrows / X::C; \
-    /* one workgroup fits per CU (LDS) and does not spill: persistent; 8192-point rows spill and do better with dynamic dispatch */ \
-    const int ncu = c->num_cu - c->reserve_cus; \
-    const int grid = (X::LDS_BYTES > 80 * 1024 && X::THREADS <= 512 && nb > ncu) ? ncu : nb; \
-    hipLaunchKernelGGL((k_x_products<n, MODE, SLAB>), dim3(grid), dim3(X::THREADS), X::LDS_BYTES, c->stream, mU, mP, mQ, mQw, mPhi, gx, gy, mUq, mVq, mW, c->twx, c->kk, vz, cj, cr, nb); } break;
-    NQ_FOR_ROW_SIZES(CASE_)
-#undef CASE_
-  }
+  const int ncu = c->num_cu - c->reserve_cus;
+  with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    if constexpr (N == 8192) {
+      // rows too long for the register budget as one transform: even / odd samples as two 4096-point problems
+      // (their stage table, c->twx_half, exists on every 8192 context)
+      typedef XPlan<4096> X;
+      const int nb = c->nrows, grid = nb < ncu ? nb : ncu;
+      const size_t ldsb = X::LDS_BYTES + (size_t)4096 * sizeof(cd);             // + the 64 KB of thread-private park slots
+      hipLaunchKernelGGL((k_x_products_eo<8192, MODE, SLAB>), dim3(grid), dim3(X::THREADS), ldsb, c->stream, mU, mP, mQ, mQw, mPhi, gx, gy, mUq, mVq, mW, c->twx_half, c->tw, c->kk, vz, cj, cr, nb);
+    } else {
+      typedef XPlan<N> X;
+      const int nb = c->nrows / X::C;
+      // one workgroup fits per CU (LDS) and does not spill: persistent; 8192-point rows spill and do better with dynamic dispatch
+      const int grid = (X::LDS_BYTES > 80 * 1024 && X::THREADS <= 512 && nb > ncu) ? ncu : nb;
+      hipLaunchKernelGGL((k_x_products<N, MODE, SLAB>), dim3(grid), dim3(X::THREADS), X::LDS_BYTES, c->stream, mU, mP, mQ, mQw, mPhi, gx, gy, mUq, mVq, mW, c->twx, c->kk, vz, cj, cr, nb);
+    }
+  });
 }
 template <int MODE>
 static void launch_products_m(nq_ctx* c, double cj, double cr, bool fresh_grad) {
@@ -1254,9 +1258,11 @@ static EtdArrays etd_arrays(EqState& e, int stage, int* out_slot) {
   return ea;
 }
 
-template <int S, int CLX>
-static void launch_sq_s(nq_ctx* c, const EtdArrays& ea, int stage, const MArr& huq, const MArr& hvq, bool q_equation) {
-  typedef YPlanT<S, CLX> Y;
+// huq, hvq: the products' arrays, when they are not Muq, Mvq (the passive scalar's equation)
+static void launch_sq(nq_ctx* c, const EtdArrays& ea, int stage, const MArr* huq_ = nullptr, const MArr* hvq_ = nullptr) {
+  ProfScope ps(c, PK_SQ);
+  const MArr& huq = huq_ ? *huq_ : c->mUq;
+  const MArr& hvq = hvq_ ? *hvq_ : c->mVq;
   DualQ dq;
   EtdArrays eap = ea;
   memset(&dq, 0, sizeof(dq));
@@ -1274,15 +1280,19 @@ static void launch_sq_s(nq_ctx* c, const EtdArrays& ea, int stage, const MArr& h
   }
   const YGeom g = geom_half(c);
   if (g.width <= 0) return;
-  const dim3 grid((g.width + CLX - 1) / CLX, c->S2), block(Y::THREADS);
   EtdArrays ep;
   memset(&ep, 0, sizeof(ep));
-  if (c->pass && q_equation) {             // the q equation itself, not the passive scalar's
+  if (c->pass && huq_ == nullptr) {        // the q equation itself, not the passive scalar's
     int slot = 0;
     ep = etd_arrays(c->qp, stage, &slot);
   }
-  if (c->dual) hipLaunchKernelGGL((k_s_q<S, true, CLX>), grid, block, Y::LDS_BYTES, c->stream, huq, hvq, eap, stage, g, c->kk, c->ll, c->tw, 1, dq, ep);
-  else hipLaunchKernelGGL((k_s_q<S, false, CLX>), grid, block, Y::LDS_BYTES, c->stream, huq, hvq, eap, stage, g, c->kk, c->ll, c->tw, 1, dq, ep);
+  with_col_plan(c, [&](auto s1, auto cly) {
+    constexpr int S = decltype(s1)::value, CLX = decltype(cly)::value;
+    typedef YPlanT<S, CLX> Y;
+    const dim3 grid((g.width + CLX - 1) / CLX, c->S2), block(Y::THREADS);
+    if (c->dual) hipLaunchKernelGGL((k_s_q<S, true, CLX>), grid, block, Y::LDS_BYTES, c->stream, huq, hvq, eap, stage, g, c->kk, c->ll, c->tw, 1, dq, ep);
+    else hipLaunchKernelGGL((k_s_q<S, false, CLX>), grid, block, Y::LDS_BYTES, c->stream, huq, hvq, eap, stage, g, c->kk, c->ll, c->tw, 1, dq, ep);
+  });
 }
 static BudgetW budget_w(nq_ctx* c, double* part, const cd* y_start) {
   BudgetW bw;
@@ -1293,24 +1303,33 @@ static BudgetW budget_w(nq_ctx* c, double* part, const cd* y_start) {
   bw.muw = c->p.muw;
   return bw;
 }
-template <int S, int CLX>
-static void launch_sphi_s(nq_ctx* c, const EtdArrays& ea, int stage, const cd* y_start, const MArr& ophi, const MArr& ophiy) {
-  typedef YPlanT<S, CLX> Y;
+// ophi, ophiy: where phi and phiy of the stage result go, when not to Mphi, Mphiy (do_step_ybj)
+static void launch_sphi(nq_ctx* c, const EtdArrays& ea, int stage, const cd* y_start, const MArr* ophi_ = nullptr,
+                        const MArr* ophiy_ = nullptr) {
+  ProfScope ps(c, PK_SPHI);
+  const MArr& ophi = ophi_ ? *ophi_ : c->mPhi;
+  const MArr& ophiy = ophiy_ ? *ophiy_ : c->mPhiy;
   BudgetW bw = budget_w(c, c->partW + (size_t)stage * c->nww * NQ_PARTW, y_start);
   const cd* jpass = c->ybj ? nullptr : c->mUq.ys + c->mUq.W;     // YBJModel.jacobian_psi_phi keeps [0,0] (YBJModel.py:123-133)
   const cd* jown = (jpass && c->redir_now) ? c->mUq.xs + c->mUq.W : jpass;     // the own block was not copied across (ArrayListR)
   const int own0 = c->redir_now ? c->rank * c->Nloc : 0, own1 = c->redir_now ? own0 + c->Nloc : 0;
-  hipLaunchKernelGGL((k_s_phi<S, CLX>), dim3(c->Wf / CLX, c->S2), dim3(Y::THREADS), Y::LDS_BYTES, c->stream, c->mW, jpass, jown, own0, own1, c->mUq.pitch, ea, stage, geom_full(c), ophi, ophiy, 1.0 / ((double)c->N * c->N), c->kk, c->ll, c->tw, 1, bw);
+  with_col_plan(c, [&](auto s1, auto cly) {
+    constexpr int S = decltype(s1)::value, CLX = decltype(cly)::value;
+    typedef YPlanT<S, CLX> Y;
+    hipLaunchKernelGGL((k_s_phi<S, CLX>), dim3(c->Wf / CLX, c->S2), dim3(Y::THREADS), Y::LDS_BYTES, c->stream, c->mW, jpass, jown, own0, own1, c->mUq.pitch, ea, stage, geom_full(c), ophi, ophiy, 1.0 / ((double)c->N * c->N), c->kk, c->ll, c->tw, 1, bw);
+  });
 }
-template <int S, int CLX>
-static void launch_emit_phi_s(nq_ctx* c, const cd* phih) {
-  typedef YPlanT<S, CLX> Y;
+static void launch_emit_phi(nq_ctx* c, const cd* phih) {
   BudgetW bw = budget_w(c, c->part0W, phih);
-  hipLaunchKernelGGL((k_s_emit_phi<S, CLX>), dim3(c->Wf / CLX, c->S2), dim3(Y::THREADS), Y::LDS_BYTES, c->stream, phih, geom_full(c), c->mPhi, c->mPhiy, 1.0 / ((double)c->N * c->N), c->kk, c->ll, c->tw, 1, bw);
+  with_col_plan(c, [&](auto s1, auto cly) {
+    constexpr int S = decltype(s1)::value, CLX = decltype(cly)::value;
+    typedef YPlanT<S, CLX> Y;
+    hipLaunchKernelGGL((k_s_emit_phi<S, CLX>), dim3(c->Wf / CLX, c->S2), dim3(Y::THREADS), Y::LDS_BYTES, c->stream, phih, geom_full(c), c->mPhi, c->mPhiy, 1.0 / ((double)c->N * c->N), c->kk, c->ll, c->tw, 1, bw);
+  });
 }
-template <int S, int MODE, int CLX>
-static void launch_invert_sm(nq_ctx* c, const cd* qh, bool store_aux, double* part, const cd* q_bud, const cd* c_hat = nullptr) {
-  typedef YPlanT<S, CLX> Y;
+// c_hat: the passive scalar's spectrum (contexts that have one; nullptr otherwise)
+static void launch_invert(nq_ctx* c, const cd* qh, bool store_aux, double* part, const cd* q_bud, const cd* c_hat = nullptr) {
+  ProfScope ps(c, PK_INVERT);
   // the second copy lives in the same rotating slot as qh
   const cd* qh_minus = nullptr;
   if (c->dual)
@@ -1318,63 +1337,31 @@ static void launch_invert_sm(nq_ctx* c, const cd* qh, bool store_aux, double* pa
       if (c->q.y[i] == qh) qh_minus = c->q2.y[i];
   const YGeom g = geom_half(c);
   if (g.width <= 0) return;
-  hipLaunchKernelGGL((k_s_invert<S, MODE, CLX>), dim3((g.width + CLX - 1) / CLX, c->S2), dim3(Y::THREADS), Y::LDS_BYTES, c->stream, c->mA, c->mB, qh, c->filt_h, c->mU, c->mP, c->mQ, c->mQw, store_aux ? c->qwh : nullptr, store_aux ? c->ph : nullptr, g, 1.0 / ((double)c->N * c->N), c->p.f, c->kk, c->ll, c->tw, 1, c->bud ? part : nullptr, q_bud, qh_minus, c->dual ? c->filt_m : nullptr, c_hat);
+  with_col_plan(c, [&](auto s1, auto cly) {
+    constexpr int S = decltype(s1)::value, CLX = decltype(cly)::value;
+    typedef YPlanT<S, CLX> Y;
+    auto launch = [&](auto mode) {
+      hipLaunchKernelGGL((k_s_invert<S, decltype(mode)::value, CLX>), dim3((g.width + CLX - 1) / CLX, c->S2), dim3(Y::THREADS), Y::LDS_BYTES, c->stream, c->mA, c->mB, qh, c->filt_h, c->mU, c->mP, c->mQ, c->mQw, store_aux ? c->qwh : nullptr, store_aux ? c->ph : nullptr, g, 1.0 / ((double)c->N * c->N), c->p.f, c->kk, c->ll, c->tw, 1, c->bud ? part : nullptr, q_bud, qh_minus, c->dual ? c->filt_m : nullptr, c_hat);
+    };
+    if (c->passive) launch(Int<MODE_QGC>{});
+    else if (c->p.model == NQ_MODEL_COUPLED) launch(Int<MODE_COUPLED>{});
+    else launch(Int<MODE_UNCOUPLED>{});
+  });
 }
 
-static void launch_sq(nq_ctx* c, const EtdArrays& ea, int stage, const MArr* huq = nullptr, const MArr* hvq = nullptr) {
-  ProfScope ps(c, PK_SQ);
-  const MArr& a1 = huq ? *huq : c->mUq;
-  const MArr& a2 = hvq ? *hvq : c->mVq;
-#define CALL_(s, clx) launch_sq_s<s, clx>(c, ea, stage, a1, a2, huq == nullptr)
-  NQ_S1_SWITCH(c, CALL_)
-#undef CALL_
-}
-static void launch_sphi(nq_ctx* c, const EtdArrays& ea, int stage, const cd* y_start, const MArr* ophi = nullptr,
-                        const MArr* ophiy = nullptr) {
-  ProfScope ps(c, PK_SPHI);
-  const MArr& o1 = ophi ? *ophi : c->mPhi;
-  const MArr& o2 = ophiy ? *ophiy : c->mPhiy;
-#define CALL_(s, clx) launch_sphi_s<s, clx>(c, ea, stage, y_start, o1, o2)
-  NQ_S1_SWITCH(c, CALL_)
-#undef CALL_
-}
-static void launch_emit_phi(nq_ctx* c, const cd* phih) {
-#define CALL_(s, clx) launch_emit_phi_s<s, clx>(c, phih)
-  NQ_S1_SWITCH(c, CALL_)
-#undef CALL_
-}
-static void launch_invert(nq_ctx* c, const cd* qh, bool store_aux, double* part, const cd* q_bud, const cd* c_hat = nullptr) {
-  ProfScope ps(c, PK_INVERT);
-  if (c->passive) {
-#define CALL_(s, clx) launch_invert_sm<s, MODE_QGC, clx>(c, qh, store_aux, part, q_bud, c_hat)
-    NQ_S1_SWITCH(c, CALL_)
-#undef CALL_
-  } else if (c->p.model == NQ_MODEL_COUPLED) {
-#define CALL_(s, clx) launch_invert_sm<s, MODE_COUPLED, clx>(c, qh, store_aux, part, q_bud)
-    NQ_S1_SWITCH(c, CALL_)
-#undef CALL_
-  } else {
-#define CALL_(s, clx) launch_invert_sm<s, MODE_UNCOUPLED, clx>(c, qh, store_aux, part, q_bud)
-    NQ_S1_SWITCH(c, CALL_)
-#undef CALL_
-  }
-}
-
-template <int N_, int CW_>
-static void launch_cqg_t(nq_ctx* c, const EtdArrays& ea, int stage, bool store_aux, double* part, const cd* q_bud) {
-  typedef SmallColPlan<N_, CW_> Y;
-  hipLaunchKernelGGL((k_c_qg<N_, CW_>), dim3((c->Wh + CW_ - 1) / CW_), dim3(Y::THREADS), Y::LDS_BYTES, c->stream, c->mUq, c->mVq, ea, stage,
-                     geom_half(c), c->mU, c->mP, c->mQ, store_aux ? c->ph : nullptr, 1.0 / ((double)c->N * c->N), c->kk, c->ll, c->tw,
-                     c->bud ? part : nullptr, q_bud);
-}
 // QGModel, small grid: N_q, the stage update, the inversion and its three inverse y transforms in one launch
 static void launch_cqg(nq_ctx* c, const EtdArrays& ea, int stage, bool store_aux, double* part, const cd* q_bud) {
   ProfScope ps(c, PK_SQ);
-  switch (c->N) {
-    case 128: launch_cqg_t<128, 4>(c, ea, stage, store_aux, part, q_bud); break;
-    case 256: launch_cqg_t<256, 2>(c, ea, stage, store_aux, part, q_bud); break;
-    case 512: launch_cqg_t<512, 2>(c, ea, stage, store_aux, part, q_bud); break;
-  }
+  with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    if constexpr (N == 128 || N == 256 || N == 512) {
+      constexpr int CW = N == 128 ? 4 : 2;           // columns per workgroup
+      typedef SmallColPlan<N, CW> Y;
+      hipLaunchKernelGGL((k_c_qg<N, CW>), dim3((c->Wh + CW - 1) / CW), dim3(Y::THREADS), Y::LDS_BYTES, c->stream, c->mUq, c->mVq, ea, stage,
+                         geom_half(c), c->mU, c->mP, c->mQ, store_aux ? c->ph : nullptr, 1.0 / ((double)c->N * c->N), c->kk, c->ll, c->tw,
+                         c->bud ? part : nullptr, q_bud);
+    }
+  });
 }
 
 static BudgetAcc budget_acc(nq_ctx* c) {
@@ -1469,24 +1456,55 @@ static void do_invert_now(nq_ctx* c) {
     hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, c->stream, c->part0Q, c->nwq, 3, 3, c->carryQ);
 }
 
+// physical rows <-> the x side of a mixed-space array, one row kernel each.  SLAB: this rank's c->Nloc rows in the slab
+// layout; otherwise the c->N rows of a one-rank context.  false: no row plan, nothing launched.
+template <bool SLAB>
+static bool launch_get_real(nq_ctx* c, const MArr& src, double* out, int mode, int zero_nyq) {
+  const int rows = SLAB ? c->Nloc : c->N;
+  return with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    typedef XPlan<N> X;
+    hipLaunchKernelGGL((k_x_get_real<N, SLAB>), rows_grid<X>(rows), dim3(X::THREADS), X::LDS_BYTES, c->stream, src, out, rows, c->tw, c->kk, mode, zero_nyq);
+  });
+}
+static bool launch_get_cplx(nq_ctx* c, const MArr& src, cd* out, int mul_ik) {
+  return with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    typedef XPlan<N> X;
+    hipLaunchKernelGGL((k_x_get_cplx<N, true>), rows_grid<X>(c->Nloc), dim3(X::THREADS), X::LDS_BYTES, c->stream, src, out, c->Nloc, c->tw, c->kk, mul_ik);
+  });
+}
+static bool launch_put_real(nq_ctx* c, const double* in, const MArr& dst) {
+  return with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    typedef XPlan<N> X;
+    hipLaunchKernelGGL((k_x_put_real<N, true>), rows_grid<X>(c->Nloc), dim3(X::THREADS), X::LDS_BYTES, c->stream, in, dst, c->Nloc, c->tw);
+  });
+}
+static bool launch_put_cplx(nq_ctx* c, const cd* in, const MArr& dst) {
+  return with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    typedef XPlan<N> X;
+    hipLaunchKernelGGL((k_x_put_cplx<N, true>), rows_grid<X>(c->Nloc), dim3(X::THREADS), X::LDS_BYTES, c->stream, in, dst, c->Nloc, c->tw);
+  });
+}
+// max |u|, max |v| over this rank's rows of Mu, Mp (x side) into out2[0], out2[1], which the caller has zeroed; scr: Nloc * N doubles
+static bool launch_uv_max(nq_ctx* c, double* scr, double* out2) {
+  const size_t n = (size_t)c->Nloc * c->N;
+  for (int which = 0; which < 2; ++which) {
+    if (!launch_get_real<true>(c, which == 0 ? c->mU : c->mP, scr, which, (which == 1 && c->kernel_family) ? 1 : 0)) return false;
+    hipLaunchKernelGGL(k_reduce_real_max, dim3(1024), dim3(256), 0, c->stream, (const double*)scr, n, out2 + which);
+  }
+  return true;
+}
+
 // max |u|, max |v| over this rank's rows of the fields the LAST inversion emitted (Mu, Mp on the x side): during a step, right
 // after stage index 2, these are the u, v of the reference's fourth jacobian_psi_q call (Kernel.py:364-368, :481-482)
 static int stage4_uv_max(nq_ctx* c) {
   if (!c->uv4) ALLOC(c, c->uv4, (size_t)2);
   if (!c->scr_f0) ALLOC(c, c->scr_f0, (size_t)c->Nloc * c->N);
   HIPCHK(c, hipMemsetAsync(c->uv4, 0, sizeof(double) * 2, c->stream));
-  double* scr = reinterpret_cast<double*>(c->scr_f0);
-  const size_t n = (size_t)c->Nloc * c->N;
-  for (int which = 0; which < 2; ++which) {
-    const MArr& src = which == 0 ? c->mU : c->mP;
-    switch (c->N) {
-#define CASE_(nn, a, b) case nn: { typedef XPlan<nn> X; \
-      hipLaunchKernelGGL((k_x_get_real<nn, true>), dim3((c->Nloc + X::C - 1) / X::C), dim3(X::THREADS), X::LDS_BYTES, c->stream, src, scr, c->Nloc, c->tw, c->kk, which, (which == 1 && c->kernel_family) ? 1 : 0); } break;
-      NQ_FOR_SIZES(CASE_)
-#undef CASE_
-    }
-    hipLaunchKernelGGL(k_reduce_real_max, dim3(1024), dim3(256), 0, c->stream, (const double*)scr, n, c->uv4 + which);
-  }
+  if (!launch_uv_max(c, reinterpret_cast<double*>(c->scr_f0), c->uv4)) NQ_FAIL(c, -2, "no row plan of length %d", c->N);
   c->have_uv4 = true;
   return 0;
 }
@@ -1713,11 +1731,10 @@ static int slab_group(nq_ctx* c, std::vector<nq_ctx*>* g) {
 static int effective_chunks(const nq_ctx* c) {
   if (c->link == LINK_CALLBACK) return 1;
   int rows_per_wg = 1;
-  switch (c->N) {
-#define CASE_(n, a, b) case n: rows_per_wg = XPlan<n>::C > XPlan1<n>::C ? XPlan<n>::C : XPlan1<n>::C; break;
-    NQ_FOR_SIZES(CASE_)
-#undef CASE_
-  }
+  with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    rows_per_wg = XPlan<N>::C > XPlan1<N>::C ? XPlan<N>::C : XPlan1<N>::C;
+  });
   int n = c->nchunk < 1 ? 1 : (c->nchunk > 8 ? 8 : c->nchunk);
   while (n > 1 && (c->Nloc % (n * rows_per_wg) != 0)) n >>= 1;
   return n;
@@ -2066,24 +2083,23 @@ static int slab_settle(std::vector<nq_ctx*>& grp) {
 
 // ---------------------------------------------------------------------------------------------
 // diagnostics tick launches
-template <int S, int CLX>
-static void launch_project_s(nq_ctx* c, double* part) {
-  typedef YPlanT<S, CLX> Y;
-  hipLaunchKernelGGL((k_s_project<S, CLX>), dim3(c->Wf / CLX, c->S2), dim3(Y::THREADS), Y::LDS_BYTES, c->stream, c->mW,
-                     (const cd*)c->w.y[c->w.cur], geom_full(c), c->kk, c->ll, c->tw, 1, c->p.nu4w, c->p.nuw, c->p.muw, part);
-}
 static void launch_project(nq_ctx* c, double* part) {
-#define CALL_(s, clx) launch_project_s<s, clx>(c, part)
-  NQ_S1_SWITCH(c, CALL_)
-#undef CALL_
+  with_col_plan(c, [&](auto s1, auto cly) {
+    constexpr int S = decltype(s1)::value, CLX = decltype(cly)::value;
+    typedef YPlanT<S, CLX> Y;
+    hipLaunchKernelGGL((k_s_project<S, CLX>), dim3(c->Wf / CLX, c->S2), dim3(Y::THREADS), Y::LDS_BYTES, c->stream, c->mW,
+                       (const cd*)c->w.y[c->w.cur], geom_full(c), c->kk, c->ll, c->tw, 1, c->p.nu4w, c->p.nuw, c->p.muw, part);
+  });
 }
 // the passive scalar's Gamma_c projection: B-fft of Muc, Mvc against c-hat; one partial per workgroup, their count returned
 static int launch_project_c(nq_ctx* x, const cd* ch, double* part) {
   const YGeom g = geom_half(x);
   if (g.width <= 0) return 0;
-#define CALL_(sz, clx) hipLaunchKernelGGL((k_s_project_c<sz, clx>), dim3((g.width + clx - 1) / clx, x->S2), dim3((YPlanT<sz, clx>::THREADS)), (YPlanT<sz, clx>::LDS_BYTES), x->stream, x->mUc, x->mVc, ch, g, x->kk, x->ll, x->tw, 1, part)
-  NQ_S1_SWITCH(x, CALL_)
-#undef CALL_
+  with_col_plan(x, [&](auto s1, auto cly) {
+    constexpr int S = decltype(s1)::value, CLX = decltype(cly)::value;
+    typedef YPlanT<S, CLX> Y;
+    hipLaunchKernelGGL((k_s_project_c<S, CLX>), dim3((g.width + CLX - 1) / CLX, x->S2), dim3(Y::THREADS), Y::LDS_BYTES, x->stream, x->mUc, x->mVc, ch, g, x->kk, x->ll, x->tw, 1, part);
+  });
   return ((g.width + x->CLy - 1) / x->CLy) * x->S2;
 }
 // the tick's two products passes: which = 0 leaves J = u phix + v phiy in Mw (c_J = 1, c_R = 0), which = 1 i phi q_psi (0, 1)
@@ -2112,24 +2128,21 @@ static int sum_ranks_on_host(std::vector<nq_ctx*>& grp, double* nq_ctx::*sums, s
   }
   return 0;
 }
-template <int S, int CLX>
-static void launch_project_bin_s(nq_ctx* c, double* rlap, double* rdiss) {
-  typedef YPlanT<S, CLX> Y;
-  hipLaunchKernelGGL((k_s_project_bin<S, CLX>), dim3(c->Wf / CLX, c->S2), dim3(Y::THREADS), Y::LDS_BYTES, c->stream, c->mW,
-                     (const cd*)c->w.y[c->w.cur], geom_full(c), c->kk, c->ll, c->tw, 1, c->p.nu4w, c->p.nuw, c->p.muw, rlap, rdiss, c->Wf);
-}
 static void launch_project_bin(nq_ctx* c, double* rlap, double* rdiss) {
-#define CALL_(s, clx) launch_project_bin_s<s, clx>(c, rlap, rdiss)
-  NQ_S1_SWITCH(c, CALL_)
-#undef CALL_
+  with_col_plan(c, [&](auto s1, auto cly) {
+    constexpr int S = decltype(s1)::value, CLX = decltype(cly)::value;
+    typedef YPlanT<S, CLX> Y;
+    hipLaunchKernelGGL((k_s_project_bin<S, CLX>), dim3(c->Wf / CLX, c->S2), dim3(Y::THREADS), Y::LDS_BYTES, c->stream, c->mW,
+                       (const cd*)c->w.y[c->w.cur], geom_full(c), c->kk, c->ll, c->tw, 1, c->p.nu4w, c->p.nuw, c->p.muw, rlap, rdiss, c->Wf);
+  });
 }
 template <int MODE, bool SLAB>
 static void launch_xdiag_t(nq_ctx* c, double qbar, double abar, double* part) {
-  switch (c->N) {
-#define CASE_(n, a, b) case n: { typedef XPlan<n> X; hipLaunchKernelGGL((k_x_diag<n, MODE, SLAB>), dim3(c->Nloc / X::C), dim3(X::THREADS), X::LDS_BYTES, c->stream, c->mQ, c->mQw, c->mPhi, c->twx, c->kk, qbar, abar, part); } break;
-    NQ_FOR_SIZES(CASE_)
-#undef CASE_
-  }
+  with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    typedef XPlan<N> X;
+    hipLaunchKernelGGL((k_x_diag<N, MODE, SLAB>), dim3(c->Nloc / X::C), dim3(X::THREADS), X::LDS_BYTES, c->stream, c->mQ, c->mQw, c->mPhi, c->twx, c->kk, qbar, abar, part);
+  });
 }
 template <int MODE>
 static void launch_xdiag_m(nq_ctx* c, double qbar, double abar, double* part) {
@@ -2137,23 +2150,20 @@ static void launch_xdiag_m(nq_ctx* c, double qbar, double abar, double* part) {
   else launch_xdiag_t<MODE, false>(c, qbar, abar, part);
 }
 static int xdiag_blocks(const nq_ctx* c) {
-  switch (c->N) {
-#define CASE_(n, a, b) case n: return c->Nloc / XPlan<n>::C;
-    NQ_FOR_SIZES(CASE_)
-#undef CASE_
-  }
-  return 0;
+  int nb = 0;
+  with_row_size(c->N, [&](auto n) { nb = c->Nloc / XPlan<decltype(n)::value>::C; });
+  return nb;
 }
 
 // PDFs of the physical fields (csrc/nq_hist.hpp): the tick's row pass with the binning (or the min/max) in place of the sums
 template <int MODE, bool SLAB, bool MINMAX>
 static void launch_xhist_t(nq_ctx* c, const HistArgs& h, double* part) {
   const int words = MINMAX ? 0 : hist_words(h.bins, h.jbins);
-  switch (c->N) {
-#define CASE_(n, a, b) case n: { typedef XPlan<n> X; hipLaunchKernelGGL((k_x_hist<n, MODE, SLAB, MINMAX>), dim3(c->Nloc / X::C), dim3(X::THREADS), hist_lds_bytes<n>(words), c->stream, c->mQ, c->mQw, c->mPhi, c->twx, c->kk, h, part); } break;
-    NQ_FOR_SIZES(CASE_)
-#undef CASE_
-  }
+  with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    typedef XPlan<N> X;
+    hipLaunchKernelGGL((k_x_hist<N, MODE, SLAB, MINMAX>), dim3(c->Nloc / X::C), dim3(X::THREADS), hist_lds_bytes<N>(words), c->stream, c->mQ, c->mQw, c->mPhi, c->twx, c->kk, h, part);
+  });
 }
 template <bool MINMAX>
 static void launch_xhist(nq_ctx* c, const HistArgs& h, double* part) {
@@ -2962,13 +2972,13 @@ static int pt_blocks(int n) { return (n + 255) / 256 < 4096 ? (n + 255) / 256 : 
 
 // the velocity plane of the current ph from Mu, Mp (one row kernel)
 static void pt_form_uv(nq_ctx* c, cd* out) {
-  switch (c->N) {
-#define CASE_(nn, a, b) case nn: { typedef XPlan<nn> X; constexpr bool one = nn >= 8192; \
-    for (int comp = 0; comp < (one ? 2 : 1); ++comp) \
-      hipLaunchKernelGGL((k_x_get_uv<nn, false, one>), dim3((c->N + X::C - 1) / X::C), dim3(X::THREADS), X::LDS_BYTES, c->stream, c->mU, c->mP, out, c->N, c->tw, c->kk, c->kernel_family ? 1 : 0, comp); } break;
-    NQ_FOR_SIZES(CASE_)
-#undef CASE_
-  }
+  with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    typedef XPlan<N> X;
+    constexpr bool one = N >= 8192;
+    for (int comp = 0; comp < (one ? 2 : 1); ++comp)
+      hipLaunchKernelGGL((k_x_get_uv<N, false, one>), rows_grid<X>(c->N), dim3(X::THREADS), X::LDS_BYTES, c->stream, c->mU, c->mP, out, c->N, c->tw, c->kk, c->kernel_family ? 1 : 0, comp);
+  });
 }
 static void pt_mark_stale(nq_ctx* c) {
   if (c && c->pt) c->pt->u0 = false;
@@ -2990,12 +3000,8 @@ static int pt_sample_into(nq_ctx* c, int name, double* o0, double* o1) {
     hipLaunchKernelGGL(k_pt_sample<cd>, dim3(nb), dim3(256), 0, c->stream, (const cd*)P->uv[P->cur], (const double*)P->x, (const double*)P->y, P->n, g, name == PT_U ? o0 : nullptr, name == PT_V ? o0 : nullptr);
   } else if (name == PT_Q) {
     if (!P->qplane) { int rc = pt_alloc(c, &P->qplane, (size_t)c->N * c->N); if (rc) return rc; }
-    switch (c->N) {      // Mq holds the q the last inversion saw (the mean of the two copies on dual-q contexts): m.q
-#define CASE_(nn, a, b) case nn: { typedef XPlan<nn> X; \
-      hipLaunchKernelGGL((k_x_get_real<nn, false>), dim3((c->N + X::C - 1) / X::C), dim3(X::THREADS), X::LDS_BYTES, c->stream, c->mQ, P->qplane, c->N, c->tw, c->kk, 0, 0); } break;
-      NQ_FOR_SIZES(CASE_)
-#undef CASE_
-    }
+    // Mq holds the q the last inversion saw (the mean of the two copies on dual-q contexts): m.q
+    if (!launch_get_real<false>(c, c->mQ, P->qplane, 0, 0)) NQ_FAIL(c, -2, "no row plan of length %d", c->N);
     hipLaunchKernelGGL(k_pt_sample<double>, dim3(nb), dim3(256), 0, c->stream, (const double*)P->qplane, (const double*)P->x, (const double*)P->y, P->n, g, o0, nullptr);
   } else if (name == PT_PHI) {
     if (!c->kernel_family) NQ_FAIL(c, -4, "particles: QGModel has no wave field (phi)");
@@ -3457,18 +3463,10 @@ int nq_slab_put_rows(nq_ctx* c, int which, const double* rows) {
   if (which == 2 && !c->passive) NQ_FAIL(c, -4, "nq_slab_put_rows: this context has no passive scalar");
   if (which == 0 || which == 2) {
     HIPCHK(c, hipMemcpyAsync(scr, rows, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-    switch (c->N) {
-#define CASE_(nn, a, b) case nn: { typedef XPlan<nn> X; hipLaunchKernelGGL((k_x_put_real<nn, true>), dim3((c->Nloc + X::C - 1) / X::C), dim3(X::THREADS), X::LDS_BYTES, c->stream, (const double*)scr, c->mUq, c->Nloc, c->tw); } break;
-      NQ_FOR_SIZES(CASE_)
-#undef CASE_
-    }
+    if (!launch_put_real(c, (const double*)scr, c->mUq)) NQ_FAIL(c, -2, "no row plan of length %d", c->N);
   } else if (which == 1) {
     HIPCHK(c, hipMemcpyAsync(scr, rows, sizeof(cd) * n, hipMemcpyHostToDevice, c->stream));
-    switch (c->N) {
-#define CASE_(nn, a, b) case nn: { typedef XPlan<nn> X; hipLaunchKernelGGL((k_x_put_cplx<nn, true>), dim3((c->Nloc + X::C - 1) / X::C), dim3(X::THREADS), X::LDS_BYTES, c->stream, (const cd*)scr, c->mW, c->Nloc, c->tw); } break;
-      NQ_FOR_SIZES(CASE_)
-#undef CASE_
-    }
+    if (!launch_put_cplx(c, (const cd*)scr, c->mW)) NQ_FAIL(c, -2, "no row plan of length %d", c->N);
   } else NQ_FAIL(c, -1, "nq_slab_put_rows: which = %d", which);
   HIPCHK(c, hipGetLastError());
   return nq_sync(c);                            // the host rows may be released
@@ -3574,13 +3572,8 @@ int nq_slab_get_rows(nq_ctx* c, int id, double* out) {
     default: NQ_FAIL(c, -1, "nq_slab_get_rows: field id %d", id);
   }
   if (!real && !c->kernel_family) NQ_FAIL(c, -4, "no wave field in QGModel");
-  switch (c->N) {
-#define CASE_(nn, a, b) case nn: { typedef XPlan<nn> X; const dim3 grid((c->Nloc + X::C - 1) / X::C), blk(X::THREADS); \
-      if (real) hipLaunchKernelGGL((k_x_get_real<nn, true>), grid, blk, X::LDS_BYTES, c->stream, *src, reinterpret_cast<double*>(scr), c->Nloc, c->tw, c->kk, mode, zero_nyq); \
-      else hipLaunchKernelGGL((k_x_get_cplx<nn, true>), grid, blk, X::LDS_BYTES, c->stream, *src, scr, c->Nloc, c->tw, c->kk, mul_ik); } break;
-    NQ_FOR_SIZES(CASE_)
-#undef CASE_
-  }
+  if (!(real ? launch_get_real<true>(c, *src, reinterpret_cast<double*>(scr), mode, zero_nyq) : launch_get_cplx(c, *src, scr, mul_ik)))
+    NQ_FAIL(c, -2, "no row plan of length %d", c->N);
   HIPCHK(c, hipMemcpyAsync(out, scr, (real ? sizeof(double) : sizeof(cd)) * n, hipMemcpyDeviceToHost, c->stream));
   return nq_sync(c);
 }
@@ -3650,18 +3643,10 @@ int nq_slab_local_max(nq_ctx* c, double* out3) {
   }
   double* d = c->diag_out + 34;
   HIPCHK(c, hipMemsetAsync(d, 0, sizeof(double) * 3, c->stream));
-  const size_t n = (size_t)c->Nloc * c->N;
-  for (int which = 0; which < (c->kernel_family ? 3 : 2); ++which) {
-    const MArr& src = which == 0 ? c->mU : (which == 1 ? c->mP : c->mPhi);
-    switch (c->N) {
-#define CASE_(nn, a, b) case nn: { typedef XPlan<nn> X; const dim3 grid((c->Nloc + X::C - 1) / X::C), blk(X::THREADS); \
-        if (which < 2) hipLaunchKernelGGL((k_x_get_real<nn, true>), grid, blk, X::LDS_BYTES, c->stream, src, reinterpret_cast<double*>(scr), c->Nloc, c->tw, c->kk, which, (which == 1 && c->kernel_family) ? 1 : 0); \
-        else hipLaunchKernelGGL((k_x_get_cplx<nn, true>), grid, blk, X::LDS_BYTES, c->stream, src, scr, c->Nloc, c->tw, c->kk, 0); } break;
-      NQ_FOR_SIZES(CASE_)
-#undef CASE_
-    }
-    if (which < 2) hipLaunchKernelGGL(k_reduce_real_max, dim3(1024), dim3(256), 0, c->stream, reinterpret_cast<const double*>(scr), n, d + which);
-    else hipLaunchKernelGGL(k_reduce, dim3((c->N + 255) / 256, c->Nloc), dim3(256), 0, c->stream, (const cd*)scr, c->N, c->N, c->N, 3, c->kk, c->ll, d + 2);
+  if (!launch_uv_max(c, reinterpret_cast<double*>(scr), d)) NQ_FAIL(c, -2, "no row plan of length %d", c->N);
+  if (c->kernel_family) {
+    launch_get_cplx(c, c->mPhi, scr, 0);
+    hipLaunchKernelGGL(k_reduce, dim3((c->N + 255) / 256, c->Nloc), dim3(256), 0, c->stream, (const cd*)scr, c->N, c->N, c->N, 3, c->kk, c->ll, d + 2);
   }
   HIPCHK(c, hipMemcpyAsync(out3, d, sizeof(double) * 3, hipMemcpyDeviceToHost, c->stream));
   return nq_sync(c);
@@ -4722,50 +4707,51 @@ static int any_rows_fft(nq_any* e, const nq_any::Plan& pl, int nlines, double sc
     const dim3 tg(A / 16, B / 16, nlines), tb(256);
     const int rows128 = nlines * 128;
     hipLaunchKernelGGL(k_any_btranspose, tg, tb, 0, e->stream, (const cd*)e->tmp, e->tmp2, B, A, (const cd*)nullptr, 0, 0);
-    hipLaunchKernelGGL((k_x_c2c<128, INV>), dim3((rows128 + X::C - 1) / X::C), dim3(X::THREADS), X::LDS_BYTES, e->stream, (const cd*)e->tmp2, e->tmp2, 128, 128,
+    hipLaunchKernelGGL((k_x_c2c<128, INV>), rows_grid<X>(rows128), dim3(X::THREADS), X::LDS_BYTES, e->stream, (const cd*)e->tmp2, e->tmp2, 128, 128,
                        rows128, 1.0, (const cd*)pl.tw_small, (const double*)nullptr, 0);
     hipLaunchKernelGGL(k_any_btranspose, tg, tb, 0, e->stream, (const cd*)e->tmp2, e->tmp, A, B, (const cd*)pl.tw, 1, INV ? 1 : 0);
-    hipLaunchKernelGGL((k_x_c2c<128, INV>), dim3((rows128 + X::C - 1) / X::C), dim3(X::THREADS), X::LDS_BYTES, e->stream, (const cd*)e->tmp, e->tmp, 128, 128,
+    hipLaunchKernelGGL((k_x_c2c<128, INV>), rows_grid<X>(rows128), dim3(X::THREADS), X::LDS_BYTES, e->stream, (const cd*)e->tmp, e->tmp, 128, 128,
                        rows128, scale, (const cd*)pl.tw_small, (const double*)nullptr, 0);
     hipLaunchKernelGGL(k_any_btranspose, tg, tb, 0, e->stream, (const cd*)e->tmp, e->tmp2, B, A, (const cd*)nullptr, 0, 0);
     std::swap(e->tmp, e->tmp2);
     std::swap(e->tmp_elems, e->tmp2_elems);
     return 0;
   }
-  switch (pl.M) {
-#define CASE_(n, a, b) case n: { typedef XPlan<n> X; \
-      hipLaunchKernelGGL((k_x_c2c<n, INV>), dim3((nlines + X::C - 1) / X::C), dim3(X::THREADS), X::LDS_BYTES, e->stream, \
-                         (const cd*)e->tmp, e->tmp, pl.M, pl.M, nlines, scale, (const cd*)pl.tw, (const double*)nullptr, 0); } break;
-    NQ_FOR_SIZES(CASE_)
-#undef CASE_
-    default: ANYFAIL(e, -2, "any-size engine: no row plan of length %d", pl.M);
-  }
+  const bool ok = with_row_size(pl.M, [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    typedef XPlan<M> X;
+    hipLaunchKernelGGL((k_x_c2c<M, INV>), rows_grid<X>(nlines), dim3(X::THREADS), X::LDS_BYTES, e->stream,
+                       (const cd*)e->tmp, e->tmp, pl.M, pl.M, nlines, scale, (const cd*)pl.tw, (const double*)nullptr, 0);
+  });
+  if (!ok) ANYFAIL(e, -2, "any-size engine: no row plan of length %d", pl.M);
   return 0;
 }
 // the fused Bluestein row kernel on `nlines` contiguous rows of `n` values (pitch n), in place or src -> dst
 static int any_bluestein_rows(nq_any* e, const nq_any::Plan& pl, const cd* src, cd* dst, int nlines, int n, int inverse) {
   const double scale = (inverse ? 1.0 / (double)n : 1.0) / (double)pl.M;
-  switch (pl.M) {
-#define CASE_(m, a, b) case m: { typedef XPlan<m> X; \
-      hipLaunchKernelGGL((k_any_bluestein_rows<m>), dim3((nlines + X::C - 1) / X::C), dim3(X::THREADS), X::LDS_BYTES, e->stream, src, dst, nlines, n, n, \
-                         (const cd*)pl.chirp, (const cd*)pl.bhat, (const cd*)pl.tw, inverse ? 1 : 0, scale); } break;
-    NQ_FOR_SIZES(CASE_)
-#undef CASE_
-    default: ANYFAIL(e, -2, "any-size engine: no fused row plan of length %d", pl.M);
-  }
+  const bool ok = with_row_size(pl.M, [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    typedef XPlan<M> X;
+    hipLaunchKernelGGL((k_any_bluestein_rows<M>), rows_grid<X>(nlines), dim3(X::THREADS), X::LDS_BYTES, e->stream, src, dst, nlines, n, n,
+                       (const cd*)pl.chirp, (const cd*)pl.bhat, (const cd*)pl.tw, inverse ? 1 : 0, scale);
+  });
+  if (!ok) ANYFAIL(e, -2, "any-size engine: no fused row plan of length %d", pl.M);
   return 0;
 }
 template <int R>
 static int any_split_rows(nq_any* e, const nq_any::Plan& pl, const cd* src, cd* dst, int nlines, int n, int inverse) {
   const double scale = inverse ? 1.0 / (double)n : 1.0;
-  switch (pl.M) {
-#define CASE_(m, a, b) case m: { typedef XPlan<m> X; \
-      hipLaunchKernelGGL((k_any_split_rows<m, R>), dim3((nlines + X::C - 1) / X::C), dim3(X::THREADS), X::LDS_BYTES, e->stream, src, dst, nlines, n, \
-                         (const cd*)pl.chirp, (const cd*)pl.tw, inverse ? 1 : 0, scale); } break;
-    M_SMALL(CASE_)
-#undef CASE_
-    default: ANYFAIL(e, -2, "any-size engine: no split row plan of length %d x %d", R, pl.M);
-  }
+  bool ok = false;
+  with_row_size(pl.M, [&](auto m) {
+    constexpr int M = decltype(m)::value;
+    if constexpr (M <= 2048) {                       // the split kernels exist for these lengths only
+      typedef XPlan<M> X;
+      hipLaunchKernelGGL((k_any_split_rows<M, R>), rows_grid<X>(nlines), dim3(X::THREADS), X::LDS_BYTES, e->stream, src, dst, nlines, n,
+                         (const cd*)pl.chirp, (const cd*)pl.tw, inverse ? 1 : 0, scale);
+      ok = true;
+    }
+  });
+  if (!ok) ANYFAIL(e, -2, "any-size engine: no split row plan of length %d x %d", R, pl.M);
   return 0;
 }
 // device temporaries of one call: freed when the call returns, on the error paths too
