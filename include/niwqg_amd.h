@@ -280,6 +280,31 @@ int nq_particles_get(nq_ctx* ctx, double* x, double* y);
 int nq_particles_sample(nq_ctx* ctx, int nnames, const int* names, double* out);
 int nq_particles_records(nq_ctx* ctx, long long* info4, long long* steps, double* out);
 
+/* Stochastic forcing of q and phi, single-rank contexts only (slab contexts refuse every call with -4).
+ * After every step of nq_step (after the filtered ETDRK4 update, unfiltered) the library adds
+ *   qh(l, k)   += sqrt(dt) Aq(l, k)   xi_q(l, k; s)      half spectrum (ny, nx/2+1), Hermitian: the forcing of q is a real field
+ *   phih(l, k) += sqrt(dt) Aphi(l, k) xi_phi(l, k; s)    full plane (ny, nx), independent complex values
+ * and then does what the end of a step does: phi, phiy from the new phih (when phi is forced; UnCoupledModel's frozen gradients,
+ * quirk Q1, stay), the inversion of the new state, its spectral sums carried into slot 0 of the next step's budgets.  s starts at
+ * step0 and counts forced steps (its low 32 bits enter the counter).  xi: Philox4x32-10, counter (l, k, s, stream) with stream
+ * 0 for q and 1 for phi, key (seed & 0xffffffff, seed >> 32); from the output x0..x3: n = (x0 >> 5) 2^26 + (x1 >> 6),
+ * u1 = 1 - n 2^-53, u2 = (x2 + 0.5) 2^-32, xi = sqrt(-ln u1) (cos 2 pi u2 + i sin 2 pi u2), E|xi|^2 = 1.  xi_q is zero on row
+ * ny/2, column nx/2 and at (0, 0) whatever Aq holds; on column 0 row ny - l takes the conjugate of the value drawn at (l, 0),
+ * 1 <= l < ny/2 (Aq must be equal on the two rows); a dual-q context adds the same increment to both copies of qh.
+ * Amplitudes are finite and >= 0 (host arrays; NULL: that field is not forced; at least one).  QGModel takes q only, YBJModel
+ * phi only (-1 otherwise).  The kernels run over the bounding box of A > 0 in (|l|, |k|) only.  Work, in fp64 on the device,
+ * from per-workgroup partials summed in a fixed order (bit-reproducible), with psi-hat and phih BEFORE the increment D:
+ *   work_q   += sum_full [ -Re(conj(psi-hat) D) + |D|^2 / (2 wv2) ] / M^2     (the change of ke_qg at fixed q_w)
+ *   work_phi += sum      [  Re(conj(phih) D)    + |D|^2 / 2 ]       / M^2     (the change of ke_niw)
+ * Ke, Pw, Kw stay the unforced rates.  Every allocation is counted by nq_device_bytes and freed by detach.
+ * apply: one increment and re-inversion now, outside a step (advances s).  increment: the increment of step s of stream 0 / 1
+ * as a host plane ((ny, nx/2+1) / (ny, nx) complex), the state untouched.  state: out3 = {s, work_q, work_phi}.              */
+int nq_forcing_attach(nq_ctx* ctx, const double* Aq, const double* Aphi, unsigned long long seed, long long step0);
+int nq_forcing_detach(nq_ctx* ctx);
+int nq_forcing_apply(nq_ctx* ctx);
+int nq_forcing_increment(nq_ctx* ctx, int stream, long long s, double* out_cplx);
+int nq_forcing_state(nq_ctx* ctx, double* out3);
+
 /* copy of one ETDRK4 coefficient plane (0:E 1:Eh 2:Q 3:f0 4:fab 5:fc) of equation eq (0: q, (nx, nx/2+1) complex;
  * 1: phi, (nx, nx) complex; 2: QGModel's passive scalar, (nx, nx/2+1)), without the filter folded in; values as the
  * reference's expch, expch_h, Qh, f0, fab, fc (Kernel.py:417-454, QGModel.py:426-461).                           */
@@ -514,6 +539,13 @@ int nq_any_minmax(nq_any* eng, const void* plane, long long elems, int what, dou
 int nq_any_particles_rk4(nq_any* eng, void* pos, int n, const void* U0, const void* U1, int nx, double Lx, double Ly, double U,
                          double dt);
 int nq_any_interp(nq_any* eng, void* out, const void* plane, const void* pos, int n, int nx, double Lx, double Ly);
+/* Stochastic forcing on engine planes (nq_forcing_attach above: the same generator, counters and Hermitian rule):
+ * plane += sqrt_dt Re(amp_plane) xi(.; s).  layout 0: (rows, rows/2+1) half spectrum under the q rule; 1: full (rows, rows) plane,
+ * independent values of `stream`; 2: full plane, the Hermitian extension of the q rule (columns k > rows/2 take the conjugate of
+ * (-l, -k)).  work_in_plane (NULL: none; it may be `plane` itself, read before the increment D) and work_out2 go together:
+ * work_out2 = {sum w Re(conj(work_in) D), sum w |D|^2} / M^2, w the half-spectrum weights on layout 0, else 1.               */
+int nq_any_forcing(nq_any* eng, void* plane, const void* amp_plane, int rows, int cols, int layout, unsigned long long seed, long long s,
+                   int stream, double sqrt_dt, const void* work_in_plane, double* work_out2);
 /* E = exp(c dt), Eh = exp(c dt / 2), Q, f0, fab, fc of the linear operator c(l, k) on a (n, cols) plane, WITHOUT the filter
  * (Kernel.py:417-454, QGModel.py:426-466); eq 0: q of the Kernel family, 1: phi, 2: QGModel's q (beta term), 3: its passive
  * scalar.  The entries within delta of the contour are listed (near_*; at most cap) for the host to recompute exactly as the

@@ -788,6 +788,9 @@ class KernelFamily(object):
         if P is not None:
             P._before_step()
         self._step_etdrk4_state()
+        F = self.__dict__.get("_forcing")            # stochastic forcing (niwqg_amd/forcing.py): increment, then the end of a step again
+        if F is not None:
+            F._after_step()
         if P is not None:
             P._after_step()
 
@@ -1144,6 +1147,9 @@ class QGFamily(object):
         if P is not None:
             P._before_step()
         self._step_etdrk4_state()
+        F = self.__dict__.get("_forcing")            # stochastic forcing (niwqg_amd/forcing.py): increment, then the end of a step again
+        if F is not None:
+            F._after_step()
         if P is not None:
             P._after_step()
 

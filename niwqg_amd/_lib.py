@@ -20,7 +20,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # NIWQG_AMD_LIB: another build of the same sources (A/B experiments with compile-time knobs, tools/); default: the in-tree library
 LIB_PATH = os.environ.get("NIWQG_AMD_LIB") or os.path.join(HERE, "libniwqg_amd.so")
 SRC = os.path.join(HERE, "csrc", "nq_lib.hip")
-HEADERS = [os.path.join(HERE, "csrc", h) for h in ("nq_fft.hpp", "nq_generic.hpp", "nq_step.hpp", "nq_anysize.hpp", "nq_particles.hpp", "nq_hist.hpp")] + [
+HEADERS = [os.path.join(HERE, "csrc", h) for h in ("nq_fft.hpp", "nq_generic.hpp", "nq_step.hpp", "nq_anysize.hpp", "nq_particles.hpp", "nq_forcing.hpp", "nq_hist.hpp")] + [
     os.path.join(os.path.dirname(HERE), "include", "niwqg_amd.h")]
 
 COUPLED, UNCOUPLED, QG, YBJ = 0, 1, 2, 3
@@ -32,6 +32,7 @@ EXPORTS = ["nq_create", "nq_destroy", "nq_last_error", "nq_set_q", "nq_set_c", "
            "nq_step", "nq_profile_stride", "nq_request_stage4_max", "nq_get_stage4_max", "nq_tick_snapshot", "nq_sync", "nq_get_field", "nq_get_qh_passenger", "nq_get_scalar", "nq_fft2", "nq_ifft2", "nq_rfft2",
            "nq_irfft2", "nq_jacobian_psi_q", "nq_jacobian_psi_c", "nq_jacobian_psi_phi", "nq_jacobian_phic_phi", "nq_products_uq_vq", "nq_refraction", "nq_field_doubles", "nq_get_coeff", "nq_coeff_near_contour", "nq_coeff_patch", "nq_diagnostics", "nq_spectrum_shells", "nq_diagnostics_binned", "nq_transfer_binned",
            "nq_particles_attach", "nq_particles_detach", "nq_particles_get", "nq_particles_sample", "nq_particles_records",
+           "nq_forcing_attach", "nq_forcing_detach", "nq_forcing_apply", "nq_forcing_increment", "nq_forcing_state", "nq_any_forcing",
            "nq_stream_copy_gbs", "nq_timer_start", "nq_timer_stop", "nq_event_record", "nq_event_elapsed", "nq_profile_enable", "nq_profile_read", "nq_profile_read_all", "nq_group_elems", "nq_overlap_grid", "nq_overlap_default_cus", "nq_overlap_info", "nq_create_slab",
            "nq_slab_info", "nq_group_buffers", "nq_upload_spectral", "nq_download_spectral", "nq_phase",
            "nq_reduce_buffer", "nq_reduce_read", "nq_reduce_write", "nq_device_bytes", "nq_stream",
@@ -133,6 +134,13 @@ def lib():
     L.nq_particles_get.argtypes = [vp, dp, dp]
     L.nq_particles_sample.argtypes = [vp, ctypes.c_int, ip, dp]
     L.nq_particles_records.argtypes = [vp, llp, llp, dp]
+    L.nq_forcing_attach.argtypes = [vp, dp, dp, ctypes.c_ulonglong, ctypes.c_longlong]
+    L.nq_forcing_detach.argtypes = [vp]
+    L.nq_forcing_apply.argtypes = [vp]
+    L.nq_forcing_increment.argtypes = [vp, ctypes.c_int, ctypes.c_longlong, dp]
+    L.nq_forcing_state.argtypes = [vp, dp]
+    L.nq_any_forcing.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_longlong, ctypes.c_int,
+                                 ctypes.c_double, vp, dp]
     L.nq_get_coeff.argtypes = [vp, ctypes.c_int, ctypes.c_int, dp]
     L.nq_coeff_near_contour.argtypes = [vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     L.nq_coeff_patch.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, dp]
@@ -577,3 +585,26 @@ class Context:
         out = np.zeros(n1 + (joint_bins * joint_bins + 1 if joint_bins else 0), np.uint64)
         self._chk(self.L.nq_field_hist_read(self.h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong))), "nq_field_hist_read")
         return out[:n1].reshape(nfields, bins + 3), (out[n1:] if joint_bins else None)
+
+    # ---- stochastic forcing (include/niwqg_amd.h: nq_forcing_*; niwqg_amd/forcing.py) ------------------------------------------
+    def forcing_attach(self, Aq, Aphi, seed, step0):
+        Aq = None if Aq is None else np.ascontiguousarray(Aq, np.float64)
+        Aphi = None if Aphi is None else np.ascontiguousarray(Aphi, np.float64)
+        self._chk(self.L.nq_forcing_attach(self.h, None if Aq is None else _dptr(Aq), None if Aphi is None else _dptr(Aphi),
+                                           int(seed), int(step0)), "nq_forcing_attach")
+
+    def forcing_detach(self):
+        self._chk(self.L.nq_forcing_detach(self.h), "nq_forcing_detach")
+
+    def forcing_apply(self):
+        self._chk(self.L.nq_forcing_apply(self.h), "nq_forcing_apply")
+
+    def forcing_increment(self, stream, step):
+        out = np.empty((self.nx, self.nx // 2 + 1 if stream == 0 else self.nx), np.complex128)
+        self._chk(self.L.nq_forcing_increment(self.h, int(stream), int(step), _dptr(out.view(np.float64))), "nq_forcing_increment")
+        return out
+
+    def forcing_state(self):
+        out = np.empty(3)
+        self._chk(self.L.nq_forcing_state(self.h, _dptr(out)), "nq_forcing_state")
+        return int(out[0]), float(out[1]), float(out[2])

@@ -13,6 +13,7 @@
 #include "nq_anysize.hpp"
 #include "nq_particles.hpp"
 #include "nq_hist.hpp"
+#include "nq_forcing.hpp"
 
 using namespace nq;
 
@@ -184,8 +185,10 @@ struct nq_ctx {
   MArr mUc, mVc;      // niwqg.YBJModel: UnCoupled layouts, only phi is stepped (stage graph in do_step_ybj)
   struct NqParticles* pt = nullptr;   // Lagrangian particles (nq_particles_attach): null when none
   double pt_L[2] = {0.0, 0.0};       // their domain, Lx and Ly
+  struct NqForcing* fc = nullptr;     // stochastic forcing (nq_forcing_attach): null when none
 };
 static void pt_release(nq_ctx* c);
+static void fc_release(nq_ctx* c);
 
 // Device arrays start at staggered offsets inside their allocations.  hipMalloc hands out large blocks at addresses that
 // differ by multiples of 2 MiB (the 256 MiB planes: by exact multiples of their size), so element idx of every state,
@@ -2630,6 +2633,7 @@ int nq_destroy(nq_ctx* c) {
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);
   pt_release(c);
+  fc_release(c);
   for (void* p : c->allocs) hipFree(p);
   for (auto& pt : c->patch) { (void)hipFree(pt.l); (void)hipFree(pt.k); (void)hipFree(pt.v); }
   for (hipEvent_t e : c->prof_ev) hipEventDestroy(e);
@@ -2876,6 +2880,7 @@ int nq_refresh_grad_phi(nq_ctx* c) {
 
 static void pt_before_step(nq_ctx* c);
 static int pt_after_step(nq_ctx* c);
+static int fc_apply(nq_ctx* c);
 int nq_step(nq_ctx* c, int nsteps) {
   if (!c) return -1;
   NQ_SINGLE_RANK(c, "nq_step");
@@ -2885,6 +2890,10 @@ int nq_step(nq_ctx* c, int nsteps) {
     c->uv4_now = c->want_uv4 && i == nsteps - 1 && c->kernel_family && !c->ybj;
     if (c->pt) pt_before_step(c);
     do_step(c);
+    if (c->fc) {                       // the forced, re-inverted state is what the particles' U1 and the next step see
+      const int rc = fc_apply(c);
+      if (rc) return rc;
+    }
     if (c->pt) {
       const int rc = pt_after_step(c);
       if (rc) return rc;
@@ -3159,6 +3168,185 @@ int nq_particles_records(nq_ctx* c, long long* info, long long* steps, double* o
     if (steps) steps[r] = P->ring_step[slot];
     if (out) HIPCHK(c, hipMemcpyAsync(out + (size_t)r * rec, P->ring + (size_t)slot * rec, sizeof(double) * rec, hipMemcpyDeviceToHost, c->stream));
   }
+  return nq_sync(c);
+}
+
+// ---- stochastic forcing (kernels and the generator: nq_forcing.hpp) --------------------------------
+struct NqForcing {
+  double *Aq = nullptr, *Aphi = nullptr;   // amplitude planes: (N, N/2+1) and (N, N), contiguous
+  FcBox bq = {}, bphi = {};                // bounding boxes of A > 0 (nrows = 0: nothing to add)
+  dim3 gq, gphi;                           // launch grids over the boxes
+  int npq = 0, npphi = 0;                  // workgroups = work partials of each kernel
+  double *partq = nullptr, *partphi = nullptr, *work = nullptr;   // partials [workgroups][2]; work_q, work_phi
+  unsigned long long seed = 0;
+  long long s = 0;                         // index of the next forced step
+  std::vector<void*> mem;
+  long long bytes = 0;
+};
+static int fc_alloc_raw(nq_ctx* c, void** out, size_t bytes) {
+  NqForcing* F = c->fc;
+  void* p = nullptr;
+  HIPCHK(c, hipMalloc(&p, bytes));
+  F->mem.push_back(p);
+  F->bytes += (long long)bytes;
+  c->bytes += (long long)bytes;
+  HIPCHK(c, hipMemsetAsync(p, 0, bytes, c->stream));
+  *out = p;
+  return 0;
+}
+#define fc_alloc(c, pptr, count) fc_alloc_raw((c), reinterpret_cast<void**>(pptr), (size_t)(count) * sizeof(**(pptr)))
+static void fc_release(nq_ctx* c) {
+  NqForcing* F = c->fc;
+  if (!F) return;
+  (void)hipSetDevice(c->device);
+  (void)hipStreamSynchronize(c->stream);
+  for (void* p : F->mem) (void)hipFree(p);
+  c->bytes -= F->bytes;
+  delete F;
+  c->fc = nullptr;
+}
+// bounding box of A > 0 on a (N, cols) host plane: cols = N/2+1 (half: k itself) or N (full: |k| as |l|)
+static FcBox fc_box(const double* A, int N, int cols) {
+  int L = -1, K = -1;
+  for (int l = 0; l < N; ++l)
+    for (int k = 0; k < cols; ++k)
+      if (A[(size_t)l * cols + k] > 0.0) {
+        const int al = l <= N / 2 ? l : N - l, ak = (cols == N && k > N / 2) ? N - k : k;
+        if (al > L) L = al;
+        if (ak > K) K = ak;
+      }
+  FcBox b = {N, L, K, 0, 0};
+  if (L < 0) return b;
+  b.nrows = 2 * L + 1 < N ? 2 * L + 1 : N;
+  b.ncols = cols == N ? (2 * K + 1 < N ? 2 * K + 1 : N) : K + 1;
+  return b;
+}
+static dim3 fc_grid(const FcBox& b) { return dim3((b.ncols + 63) / 64, (b.nrows + 3) / 4); }
+
+// one increment of step index s into the state, its work into F->work, then the end of a step: phi, phiy from the new phih
+// (when phi was forced), the inversion of the new state with its spectral sums carried into the next step's slot 0
+static int fc_apply(nq_ctx* c) {
+  NqForcing* F = c->fc;
+  const double sdt = sqrt(c->p.dt);
+  const uint32_t s = (uint32_t)((unsigned long long)F->s & 0xffffffffull);
+  const bool fq = F->Aq && F->bq.nrows > 0, fw = F->Aphi && F->bphi.nrows > 0;
+  if (fq)
+    hipLaunchKernelGGL(k_force_half<double>, F->gq, dim3(64, 4), 0, c->stream, c->q.y[c->q.cur], c->dual ? c->q2.y[c->q2.cur] : (cd*)nullptr, c->Ph,
+                       (const double*)F->Aq, F->bq, sdt, s, F->seed, (const cd*)c->ph, c->Ph, (const double*)c->kk, (const double*)c->ll, F->partq, (cd*)nullptr);
+  if (fw)
+    hipLaunchKernelGGL((k_force_full<double, false>), F->gphi, dim3(64, 4), 0, c->stream, c->w.y[c->w.cur], (const double*)F->Aphi, F->bphi, sdt, s, 1u,
+                       F->seed, (const cd*)c->w.y[c->w.cur], (const double*)nullptr, (const double*)nullptr, F->partphi, (cd*)nullptr);
+  if (fq || fw)
+    hipLaunchKernelGGL(k_force_accum, dim3(1), dim3(256), 0, c->stream, (const double*)F->partq, fq ? F->npq : 0, (const double*)F->partphi, fw ? F->npphi : 0,
+                       1.0 / ((double)c->N * c->N * (double)c->N * c->N), F->work, (double*)nullptr);
+  if (F->Aphi) {                          // as nq_set_phi, without its refresh of UnCoupledModel's frozen gradients (quirk Q1)
+    launch_emit_phi(c, c->w.y[c->w.cur]);
+    launch_A_m(c, true, {&c->mPhi, &c->mPhiy});
+    if (c->bud) hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(1024), 0, c->stream, c->part0W, c->nww, NQ_PARTW, 4, c->carryW);
+  }
+  if (!c->ybj) do_invert_now(c);          // (YBJModel: psi is steady)
+  ++F->s;
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+int nq_forcing_attach(nq_ctx* c, const double* Aq, const double* Aphi, unsigned long long seed, long long step0) {
+  NQ_SINGLE_RANK(c, "nq_forcing_attach");
+  if (c->fc) NQ_FAIL(c, -4, "nq_forcing_attach: a forcing is attached already (nq_forcing_detach first)");
+  if (!Aq && !Aphi) NQ_FAIL(c, -1, "nq_forcing_attach: no amplitude plane");
+  if (Aq && c->ybj) NQ_FAIL(c, -1, "nq_forcing_attach: YBJModel's psi is steady (phi forcing only)");
+  if (Aphi && !c->kernel_family) NQ_FAIL(c, -1, "nq_forcing_attach: QGModel has no wave field (q forcing only)");
+  if (step0 < 0) NQ_FAIL(c, -1, "nq_forcing_attach: step0 = %lld", step0);
+  const int N = c->N, Wh = N / 2 + 1;
+  if (Aq) {
+    for (size_t i = 0; i < (size_t)N * Wh; ++i)
+      if (!std::isfinite(Aq[i]) || Aq[i] < 0.0) NQ_FAIL(c, -1, "nq_forcing_attach: the q amplitude is not finite and >= 0 at element %zu", i);
+    for (int l = 1; l < N / 2; ++l)          // the increment is a real field's: column 0 mirrors in l
+      if (Aq[(size_t)l * Wh] != Aq[(size_t)(N - l) * Wh]) NQ_FAIL(c, -1, "nq_forcing_attach: the q amplitude differs between rows %d and %d of column 0", l, N - l);
+  }
+  if (Aphi)
+    for (size_t i = 0; i < (size_t)N * N; ++i)
+      if (!std::isfinite(Aphi[i]) || Aphi[i] < 0.0) NQ_FAIL(c, -1, "nq_forcing_attach: the phi amplitude is not finite and >= 0 at element %zu", i);
+  HIPCHK(c, hipSetDevice(c->device));
+  c->fc = new NqForcing();
+  NqForcing* F = c->fc;
+  F->seed = seed;
+  F->s = step0;
+  int rc = fc_alloc(c, &F->work, 2);
+  if (!rc && Aq) {
+    F->bq = fc_box(Aq, N, Wh);
+    F->gq = fc_grid(F->bq);
+    F->npq = (int)(F->gq.x * F->gq.y);
+    rc = fc_alloc(c, &F->Aq, (size_t)N * Wh);
+    if (!rc && F->npq > 0) rc = fc_alloc(c, &F->partq, (size_t)2 * F->npq);
+  }
+  if (!rc && Aphi) {
+    F->bphi = fc_box(Aphi, N, N);
+    F->gphi = fc_grid(F->bphi);
+    F->npphi = (int)(F->gphi.x * F->gphi.y);
+    rc = fc_alloc(c, &F->Aphi, (size_t)N * N);
+    if (!rc && F->npphi > 0) rc = fc_alloc(c, &F->partphi, (size_t)2 * F->npphi);
+  }
+  if (rc) {
+    const std::string e = c->err;
+    fc_release(c);
+    NQ_FAIL(c, rc, "%s", e.c_str());
+  }
+  if (Aq) HIPCHK(c, hipMemcpyAsync(F->Aq, Aq, sizeof(double) * (size_t)N * Wh, hipMemcpyHostToDevice, c->stream));
+  if (Aphi) HIPCHK(c, hipMemcpyAsync(F->Aphi, Aphi, sizeof(double) * (size_t)N * N, hipMemcpyHostToDevice, c->stream));
+  return nq_sync(c);
+}
+int nq_forcing_detach(nq_ctx* c) {
+  NQ_SINGLE_RANK(c, "nq_forcing_detach");
+  if (!c->fc) NQ_FAIL(c, -4, "nq_forcing_detach: no forcing attached");
+  fc_release(c);
+  return 0;
+}
+int nq_forcing_apply(nq_ctx* c) {
+  NQ_SINGLE_RANK(c, "nq_forcing_apply");
+  if (!c->fc) NQ_FAIL(c, -4, "nq_forcing_apply: no forcing attached");
+  pt_mark_stale(c);
+  HIPCHK(c, hipSetDevice(c->device));
+  const int rc = fc_apply(c);
+  if (rc) return rc;
+  return nq_sync(c);
+}
+int nq_forcing_increment(nq_ctx* c, int stream, long long s, double* out) {
+  NQ_SINGLE_RANK(c, "nq_forcing_increment");
+  NqForcing* F = c->fc;
+  if (!F) NQ_FAIL(c, -4, "nq_forcing_increment: no forcing attached");
+  if (!out || s < 0) return -1;
+  if (stream != 0 && stream != 1) NQ_FAIL(c, -1, "nq_forcing_increment: stream %d (0: q, 1: phi)", stream);
+  if (!(stream == 0 ? F->Aq : F->Aphi)) NQ_FAIL(c, -4, "nq_forcing_increment: %s is not forced", stream == 0 ? "q" : "phi");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int N = c->N;
+  const size_t n = (size_t)N * (stream == 0 ? N / 2 + 1 : N);
+  void* tmp = nullptr;
+  HIPCHK(c, hipMalloc(&tmp, sizeof(cd) * n));
+  const double sdt = sqrt(c->p.dt);
+  const uint32_t s32 = (uint32_t)((unsigned long long)s & 0xffffffffull);
+  hipError_t er = hipMemsetAsync(tmp, 0, sizeof(cd) * n, c->stream);
+  if (stream == 0 && F->bq.nrows > 0)
+    hipLaunchKernelGGL(k_force_half<double>, F->gq, dim3(64, 4), 0, c->stream, (cd*)nullptr, (cd*)nullptr, c->Ph, (const double*)F->Aq, F->bq, sdt, s32, F->seed,
+                       (const cd*)nullptr, 0, (const double*)nullptr, (const double*)nullptr, (double*)nullptr, reinterpret_cast<cd*>(tmp));
+  if (stream == 1 && F->bphi.nrows > 0)
+    hipLaunchKernelGGL((k_force_full<double, false>), F->gphi, dim3(64, 4), 0, c->stream, (cd*)nullptr, (const double*)F->Aphi, F->bphi, sdt, s32, 1u, F->seed,
+                       (const cd*)nullptr, (const double*)nullptr, (const double*)nullptr, (double*)nullptr, reinterpret_cast<cd*>(tmp));
+  if (er == hipSuccess) er = hipGetLastError();
+  if (er == hipSuccess) er = hipMemcpyAsync(out, tmp, sizeof(cd) * n, hipMemcpyDeviceToHost, c->stream);
+  const int rc = nq_sync(c);
+  (void)hipFree(tmp);
+  if (er != hipSuccess) NQ_FAIL(c, -5, "nq_forcing_increment: %s", hipGetErrorString(er));
+  return rc;
+}
+int nq_forcing_state(nq_ctx* c, double* out3) {
+  NQ_SINGLE_RANK(c, "nq_forcing_state");
+  NqForcing* F = c->fc;
+  if (!F) NQ_FAIL(c, -4, "nq_forcing_state: no forcing attached");
+  if (!out3) return -1;
+  HIPCHK(c, hipSetDevice(c->device));
+  out3[0] = (double)F->s;
+  HIPCHK(c, hipMemcpyAsync(out3 + 1, F->work, sizeof(double) * 2, hipMemcpyDeviceToHost, c->stream));
   return nq_sync(c);
 }
 
@@ -5247,6 +5435,45 @@ int nq_any_interp(nq_any* e, void* out, const void* plane, const void* pos, int 
                      reinterpret_cast<const cd*>(pos), n, g);
   ANYCHK(e, hipGetLastError());
   return 0;
+}
+// Stochastic forcing on engine planes: plane += sqrt_dt Re(amp) xi with the generator, counters and
+// Hermitian rule of the fused contexts.  layout 0: (rows, rows/2+1) half spectrum, the q rule; 1: full (rows, rows) plane,
+// independent values of `stream`; 2: full plane, the Hermitian extension of the q rule (the reference's full-plane qh).
+// work_in (null: none) is the plane W of the work sums, read before the increment (it may be `plane` itself):
+// out2 = {sum w Re(conj(W) D), sum w |D|^2} / M^2 with the half-spectrum weights on layout 0.
+int nq_any_forcing(nq_any* e, void* plane, const void* amp, int rows, int cols, int layout, unsigned long long seed, long long s, int stream,
+                   double sqrt_dt, const void* work_in, double* out2) {
+  if (!e || !plane || !amp || rows < 2 || (rows & 1) || s < 0) return -1;
+  if (layout < 0 || layout > 2) ANYFAIL(e, -1, "nq_any_forcing: layout %d (0: half plane, 1: full plane, 2: full plane, Hermitian)", layout);
+  if (cols != (layout == 0 ? rows / 2 + 1 : rows)) ANYFAIL(e, -1, "nq_any_forcing: %d columns for layout %d of %d rows", cols, layout, rows);
+  if (stream != 0 && stream != 1) ANYFAIL(e, -1, "nq_any_forcing: stream %d", stream);
+  if ((work_in == nullptr) != (out2 == nullptr)) ANYFAIL(e, -1, "nq_any_forcing: work_in and work_out2 go together");
+  ANYCHK(e, hipSetDevice(e->device));
+  const FcBox b = {rows, rows / 2, layout == 0 ? rows / 2 : rows / 2, rows, cols};      // the whole plane (A lives on the device)
+  const dim3 g = fc_grid(b);
+  const int np = (int)(g.x * g.y);
+  double* part = nullptr;
+  AnyScratch tmp;
+  if (out2) ANYCHK(e, tmp.get(&part, (size_t)2 * np + 2));
+  const uint32_t s32 = (uint32_t)((unsigned long long)s & 0xffffffffull);
+  cd* y = reinterpret_cast<cd*>(plane);
+  const cd *A = reinterpret_cast<const cd*>(amp), *W = reinterpret_cast<const cd*>(work_in);
+  if (layout == 0)
+    hipLaunchKernelGGL(k_force_half<cd>, g, dim3(64, 4), 0, e->stream, y, (cd*)nullptr, cols, A, b, sqrt_dt, s32, seed, W, cols, (const double*)nullptr,
+                       (const double*)nullptr, part, (cd*)nullptr);
+  else if (layout == 1)
+    hipLaunchKernelGGL((k_force_full<cd, false>), g, dim3(64, 4), 0, e->stream, y, A, b, sqrt_dt, s32, (uint32_t)stream, seed, W, (const double*)nullptr,
+                       (const double*)nullptr, part, (cd*)nullptr);
+  else
+    hipLaunchKernelGGL((k_force_full<cd, true>), g, dim3(64, 4), 0, e->stream, y, A, b, sqrt_dt, s32, 0u, seed, W, (const double*)nullptr,
+                       (const double*)nullptr, part, (cd*)nullptr);
+  ANYCHK(e, hipGetLastError());
+  if (!out2) return 0;
+  const double M = (double)rows * rows;
+  hipLaunchKernelGGL(k_force_accum, dim3(1), dim3(256), 0, e->stream, (const double*)part, np, (const double*)nullptr, 0, 1.0 / (M * M), (double*)nullptr,
+                     part + 2 * np);
+  ANYCHK(e, hipMemcpyAsync(out2, part + 2 * np, sizeof(double) * 2, hipMemcpyDeviceToHost, e->stream));
+  return nq_any_sync(e);
 }
 // ETDRK4 planes of the linear operator c(l, k) on the whole (n, cols) plane, no filter folded in (the any-size path multiplies by
 // `filtr` as the reference does): eq as k_etdrk4_coeffs (0 q Kernel family, 1 phi, 2 QGModel's q, 3 its passive scalar);
