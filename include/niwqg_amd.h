@@ -305,6 +305,30 @@ int nq_forcing_apply(nq_ctx* ctx);
 int nq_forcing_increment(nq_ctx* ctx, int stream, long long s, double* out_cplx);
 int nq_forcing_state(nq_ctx* ctx, double* out3);
 
+/* Low-mode time series recorded in the step and their frequency - wavenumber spectra, single-rank contexts
+ * only (slab contexts refuse every call with -4).  A recorder keeps the block |i|, |j| <= kmax (1 <= kmax < nx/2) of the spectral
+ * state in a device ring of `length` records, [field][record][row][col] complex128: rows j = 0..kmax, -kmax..-1 (fftfreq order);
+ * columns the same for field 0 (phi-hat, full plane), i = 0..kmax for fields 1 (q-hat as the device holds it; the copy X+ of a
+ * dual-q context) and 2 (psi-hat as the model's ph: on the Kernel family column 0 takes its Hermitian part in l).  CoupledModel
+ * and UnCoupledModel take all three, QGModel 1 and 2, YBJModel 0 (-1 otherwise).  attach writes record 0 from the current state;
+ * after that every `every`-th step of a step call since attach ends with one more record (after the forcing, one launch for all
+ * fields, on the context's stream).  One recorder per context (-4 while one is attached).  Every allocation is counted by
+ * nq_device_bytes and freed by detach; an allocation that fails is an error (-5) that leaves the context as it was.
+ * info3 = {records written, records held, steps since attach}.  series: the held records, oldest first, steps (held) and
+ * out_cplx (held x rows x cols complex); either may be NULL.
+ * spectrum: with the T >= 2 held records x_n, a real finite window w_n (T values) and X_p = sum_n w_n x_n e^{+2 pi i p n / T}
+ * (T ifft: a mode evolving as e^{-i omega t} appears at +omega), out (T, nb) with nb = shell(kmax, kmax) + 1, row p = FFT bin p:
+ *   field 0:  1/2 sum_{block, shell b} |X_p|^2 / (M^2 T sum w^2),  M = nx ny
+ *   field 1:  1/2 [sum_{col 0} |X_p|^2 + sum_{cols 1..kmax} (|X_p|^2 + |X_-p|^2)] / (M^2 T sum w^2)
+ *   field 2:  as field 1 with kappa^2 = dk^2 (i^2 + j^2) inside the sums
+ * demean: each mode's time mean is subtracted before the window.  Window, transform along the record axis (the any-length
+ * column transform of the any-size engine) and binning run on the device; the binning is deterministic (no atomics).       */
+int nq_freq_attach(nq_ctx* ctx, int kmax, int every, int length, int nfields, const int* fields);
+int nq_freq_detach(nq_ctx* ctx);
+int nq_freq_info(nq_ctx* ctx, long long* info3);
+int nq_freq_series(nq_ctx* ctx, int field, long long* steps, double* out_cplx);
+int nq_freq_spectrum(nq_ctx* ctx, int field, const double* window, int demean, double dk, int nb, double* out);
+
 /* copy of one ETDRK4 coefficient plane (0:E 1:Eh 2:Q 3:f0 4:fab 5:fc) of equation eq (0: q, (nx, nx/2+1) complex;
  * 1: phi, (nx, nx) complex; 2: QGModel's passive scalar, (nx, nx/2+1)), without the filter folded in; values as the
  * reference's expch, expch_h, Qh, f0, fab, fc (Kernel.py:417-454, QGModel.py:426-461).                           */
@@ -546,6 +570,14 @@ int nq_any_interp(nq_any* eng, void* out, const void* plane, const void* pos, in
  * work_out2 = {sum w Re(conj(work_in) D), sum w |D|^2} / M^2, w the half-spectrum weights on layout 0, else 1.               */
 int nq_any_forcing(nq_any* eng, void* plane, const void* amp_plane, int rows, int cols, int layout, unsigned long long seed, long long s,
                    int stream, double sqrt_dt, const void* work_in_plane, double* work_out2);
+/* The recorder on engine planes (nq_freq_attach above: the same kernels).  record: one record of nf planes into slot `slot` of their
+ * rings, one launch; planes[f] is (rows, cols[f]); full[f] != 0: the block takes columns 0..kmax and -kmax..-1 of a full plane
+ * (cols[f] == rows), else columns 0..kmax; rings[f]: [length][2 kmax + 1][2 kmax + 1 or kmax + 1] complex.  spectrum: the table of
+ * the T records of one ring, the oldest in slot `first`; full / kappa: 1, 0 (phi), 0, 0 (q), 0, 1 (psi); out (T, nb).          */
+int nq_any_freq_record(nq_any* eng, int nf, void* const* rings, const void* const* planes, const int* cols, const int* full, int rows, int kmax,
+                       int length, int slot);
+int nq_any_freq_spectrum(nq_any* eng, const void* ring, int rows, int kmax, int full, int kappa, int length, int first, int T,
+                         const double* window, int demean, double dk, int nb, double* out);
 /* E = exp(c dt), Eh = exp(c dt / 2), Q, f0, fab, fc of the linear operator c(l, k) on a (n, cols) plane, WITHOUT the filter
  * (Kernel.py:417-454, QGModel.py:426-466); eq 0: q of the Kernel family, 1: phi, 2: QGModel's q (beta term), 3: its passive
  * scalar.  The entries within delta of the contour are listed (near_*; at most cap) for the host to recompute exactly as the

@@ -793,6 +793,9 @@ class KernelFamily(object):
             F._after_step()
         if P is not None:
             P._after_step()
+        R = self.__dict__.get("_frequency")          # low-mode recorder (niwqg_amd/frequency.py): the record of this step
+        if R is not None:
+            R._after_step()
 
     def _step_etdrk4_state(self):
         """ref: niwqg/Kernel.py:307-397"""
@@ -1152,6 +1155,9 @@ class QGFamily(object):
             F._after_step()
         if P is not None:
             P._after_step()
+        R = self.__dict__.get("_frequency")          # low-mode recorder (niwqg_amd/frequency.py): the record of this step
+        if R is not None:
+            R._after_step()
 
     def _step_etdrk4_state(self):
         """ref: niwqg/QGModel.py:328-407"""

@@ -20,7 +20,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # NIWQG_AMD_LIB: another build of the same sources (A/B experiments with compile-time knobs, tools/); default: the in-tree library
 LIB_PATH = os.environ.get("NIWQG_AMD_LIB") or os.path.join(HERE, "libniwqg_amd.so")
 SRC = os.path.join(HERE, "csrc", "nq_lib.hip")
-HEADERS = [os.path.join(HERE, "csrc", h) for h in ("nq_fft.hpp", "nq_generic.hpp", "nq_step.hpp", "nq_anysize.hpp", "nq_particles.hpp", "nq_forcing.hpp", "nq_hist.hpp")] + [
+HEADERS = [os.path.join(HERE, "csrc", h) for h in ("nq_fft.hpp", "nq_generic.hpp", "nq_step.hpp", "nq_anysize.hpp", "nq_particles.hpp", "nq_forcing.hpp", "nq_hist.hpp", "nq_freq.hpp")] + [
     os.path.join(os.path.dirname(HERE), "include", "niwqg_amd.h")]
 
 COUPLED, UNCOUPLED, QG, YBJ = 0, 1, 2, 3
@@ -33,6 +33,7 @@ EXPORTS = ["nq_create", "nq_destroy", "nq_last_error", "nq_set_q", "nq_set_c", "
            "nq_irfft2", "nq_jacobian_psi_q", "nq_jacobian_psi_c", "nq_jacobian_psi_phi", "nq_jacobian_phic_phi", "nq_products_uq_vq", "nq_refraction", "nq_field_doubles", "nq_get_coeff", "nq_coeff_near_contour", "nq_coeff_patch", "nq_diagnostics", "nq_spectrum_shells", "nq_diagnostics_binned", "nq_transfer_binned",
            "nq_particles_attach", "nq_particles_detach", "nq_particles_get", "nq_particles_sample", "nq_particles_records",
            "nq_forcing_attach", "nq_forcing_detach", "nq_forcing_apply", "nq_forcing_increment", "nq_forcing_state", "nq_any_forcing",
+           "nq_freq_attach", "nq_freq_detach", "nq_freq_info", "nq_freq_series", "nq_freq_spectrum", "nq_any_freq_record", "nq_any_freq_spectrum",
            "nq_stream_copy_gbs", "nq_timer_start", "nq_timer_stop", "nq_event_record", "nq_event_elapsed", "nq_profile_enable", "nq_profile_read", "nq_profile_read_all", "nq_group_elems", "nq_overlap_grid", "nq_overlap_default_cus", "nq_overlap_info", "nq_create_slab",
            "nq_slab_info", "nq_group_buffers", "nq_upload_spectral", "nq_download_spectral", "nq_phase",
            "nq_reduce_buffer", "nq_reduce_read", "nq_reduce_write", "nq_device_bytes", "nq_stream",
@@ -141,6 +142,15 @@ def lib():
     L.nq_forcing_state.argtypes = [vp, dp]
     L.nq_any_forcing.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_longlong, ctypes.c_int,
                                  ctypes.c_double, vp, dp]
+    L.nq_freq_attach.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ip]
+    L.nq_freq_detach.argtypes = [vp]
+    L.nq_freq_info.argtypes = [vp, llp]
+    L.nq_freq_series.argtypes = [vp, ctypes.c_int, llp, dp]
+    L.nq_freq_spectrum.argtypes = [vp, ctypes.c_int, dp, ctypes.c_int, ctypes.c_double, ctypes.c_int, dp]
+    L.nq_any_freq_record.argtypes = [vp, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(vp), ip, ip, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_int]
+    L.nq_any_freq_spectrum.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp,
+                                       ctypes.c_int, ctypes.c_double, ctypes.c_int, dp]
     L.nq_get_coeff.argtypes = [vp, ctypes.c_int, ctypes.c_int, dp]
     L.nq_coeff_near_contour.argtypes = [vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     L.nq_coeff_patch.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, dp]
@@ -608,3 +618,28 @@ class Context:
         out = np.empty(3)
         self._chk(self.L.nq_forcing_state(self.h, _dptr(out)), "nq_forcing_state")
         return int(out[0]), float(out[1]), float(out[2])
+
+    # ---- low-mode time series and their frequency spectra (include/niwqg_amd.h: nq_freq_*; niwqg_amd/frequency.py) ---------------
+    def freq_attach(self, kmax, every, length, fields):
+        f = (ctypes.c_int * len(fields))(*fields)
+        self._chk(self.L.nq_freq_attach(self.h, int(kmax), int(every), int(length), len(fields), f), "nq_freq_attach")
+
+    def freq_detach(self):
+        self._chk(self.L.nq_freq_detach(self.h), "nq_freq_detach")
+
+    def freq_info(self):
+        out = (ctypes.c_longlong * 3)()
+        self._chk(self.L.nq_freq_info(self.h, out), "nq_freq_info")
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def freq_series(self, field, held, rows, cols):
+        steps = (ctypes.c_longlong * max(held, 1))()
+        out = np.empty((held, rows, cols), np.complex128)
+        self._chk(self.L.nq_freq_series(self.h, int(field), steps, _dptr(out.view(np.float64))), "nq_freq_series")
+        return np.array(steps[:held], np.int64), out
+
+    def freq_spectrum(self, field, window, demean, dk, nb):
+        w = np.ascontiguousarray(window, np.float64)
+        out = np.empty((len(w), nb))
+        self._chk(self.L.nq_freq_spectrum(self.h, int(field), _dptr(w), int(bool(demean)), float(dk), int(nb), _dptr(out)), "nq_freq_spectrum")
+        return out

@@ -186,9 +186,11 @@ struct nq_ctx {
   struct NqParticles* pt = nullptr;   // Lagrangian particles (nq_particles_attach): null when none
   double pt_L[2] = {0.0, 0.0};       // their domain, Lx and Ly
   struct NqForcing* fc = nullptr;     // stochastic forcing (nq_forcing_attach): null when none
+  struct NqFreq* fq = nullptr;        // low-mode time-series recorder (nq_freq_attach): null when none
 };
 static void pt_release(nq_ctx* c);
 static void fc_release(nq_ctx* c);
+static void fq_release(nq_ctx* c);
 
 // Device arrays start at staggered offsets inside their allocations.  hipMalloc hands out large blocks at addresses that
 // differ by multiples of 2 MiB (the 256 MiB planes: by exact multiples of their size), so element idx of every state,
@@ -2634,6 +2636,7 @@ int nq_destroy(nq_ctx* c) {
   if (c->stream) hipStreamSynchronize(c->stream);
   pt_release(c);
   fc_release(c);
+  fq_release(c);
   for (void* p : c->allocs) hipFree(p);
   for (auto& pt : c->patch) { (void)hipFree(pt.l); (void)hipFree(pt.k); (void)hipFree(pt.v); }
   for (hipEvent_t e : c->prof_ev) hipEventDestroy(e);
@@ -2881,6 +2884,7 @@ int nq_refresh_grad_phi(nq_ctx* c) {
 static void pt_before_step(nq_ctx* c);
 static int pt_after_step(nq_ctx* c);
 static int fc_apply(nq_ctx* c);
+static int fq_after_step(nq_ctx* c);
 int nq_step(nq_ctx* c, int nsteps) {
   if (!c) return -1;
   NQ_SINGLE_RANK(c, "nq_step");
@@ -2896,6 +2900,10 @@ int nq_step(nq_ctx* c, int nsteps) {
     }
     if (c->pt) {
       const int rc = pt_after_step(c);
+      if (rc) return rc;
+    }
+    if (c->fq) {                       // the record of this step: the forced, re-inverted state
+      const int rc = fq_after_step(c);
       if (rc) return rc;
     }
   }
@@ -5536,6 +5544,280 @@ int nq_any_etdrk4_patch(nq_any* e, void* const* out6, int cols, int count, const
                      (const double*)nullptr, reinterpret_cast<cd*>(out6[2]), reinterpret_cast<cd*>(out6[3]), reinterpret_cast<cd*>(out6[4]), reinterpret_cast<cd*>(out6[5]), 0);
   ANYCHK(e, hipStreamSynchronize(e->stream));
   return 0;
+}
+
+}  // extern "C"
+
+// ==================================================================================================================
+// Low-mode time series recorded in the step, frequency - wavenumber spectra on the device (DESIGN.md section 5j;
+// kernels: csrc/nq_freq.hpp, included here because k_fq_bin walks the shells with shell_run above)
+// ==================================================================================================================
+#include "nq_freq.hpp"
+
+struct NqFreq {
+  int K = 0, every = 1, length = 0, nf = 0;
+  int field[FQ_NFIELDS] = {0, 0, 0}, ncols[FQ_NFIELDS] = {0, 0, 0};
+  cd* ring[FQ_NFIELDS] = {nullptr, nullptr, nullptr};     // [record][row][col] of each attached field
+  std::vector<long long> ring_step;                        // steps since attach of each slot
+  long long count = 0, steps = 0;                          // records written, steps since attach
+  cd* work = nullptr;                                      // (length, modes of the widest field): allocated by the first spectrum
+  double *win = nullptr, *tab = nullptr;                   // window (length), table (length, nb)
+  nq_any* eng = nullptr;                                   // the any-length transform of the record axis runs on an engine of its own
+  long long eng_bytes = 0;
+  std::vector<void*> mem;
+  long long bytes = 0;
+};
+static int fq_alloc_raw(nq_ctx* c, void** out, size_t bytes, const char* what) {
+  NqFreq* F = c->fq;
+  void* p = nullptr;
+  if (hipMalloc(&p, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    NQ_FAIL(c, -5, "%s: cannot allocate %zu bytes of device memory", what, bytes);
+  }
+  F->mem.push_back(p);
+  F->bytes += (long long)bytes;
+  c->bytes += (long long)bytes;
+  *out = p;
+  return 0;
+}
+static void fq_release(nq_ctx* c) {
+  NqFreq* F = c->fq;
+  if (!F) return;
+  (void)hipSetDevice(c->device);
+  (void)hipStreamSynchronize(c->stream);
+  if (F->eng) (void)nq_any_destroy(F->eng);
+  for (void* p : F->mem) (void)hipFree(p);
+  c->bytes -= F->bytes + F->eng_bytes;
+  delete F;
+  c->fq = nullptr;
+}
+// one record of every attached field from the buffers that hold the current state (what nq_get_field reads), one launch
+static int fq_record(nq_ctx* c) {
+  NqFreq* F = c->fq;
+  const int slot = (int)(F->count % F->length), R = 2 * F->K + 1;
+  FqRecord a = {};
+  int maxc = 0;
+  for (int f = 0; f < F->nf; ++f) {
+    const int id = F->field[f];
+    a.src[f] = id == FQ_PHI ? c->w.y[c->w.cur] : (id == FQ_Q ? c->q.y[c->q.cur] : c->ph);
+    a.pitch[f] = id == FQ_PHI ? c->N : c->Ph;
+    a.ncols[f] = F->ncols[f];
+    a.proj[f] = (id == FQ_PSI && c->kernel_family) ? 1 : 0;
+    a.dst[f] = F->ring[f] + (size_t)slot * R * F->ncols[f];
+    if (F->ncols[f] > maxc) maxc = F->ncols[f];
+  }
+  hipLaunchKernelGGL(k_fq_record, dim3((maxc + 63) / 64, (R + 3) / 4, F->nf), dim3(64, 4), 0, c->stream, a, c->N, F->K);
+  HIPCHK(c, hipGetLastError());
+  F->ring_step[slot] = F->steps;
+  ++F->count;
+  return 0;
+}
+static int fq_after_step(nq_ctx* c) {
+  NqFreq* F = c->fq;
+  ++F->steps;
+  if (F->steps % F->every == 0) return fq_record(c);
+  return 0;
+}
+static int fq_find(const NqFreq* F, int field) {
+  for (int f = 0; f < F->nf; ++f)
+    if (F->field[f] == field) return f;
+  return -1;
+}
+// The spectrum pass on the engine's stream: window -> transform along the record axis -> bin.  ring: [length][2K+1][ncols];
+// work: T x modes; dwin: T; dtab: T x nb (device); out: T x nb (host), row p = FFT bin p (omega_p = 2 pi fftfreq(T, Delta)[p]).
+static int fq_spectrum_run(nq_any* e, const cd* ring, int N, int K, int ncols, int full, int kappa, int length, int first, int T,
+                           const double* window, int demean, double dk, int nb, cd* work, double* dwin, double* dtab, double* out) {
+  const int nm = (2 * K + 1) * ncols;
+  double sw2 = 0.0;
+  for (int n = 0; n < T; ++n) sw2 += window[n] * window[n];
+  if (!(sw2 > 0.0)) ANYFAIL(e, -1, "frequency spectrum: the window is zero everywhere");
+  const double M = (double)N * N, scale = 0.5 / (M * M * (double)T * sw2);
+  ANYCHK(e, hipMemcpyAsync(dwin, window, sizeof(double) * T, hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(k_fq_window, dim3((nm + 255) / 256), dim3(256), 0, e->stream, ring, work, (const double*)dwin, nm, length, first, T, demean ? 1 : 0);
+  ANYCHK(e, hipGetLastError());
+  const int rc = nq_any_fft(e, work, work, T, nm, 0, 0);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_fq_bin, dim3(nb, T), dim3(256), 0, e->stream, (const cd*)work, T, K, ncols, full, kappa, dk * dk, scale, nb, dtab);
+  ANYCHK(e, hipGetLastError());
+  ANYCHK(e, hipMemcpyAsync(out, dtab, sizeof(double) * (size_t)T * nb, hipMemcpyDeviceToHost, e->stream));
+  return nq_any_sync(e);
+}
+
+extern "C" {
+
+int nq_freq_attach(nq_ctx* c, int kmax, int every, int length, int nfields, const int* fields) {
+  NQ_SINGLE_RANK(c, "nq_freq_attach");
+  if (c->fq) NQ_FAIL(c, -4, "nq_freq_attach: a recorder is attached already (nq_freq_detach first)");
+  if (kmax < 1 || kmax >= c->N / 2) NQ_FAIL(c, -1, "nq_freq_attach: kmax = %d (1 <= kmax < nx/2 = %d)", kmax, c->N / 2);
+  if (every < 1 || length < 2) NQ_FAIL(c, -1, "nq_freq_attach: every = %d (>= 1), length = %d (>= 2)", every, length);
+  if (nfields < 1 || nfields > FQ_NFIELDS || !fields) NQ_FAIL(c, -1, "nq_freq_attach: %d fields", nfields);
+  for (int f = 0; f < nfields; ++f) {
+    if (fields[f] < 0 || fields[f] >= FQ_NFIELDS) NQ_FAIL(c, -1, "nq_freq_attach: field %d (0: phi, 1: q, 2: psi)", fields[f]);
+    for (int g = 0; g < f; ++g)
+      if (fields[g] == fields[f]) NQ_FAIL(c, -1, "nq_freq_attach: field %d given twice", fields[f]);
+    if (fields[f] == FQ_PHI && !c->kernel_family) NQ_FAIL(c, -1, "nq_freq_attach: QGModel has no wave field (q and psi only)");
+    if (fields[f] != FQ_PHI && c->ybj) NQ_FAIL(c, -1, "nq_freq_attach: YBJModel's psi is steady (phi only)");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  c->fq = new NqFreq();
+  NqFreq* F = c->fq;
+  F->K = kmax;
+  F->every = every;
+  F->length = length;
+  F->nf = nfields;
+  F->ring_step.assign((size_t)length, 0);
+  const size_t R = 2 * (size_t)kmax + 1;
+  int rc = 0;
+  for (int f = 0; f < nfields && !rc; ++f) {
+    F->field[f] = fields[f];
+    F->ncols[f] = fields[f] == FQ_PHI ? 2 * kmax + 1 : kmax + 1;
+    rc = fq_alloc_raw(c, reinterpret_cast<void**>(&F->ring[f]), sizeof(cd) * (size_t)length * R * F->ncols[f], "nq_freq_attach");
+  }
+  if (!rc) rc = fq_record(c);                     // record 0: the state at attach
+  if (!rc) rc = nq_sync(c);
+  if (rc) {
+    const std::string e = c->err;
+    fq_release(c);
+    NQ_FAIL(c, rc, "%s", e.c_str());
+  }
+  return 0;
+}
+int nq_freq_detach(nq_ctx* c) {
+  NQ_SINGLE_RANK(c, "nq_freq_detach");
+  if (!c->fq) NQ_FAIL(c, -4, "nq_freq_detach: no recorder attached");
+  fq_release(c);
+  return 0;
+}
+int nq_freq_info(nq_ctx* c, long long* info3) {
+  NQ_SINGLE_RANK(c, "nq_freq_info");
+  NqFreq* F = c->fq;
+  if (!F) NQ_FAIL(c, -4, "nq_freq_info: no recorder attached");
+  if (!info3) return -1;
+  info3[0] = F->count;
+  info3[1] = F->count < F->length ? F->count : F->length;
+  info3[2] = F->steps;
+  return 0;
+}
+int nq_freq_series(nq_ctx* c, int field, long long* steps, double* out_cplx) {
+  NQ_SINGLE_RANK(c, "nq_freq_series");
+  NqFreq* F = c->fq;
+  if (!F) NQ_FAIL(c, -4, "nq_freq_series: no recorder attached");
+  const int f = fq_find(F, field);
+  if (f < 0) NQ_FAIL(c, -1, "nq_freq_series: field %d is not recorded", field);
+  HIPCHK(c, hipSetDevice(c->device));
+  const long long m = F->count < F->length ? F->count : F->length;
+  const size_t rec = (size_t)(2 * F->K + 1) * F->ncols[f];
+  for (long long r = 0; r < m; ++r) {
+    const int slot = (int)((F->count - m + r) % F->length);
+    if (steps) steps[r] = F->ring_step[slot];
+    if (out_cplx)
+      HIPCHK(c, hipMemcpyAsync(out_cplx + 2 * (size_t)r * rec, F->ring[f] + (size_t)slot * rec, sizeof(cd) * rec, hipMemcpyDeviceToHost, c->stream));
+  }
+  return nq_sync(c);
+}
+int nq_freq_spectrum(nq_ctx* c, int field, const double* window, int demean, double dk, int nb, double* out) {
+  NQ_SINGLE_RANK(c, "nq_freq_spectrum");
+  NqFreq* F = c->fq;
+  if (!F) NQ_FAIL(c, -4, "nq_freq_spectrum: no recorder attached");
+  if (!window || !out) return -1;
+  const int f = fq_find(F, field);
+  if (f < 0) NQ_FAIL(c, -1, "nq_freq_spectrum: field %d is not recorded", field);
+  const int T = (int)(F->count < F->length ? F->count : F->length);
+  if (T < 2) NQ_FAIL(c, -1, "nq_freq_spectrum: %d record held (at least 2)", T);
+  if (nb != nq_shell_of(F->K, F->K) + 1) NQ_FAIL(c, -1, "nq_freq_spectrum: nb = %d, the block has %d shells", nb, nq_shell_of(F->K, F->K) + 1);
+  for (int n = 0; n < T; ++n)
+    if (!std::isfinite(window[n])) NQ_FAIL(c, -1, "nq_freq_spectrum: the window is not finite at record %d", n);
+  if (!std::isfinite(dk) || !(dk > 0.0)) NQ_FAIL(c, -1, "nq_freq_spectrum: dk = %g", dk);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!F->work) {                                   // first call: the work plane of a full ring of the widest field, window, table
+    int maxc = 0;
+    for (int g = 0; g < F->nf; ++g) maxc = F->ncols[g] > maxc ? F->ncols[g] : maxc;
+    const size_t have = F->mem.size();
+    const long long before = F->bytes;
+    int rc = fq_alloc_raw(c, reinterpret_cast<void**>(&F->work), sizeof(cd) * (size_t)F->length * (2 * (size_t)F->K + 1) * maxc, "nq_freq_spectrum");
+    if (!rc) rc = fq_alloc_raw(c, reinterpret_cast<void**>(&F->win), sizeof(double) * (size_t)F->length, "nq_freq_spectrum");
+    if (!rc) rc = fq_alloc_raw(c, reinterpret_cast<void**>(&F->tab), sizeof(double) * (size_t)F->length * nb, "nq_freq_spectrum");
+    if (!rc && !F->eng) {
+      rc = nq_any_create(c->device, &F->eng);
+      if (rc) c->err = g_last_error;
+    }
+    if (rc) {                                       // the recorder stays as it was
+      while (F->mem.size() > have) {
+        (void)hipFree(F->mem.back());
+        F->mem.pop_back();
+      }
+      c->bytes -= F->bytes - before;
+      F->bytes = before;
+      F->work = nullptr;
+      F->win = F->tab = nullptr;
+      return rc;
+    }
+  }
+  int rc = nq_sync(c);                              // every record queued on the context's stream is in the ring
+  if (rc) return rc;
+  const int first = (int)((F->count - T) % F->length);
+  rc = fq_spectrum_run(F->eng, F->ring[f], c->N, F->K, F->ncols[f], field == FQ_PHI ? 1 : 0, field == FQ_PSI ? 1 : 0, F->length, first, T, window,
+                       demean, dk, nb, F->work, F->win, F->tab, out);
+  const long long eb = nq_any_device_bytes(F->eng);      // the engine's work rows count as the recorder's
+  c->bytes += eb - F->eng_bytes;
+  F->eng_bytes = eb;
+  if (rc) NQ_FAIL(c, rc, "nq_freq_spectrum: %s", nq_any_last_error(F->eng));
+  return 0;
+}
+
+// The same on engine planes (the any-size path steps from Python and calls this after its own step): one record of nf planes
+// into slot `slot` of their rings, ONE launch.  planes[f]: (rows, cols[f]) with cols[f] >= K + 1; full[f] != 0: the block takes
+// columns 0..K and cols - K..cols - 1 (a full plane, cols[f] == rows), else columns 0..K (a half spectrum, or the first columns
+// of the reference's full-plane q-hat).  rings[f]: [length][2K + 1][2K + 1 or K + 1] complex.
+int nq_any_freq_record(nq_any* e, int nf, void* const* rings, const void* const* planes, const int* cols, const int* full, int rows, int K,
+                       int length, int slot) {
+  if (!e || !rings || !planes || !cols || !full) return -1;
+  if (nf < 1 || nf > FQ_NFIELDS) ANYFAIL(e, -1, "nq_any_freq_record: %d fields", nf);
+  if (rows < 4 || (rows & 1) || K < 1 || K >= rows / 2) ANYFAIL(e, -1, "nq_any_freq_record: kmax = %d on %d rows (1 <= kmax < rows/2)", K, rows);
+  if (length < 2 || slot < 0 || slot >= length) ANYFAIL(e, -1, "nq_any_freq_record: slot %d of %d", slot, length);
+  ANYCHK(e, hipSetDevice(e->device));
+  FqRecord a = {};
+  const int R = 2 * K + 1;
+  int maxc = 0;
+  for (int f = 0; f < nf; ++f) {
+    if (!rings[f] || !planes[f]) return -1;
+    if (full[f] ? cols[f] != rows : cols[f] < K + 1) ANYFAIL(e, -1, "nq_any_freq_record: %d columns for a %s block of kmax %d", cols[f], full[f] ? "full" : "half", K);
+    a.src[f] = reinterpret_cast<const cd*>(planes[f]);
+    a.pitch[f] = cols[f];
+    a.ncols[f] = full[f] ? R : K + 1;
+    a.proj[f] = 0;
+    a.dst[f] = reinterpret_cast<cd*>(rings[f]) + (size_t)slot * R * a.ncols[f];
+    if (a.ncols[f] > maxc) maxc = a.ncols[f];
+  }
+  hipLaunchKernelGGL(k_fq_record, dim3((maxc + 63) / 64, (R + 3) / 4, nf), dim3(64, 4), 0, e->stream, a, rows, K);
+  ANYCHK(e, hipGetLastError());
+  return 0;
+}
+// The spectrum pass of nq_freq_spectrum on an engine-owned ring: T records, the oldest in slot `first`; full / kappa as the field
+// (phi: 1, 0; q: 0, 0; psi: 0, 1); out: (T, nb), row p = FFT bin p.  The work plane lives for the call.
+int nq_any_freq_spectrum(nq_any* e, const void* ring, int rows, int K, int full, int kappa, int length, int first, int T, const double* window,
+                         int demean, double dk, int nb, double* out) {
+  if (!e || !ring || !window || !out) return -1;
+  if (rows < 4 || (rows & 1) || K < 1 || K >= rows / 2) ANYFAIL(e, -1, "nq_any_freq_spectrum: kmax = %d on %d rows (1 <= kmax < rows/2)", K, rows);
+  if (length < 2 || T < 2 || T > length || first < 0 || first >= length) ANYFAIL(e, -1, "nq_any_freq_spectrum: %d records from slot %d of %d", T, first, length);
+  if (nb != nq_shell_of(K, K) + 1) ANYFAIL(e, -1, "nq_any_freq_spectrum: nb = %d, the block has %d shells", nb, nq_shell_of(K, K) + 1);
+  for (int n = 0; n < T; ++n)
+    if (!std::isfinite(window[n])) ANYFAIL(e, -1, "nq_any_freq_spectrum: the window is not finite at record %d", n);
+  if (!std::isfinite(dk) || !(dk > 0.0)) ANYFAIL(e, -1, "nq_any_freq_spectrum: dk = %g", dk);
+  ANYCHK(e, hipSetDevice(e->device));
+  const int ncols = full ? 2 * K + 1 : K + 1;
+  const size_t wel = (size_t)T * (2 * (size_t)K + 1) * ncols;
+  cd* work = nullptr;
+  double *dwin = nullptr, *dtab = nullptr;
+  AnyScratch tmp;
+  if (tmp.get(&work, wel) != hipSuccess) {
+    (void)hipGetLastError();
+    ANYFAIL(e, -5, "nq_any_freq_spectrum: cannot allocate %zu bytes of device memory", wel * sizeof(cd));
+  }
+  ANYCHK(e, tmp.get(&dwin, (size_t)T));
+  ANYCHK(e, tmp.get(&dtab, (size_t)T * nb));
+  return fq_spectrum_run(e, reinterpret_cast<const cd*>(ring), rows, K, ncols, full ? 1 : 0, kappa ? 1 : 0, length, first, T, window, demean, dk, nb, work,
+                         dwin, dtab, out);
 }
 
 }  // extern "C"
