@@ -12,10 +12,11 @@ from numpy import pi
 
 from . import _lib
 from .Diagnostics import add_diagnostic, increment_diagnostics
-from .Saving import (initialize_save_snapshots, save_setup, save_snapshots, save_diagnostics, flush_snapshots, flush_pending_quietly)
+from ._run import RunLoop
+from .Saving import initialize_save_snapshots, save_setup, save_snapshots
 
 
-class Model(object):
+class Model(RunLoop):
 
     def __new__(cls, *args, **kwargs):
         """grids without a fused plan: the any-size mix-in in front of the class (niwqg_amd/_anysize.py; see Kernel.Kernel.__new__)"""
@@ -274,53 +275,6 @@ class Model(object):
         increment_diagnostics(self)
         self._print_status()
         save_snapshots(self, fields=self._snapshot_fields())
-
-    def _quiet_steps(self, n_left):
-        for j in range(n_left):
-            tcb = self.tc + j
-            if (tcb % self.tdiags) == 0 or ((tcb + 1) % self.twrite) == 0:
-                return j
-            if self.save_to_disk and ((tcb + 1) % self.tsnaps) == 0:
-                return j
-        return n_left - 1
-
-    def _steps_left(self, cap):
-        t, n = self.t, 0
-        while t < self.tmax and n < cap:
-            t += self.dt
-            n += 1
-        return n
-
-    def run(self):
-        """ref: niwqg/QGModel.py:184-207"""
-        self._defer_snapshots = True              # snapshots are written while the next batch of steps runs
-        try:
-            if self.save_to_disk:
-                save_snapshots(self, fields=self._snapshot_fields())
-            while self.t < self.tmax:
-                quiet = self._quiet_steps(self._steps_left(4096))
-                if quiet > 0:
-                    self._ctx.step(quiet)
-                    flush_snapshots(self)
-                    for _ in range(quiet):
-                        self.tc += 1
-                        self.t += self.dt
-                    self._after_steps()
-                self._step_forward()
-            flush_snapshots(self)
-            if self.save_to_disk:
-                save_diagnostics(self)
-        finally:
-            self._defer_snapshots = False
-            flush_pending_quietly(self)      # (a failure in here must not mask the exception that is already on its way)
-
-    def run_with_snapshots(self, tsnapstart=0., tsnapint=432000.):
-        tsnapints = np.ceil(tsnapint / self.dt)
-        while self.t < self.tmax:
-            self._step_forward()
-            if self.t >= tsnapstart and (self.tc % tsnapints) == 0:
-                yield self.t
-        return
 
     def _print_status(self):
         """ref: niwqg/QGModel.py:554-578"""

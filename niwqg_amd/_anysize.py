@@ -16,7 +16,7 @@ import ctypes
 
 import numpy as np
 
-from . import _etdrk4, _lib
+from . import _attach, _etdrk4, _lib
 
 (EW_COPY, EW_MUL, EW_MULCONJ, EW_AXPBY, EW_AXPBYPCZ, EW_REAL, EW_ABS2, EW_SCALE, EW_CONJ, EW_ADDS, EW_IMAG,
  EW_MULADD, EW_FILL) = range(13)
@@ -327,7 +327,28 @@ def _etd_final(c, y0, N0, Na, Nb, Nc, F):
 
 
 # =====================================================================================================================
-class KernelFamily(object):
+class _Stepping(object):
+    """What the two mix-ins below share: a step with its attachments, and the run loop"""
+
+    def _step_etdrk4(self):
+        """the family's own step between the attachments' hooks (particles before; forcing, particles, recorder after: the
+        order is written once, in niwqg_amd/_attach.py, as nq_step's is in csrc/nq_lib.hip)"""
+        _attach.before_step(self)
+        self._step_etdrk4_state()
+        _attach.after_step(self)
+
+    def run(self):
+        """ref: niwqg/Kernel.py:183-203, niwqg/QGModel.py:184-207 (one step per iteration: nothing to batch on this path)"""
+        from .Saving import save_snapshots, save_diagnostics
+        if self.save_to_disk:
+            save_snapshots(self, fields=self._snapshot_fields())
+        while self.t < self.tmax:
+            self._step_forward()
+        if self.save_to_disk:
+            save_diagnostics(self)
+
+
+class KernelFamily(_Stepping):
     """Mix-in over niwqg_amd.Kernel.Kernel (CoupledModel / UnCoupledModel / YBJModel) for grids without a fused plan: every
     method that touches the device is restated on planes, in the reference's own order of operations."""
     _tick_snapshot = None            # (the literal sequence leaves the reference's own leftovers: nothing to keep at a tick)
@@ -783,20 +804,6 @@ class KernelFamily(object):
         d["phih"] = _etd_final(cw, y0, N0, Na, Nb, Nc, F)
         d["phi"] = self._ifft(d["phih"])
 
-    def _step_etdrk4(self):
-        P = self.__dict__.get("_particles")          # Lagrangian particles (niwqg_amd/particles.py): U0 before, RK4 after
-        if P is not None:
-            P._before_step()
-        self._step_etdrk4_state()
-        F = self.__dict__.get("_forcing")            # stochastic forcing (niwqg_amd/forcing.py): increment, then the end of a step again
-        if F is not None:
-            F._after_step()
-        if P is not None:
-            P._after_step()
-        R = self.__dict__.get("_frequency")          # low-mode recorder (niwqg_amd/frequency.py): the record of this step
-        if R is not None:
-            R._after_step()
-
     def _step_etdrk4_state(self):
         """ref: niwqg/Kernel.py:307-397"""
         if self.model_id == _lib.YBJ:
@@ -845,19 +852,9 @@ class KernelFamily(object):
         self._to_physical()
         self._dirty()
 
-    def run(self):
-        """ref: niwqg/Kernel.py:183-203 (one step per iteration: nothing to batch on this path)"""
-        from .Saving import save_snapshots, save_diagnostics
-        if self.save_to_disk:
-            save_snapshots(self, fields=['t', 'q', 'phi'])
-        while self.t < self.tmax:
-            self._step_forward()
-        if self.save_to_disk:
-            save_diagnostics(self)
-
 
 # =====================================================================================================================
-class QGFamily(object):
+class QGFamily(_Stepping):
     """Mix-in over niwqg_amd.QGModel.Model for grids without a fused plan (ref: niwqg/QGModel.py): spectral planes have the
     reference's (ny, nx/2+1) shape, ``fft`` / ``ifft`` numpy.fft.rfft2 / irfft2 semantics built from the engine's c2c transforms
     (forward: both axes on the full plane, first nx/2+1 columns kept; inverse: y transform on the half plane, Hermitian extension in
@@ -1145,20 +1142,6 @@ class QGFamily(object):
         return (2 * self.nu4c * lap2c.dot(d["lapc"]) / self.M - 2 * self.nu * d["lapc"].sumabs2() / self.M
                 - 2 * self.muc * self.gradC2)
 
-    def _step_etdrk4(self):
-        P = self.__dict__.get("_particles")          # Lagrangian particles (niwqg_amd/particles.py): U0 before, RK4 after
-        if P is not None:
-            P._before_step()
-        self._step_etdrk4_state()
-        F = self.__dict__.get("_forcing")            # stochastic forcing (niwqg_amd/forcing.py): increment, then the end of a step again
-        if F is not None:
-            F._after_step()
-        if P is not None:
-            P._after_step()
-        R = self.__dict__.get("_frequency")          # low-mode recorder (niwqg_amd/frequency.py): the record of this step
-        if R is not None:
-            R._after_step()
-
     def _step_etdrk4_state(self):
         """ref: niwqg/QGModel.py:328-407"""
         d, c, F = self._d, self._coef_q, self._K["F"]
@@ -1209,16 +1192,6 @@ class QGFamily(object):
         k4 = self._calc_ep_psi()
         self.Ke += self.dt * (k1 + 2 * (k2 + k3) + k4) / 6.
         self._dirty()
-
-    def run(self):
-        """ref: niwqg/QGModel.py:184-207"""
-        from .Saving import save_snapshots, save_diagnostics
-        if self.save_to_disk:
-            save_snapshots(self, fields=self._snapshot_fields())
-        while self.t < self.tmax:
-            self._step_forward()
-        if self.save_to_disk:
-            save_diagnostics(self)
 
 
 _specialised = {}

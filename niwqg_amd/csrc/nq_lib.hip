@@ -48,6 +48,68 @@ struct EqState {           // ETDRK4 state of one equation
   cd* coef[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // E, Eh, Q, f0, fab, fc (filter folded in)
 };                                                                       // (rows 0..N/2 only when nq_ctx::cmirror is set)
 
+// ---- step attachments: what rides on every step of a single-rank context -------------------------
+// Device memory an attachment allocated after the context was built: att_alloc adds to it, att_release gives it all back.
+struct DevMark { size_t n = 0; long long bytes = 0; };
+struct DevOwned {
+  std::vector<void*> mem;
+  long long bytes = 0;                     // what nq_device_bytes counts for this attachment
+  DevMark mark() const { return {mem.size(), bytes}; }
+  // frees what was allocated since `to` (a default DevMark: everything); returns the bytes no longer counted
+  long long rollback(DevMark to = DevMark()) {
+    for (; mem.size() > to.n; mem.pop_back()) (void)hipFree(mem.back());
+    const long long freed = bytes - to.bytes;
+    bytes = to.bytes;
+    return freed;
+  }
+};
+// Host bookkeeping of a ring of `cap` records, one after every `every`-th step (every == 0: never).
+struct RecordRing {
+  int cap = 0, every = 0;
+  long long count = 0, steps = 0;          // records written, steps since attach
+  std::vector<long long> ring_step;        // steps since attach of each slot
+  void init(int cap_, int every_) { cap = cap_; every = every_; ring_step.assign((size_t)cap_, 0); }
+  int slot() const { return (int)(count % cap); }                          // where the next record goes
+  long long held() const { return count < cap ? count : cap; }
+  int oldest(long long r) const { return (int)((count - held() + r) % cap); }   // slot of the r-th held record, oldest first
+  void wrote() { ring_step[slot()] = steps; ++count; }
+  bool tick() { ++steps; return every > 0 && steps % every == 0; }        // one step done: is a record due?
+};
+struct NqParticles : DevOwned {            // Lagrangian particles (section 5g)
+  int n = 0;
+  double *x = nullptr, *y = nullptr;       // unwrapped positions
+  cd* uv[2] = {nullptr, nullptr};          // velocity planes (u, v) interleaved, ping-pong: uv[cur] is the current state's
+  int cur = 0;
+  bool u0 = false;                         // uv[cur] is the velocity of the state the next step starts from
+  RecordRing rg;                           // records of (2 + ncol) x n doubles
+  int ncol = 0;
+  std::vector<int> names;                  // record columns (PT_*; PT_PHI takes two: real, imaginary part)
+  double* ring = nullptr;
+  double* qplane = nullptr;                // physical q (PT_Q), allocated when first needed
+  cd* phiplane = nullptr;                  // physical phi (PT_PHI), idem
+  double* samp = nullptr;                  // nq_particles_sample's output columns (4 x n), idem
+};
+struct NqForcing : DevOwned {              // stochastic forcing (section 5i)
+  double *Aq = nullptr, *Aphi = nullptr;   // amplitude planes: (N, N/2+1) and (N, N), contiguous
+  FcBox bq = {}, bphi = {};                // bounding boxes of A > 0 (nrows = 0: nothing to add)
+  dim3 gq, gphi;                           // launch grids over the boxes
+  int npq = 0, npphi = 0;                  // workgroups = work partials of each kernel
+  double *partq = nullptr, *partphi = nullptr, *work = nullptr;   // partials [workgroups][2]; work_q, work_phi
+  unsigned long long seed = 0;
+  long long s = 0;                         // index of the next forced step
+};
+struct NqFreq : DevOwned {                 // low-mode recorder (section 5j)
+  static constexpr int NF = 3;             // FQ_NFIELDS (nq_freq.hpp comes after the shell rule: checked where it is included)
+  int K = 0, nf = 0;
+  int field[NF] = {0, 0, 0}, ncols[NF] = {0, 0, 0};
+  cd* ring[NF] = {nullptr, nullptr, nullptr};     // [record][row][col] of each attached field
+  RecordRing rg;
+  cd* work = nullptr;                      // (rg.cap, modes of the widest field): allocated by the first spectrum
+  double *win = nullptr, *tab = nullptr;   // window (rg.cap), table (rg.cap, nb)
+  nq_any* eng = nullptr;                   // the any-length transform of the record axis runs on an engine of its own
+  ~NqFreq() { if (eng) (void)nq_any_destroy(eng); }
+};
+
 struct nq_ctx {
   nq_params p;
   int N = 0, S1 = 0, S2 = 0, nk = 0;
@@ -183,14 +245,11 @@ struct nq_ctx {
   bool passive = false;  // QGModel with its passive scalar: state cq, spectrum emitted through the qw slots of G3 / G0
   EqState cq;
   MArr mUc, mVc;      // niwqg.YBJModel: UnCoupled layouts, only phi is stepped (stage graph in do_step_ybj)
-  struct NqParticles* pt = nullptr;   // Lagrangian particles (nq_particles_attach): null when none
+  NqParticles* pt = nullptr;          // Lagrangian particles (nq_particles_attach): null when none
   double pt_L[2] = {0.0, 0.0};       // their domain, Lx and Ly
-  struct NqForcing* fc = nullptr;     // stochastic forcing (nq_forcing_attach): null when none
-  struct NqFreq* fq = nullptr;        // low-mode time-series recorder (nq_freq_attach): null when none
+  NqForcing* fc = nullptr;            // stochastic forcing (nq_forcing_attach): null when none
+  NqFreq* fq = nullptr;               // low-mode time-series recorder (nq_freq_attach): null when none
 };
-static void pt_release(nq_ctx* c);
-static void fc_release(nq_ctx* c);
-static void fq_release(nq_ctx* c);
 
 // Device arrays start at staggered offsets inside their allocations.  hipMalloc hands out large blocks at addresses that
 // differ by multiples of 2 MiB (the 256 MiB planes: by exact multiples of their size), so element idx of every state,
@@ -221,6 +280,49 @@ static int dev_alloc(nq_ctx* c, Tp** out, size_t count) {
     int rc_ = dev_alloc((c), &(ptr), (count));  \
     if (rc_) return rc_;                        \
   } while (0)
+
+// ---- the lifecycle the step attachments share -----------------------------------------------
+// `count` zero-filled elements owned by attachment `o` of context c, counted in both byte totals
+template <typename Tp>
+static int att_alloc(nq_ctx* c, DevOwned* o, Tp** out, size_t count, const char* what) {
+  const size_t bytes = count * sizeof(Tp);
+  void* p = nullptr;
+  if (hipMalloc(&p, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    NQ_FAIL(c, -5, "%s: cannot allocate %zu bytes of device memory", what, bytes);
+  }
+  o->mem.push_back(p);
+  o->bytes += (long long)bytes;
+  c->bytes += (long long)bytes;
+  HIPCHK(c, hipMemsetAsync(p, 0, bytes, c->stream));
+  *out = static_cast<Tp*>(p);
+  return 0;
+}
+// detach: the stream drains, the memory goes back, the slot (c->pt, c->fc, c->fq) is null again
+template <typename A>
+static void att_release(nq_ctx* c, A*& slot) {
+  if (!slot) return;
+  (void)hipSetDevice(c->device);
+  (void)hipStreamSynchronize(c->stream);
+  c->bytes -= slot->rollback();
+  delete slot;
+  slot = nullptr;
+}
+// a failed attach: nothing stays attached, the first error's text is the one reported
+template <typename A>
+static int att_fail(nq_ctx* c, A*& slot, int rc) {
+  const std::string e = c->err;
+  att_release(c, slot);
+  NQ_FAIL(c, rc, "%s", e.c_str());
+}
+// nq_step's two hooks, defined below the last attachment (the recorder, which needs the any-size engine): the one place
+// that fixes the order the attachments see a step in.  niwqg_amd/_anysize.py's _step_etdrk4 mirrors it on the any-size path.
+static void attachments_before_step(nq_ctx* c);
+static int attachments_after_step(nq_ctx* c);
+// particles: U0 is formed again from the state the next step starts from (DESIGN.md section 5g)
+static void pt_mark_stale(nq_ctx* c) {
+  if (c && c->pt) c->pt->u0 = false;
+}
 
 // ---------------------------------------------------------------------------------------------
 // ETDRK4 coefficient planes on the device (ref Kernel.py:417-454, QGModel.py:426-443).
@@ -2634,9 +2736,9 @@ int nq_destroy(nq_ctx* c) {
   if (!c) return 0;
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);
-  pt_release(c);
-  fc_release(c);
-  fq_release(c);
+  att_release(c, c->pt);
+  att_release(c, c->fc);
+  att_release(c, c->fq);
   for (void* p : c->allocs) hipFree(p);
   for (auto& pt : c->patch) { (void)hipFree(pt.l); (void)hipFree(pt.k); (void)hipFree(pt.v); }
   for (hipEvent_t e : c->prof_ev) hipEventDestroy(e);
@@ -2812,9 +2914,6 @@ int nq_event_elapsed(nq_ctx* c, int slot_a, int slot_b, float* ms) {
   return 0;
 }
 
-// particles: U0 is formed again from the state the next step starts from (DESIGN.md section 5g)
-static void pt_mark_stale(nq_ctx* c);
-
 int nq_set_q(nq_ctx* c, const double* q_host) {
   if (!c || !q_host) return -1;
   NQ_SINGLE_RANK(c, "nq_set_q");
@@ -2881,10 +2980,6 @@ int nq_refresh_grad_phi(nq_ctx* c) {
   return 0;
 }
 
-static void pt_before_step(nq_ctx* c);
-static int pt_after_step(nq_ctx* c);
-static int fc_apply(nq_ctx* c);
-static int fq_after_step(nq_ctx* c);
 int nq_step(nq_ctx* c, int nsteps) {
   if (!c) return -1;
   NQ_SINGLE_RANK(c, "nq_step");
@@ -2892,20 +2987,10 @@ int nq_step(nq_ctx* c, int nsteps) {
   HIPCHK(c, hipSetDevice(c->device));
   for (int i = 0; i < nsteps; ++i) {
     c->uv4_now = c->want_uv4 && i == nsteps - 1 && c->kernel_family && !c->ybj;
-    if (c->pt) pt_before_step(c);
+    attachments_before_step(c);
     do_step(c);
-    if (c->fc) {                       // the forced, re-inverted state is what the particles' U1 and the next step see
-      const int rc = fc_apply(c);
-      if (rc) return rc;
-    }
-    if (c->pt) {
-      const int rc = pt_after_step(c);
-      if (rc) return rc;
-    }
-    if (c->fq) {                       // the record of this step: the forced, re-inverted state
-      const int rc = fq_after_step(c);
-      if (rc) return rc;
-    }
+    const int rc = attachments_after_step(c);
+    if (rc) return rc;
   }
   if (nsteps > 0) {
     c->stepped = true;
@@ -2936,46 +3021,6 @@ int nq_get_stage4_max(nq_ctx* c, double* out2) {
 // re-runs do_invert_now after its stale inversion, YBJModel's step writes neither, and a dual-q context inverts the mean of its
 // two copies exactly where ph takes it.  So a velocity plane is ONE row kernel (k_x_get_uv) away at any point between steps.
 enum { PT_U = 0, PT_V = 1, PT_Q = 2, PT_PHI = 3 };
-struct NqParticles {
-  int n = 0;
-  double *x = nullptr, *y = nullptr;       // unwrapped positions
-  cd* uv[2] = {nullptr, nullptr};          // velocity planes (u, v) interleaved, ping-pong: uv[cur] is the current state's
-  int cur = 0;
-  bool u0 = false;                         // uv[cur] is the velocity of the state the next step starts from
-  int every = 0, cap = 0, ncol = 0;        // record every `every` steps into a ring of `cap` records of (2 + ncol) x n doubles
-  std::vector<int> names;                  // record columns (PT_*; PT_PHI takes two: real, imaginary part)
-  double* ring = nullptr;
-  std::vector<long long> ring_step;        // steps since attach of each slot
-  long long count = 0, steps = 0;
-  double* qplane = nullptr;                // physical q (PT_Q), allocated when first needed
-  cd* phiplane = nullptr;                  // physical phi (PT_PHI), idem
-  double* samp = nullptr;                  // nq_particles_sample's output columns (4 x n), idem
-  std::vector<void*> mem;
-  long long bytes = 0;
-};
-
-static int pt_alloc_raw(nq_ctx* c, void** out, size_t bytes) {
-  NqParticles* P = c->pt;
-  void* p = nullptr;
-  HIPCHK(c, hipMalloc(&p, bytes));
-  P->mem.push_back(p);
-  P->bytes += (long long)bytes;
-  c->bytes += (long long)bytes;
-  HIPCHK(c, hipMemsetAsync(p, 0, bytes, c->stream));
-  *out = p;
-  return 0;
-}
-#define pt_alloc(c, pptr, count) pt_alloc_raw((c), reinterpret_cast<void**>(pptr), (size_t)(count) * sizeof(**(pptr)))
-static void pt_release(nq_ctx* c) {
-  NqParticles* P = c->pt;
-  if (!P) return;
-  (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);
-  for (void* p : P->mem) (void)hipFree(p);
-  c->bytes -= P->bytes;
-  delete P;
-  c->pt = nullptr;
-}
 static PtGrid pt_grid(const nq_ctx* c) {
   PtGrid g;
   g.n = c->N;
@@ -2997,9 +3042,6 @@ static void pt_form_uv(nq_ctx* c, cd* out) {
       hipLaunchKernelGGL((k_x_get_uv<N, false, one>), rows_grid<X>(c->N), dim3(X::THREADS), X::LDS_BYTES, c->stream, c->mU, c->mP, out, c->N, c->tw, c->kk, c->kernel_family ? 1 : 0, comp);
   });
 }
-static void pt_mark_stale(nq_ctx* c) {
-  if (c && c->pt) c->pt->u0 = false;
-}
 static void pt_before_step(nq_ctx* c) {
   NqParticles* P = c->pt;
   if (!P->u0) {
@@ -3016,13 +3058,13 @@ static int pt_sample_into(nq_ctx* c, int name, double* o0, double* o1) {
     pt_before_step(c);
     hipLaunchKernelGGL(k_pt_sample<cd>, dim3(nb), dim3(256), 0, c->stream, (const cd*)P->uv[P->cur], (const double*)P->x, (const double*)P->y, P->n, g, name == PT_U ? o0 : nullptr, name == PT_V ? o0 : nullptr);
   } else if (name == PT_Q) {
-    if (!P->qplane) { int rc = pt_alloc(c, &P->qplane, (size_t)c->N * c->N); if (rc) return rc; }
+    if (!P->qplane) { int rc = att_alloc(c, P, &P->qplane, (size_t)c->N * c->N, "particles"); if (rc) return rc; }
     // Mq holds the q the last inversion saw (the mean of the two copies on dual-q contexts): m.q
     if (!launch_get_real<false>(c, c->mQ, P->qplane, 0, 0)) NQ_FAIL(c, -2, "no row plan of length %d", c->N);
     hipLaunchKernelGGL(k_pt_sample<double>, dim3(nb), dim3(256), 0, c->stream, (const double*)P->qplane, (const double*)P->x, (const double*)P->y, P->n, g, o0, nullptr);
   } else if (name == PT_PHI) {
     if (!c->kernel_family) NQ_FAIL(c, -4, "particles: QGModel has no wave field (phi)");
-    if (!P->phiplane) { int rc = pt_alloc(c, &P->phiplane, (size_t)c->N * c->N); if (rc) return rc; }
+    if (!P->phiplane) { int rc = att_alloc(c, P, &P->phiplane, (size_t)c->N * c->N, "particles"); if (rc) return rc; }
     launch_x_c2c(c, true, c->mPhi.xs, P->phiplane, c->mPhi.pitch, c->N, 1.0);         // as nq_get_field(NQ_F_PHI)
     hipLaunchKernelGGL(k_pt_sample<cd>, dim3(nb), dim3(256), 0, c->stream, (const cd*)P->phiplane, (const double*)P->x, (const double*)P->y, P->n, g, o0, o1);
   } else {
@@ -3033,9 +3075,8 @@ static int pt_sample_into(nq_ctx* c, int name, double* o0, double* o1) {
 }
 static int pt_record(nq_ctx* c) {
   NqParticles* P = c->pt;
-  const int slot = (int)(P->count % P->cap);
   const size_t n = (size_t)P->n;
-  double* r = P->ring + (size_t)slot * (2 + P->ncol) * n;
+  double* r = P->ring + (size_t)P->rg.slot() * (2 + P->ncol) * n;
   HIPCHK(c, hipMemcpyAsync(r, P->x, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(r + n, P->y, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
   int col = 2;
@@ -3044,8 +3085,7 @@ static int pt_record(nq_ctx* c) {
     if (rc) return rc;
     col += name == PT_PHI ? 2 : 1;
   }
-  P->ring_step[slot] = P->steps;
-  ++P->count;
+  P->rg.wrote();
   return 0;
 }
 static int pt_after_step(nq_ctx* c) {
@@ -3060,9 +3100,7 @@ static int pt_after_step(nq_ctx* c) {
   hipLaunchKernelGGL(k_pt_rk4, dim3(pt_blocks(P->n)), dim3(256), 0, c->stream, P->x, P->y, P->n, U0, U1, g, c->p.U, c->p.dt);
   HIPCHK(c, hipGetLastError());
   if (!c->ybj) P->cur ^= 1;
-  ++P->steps;
-  if (P->every > 0 && P->steps % P->every == 0) return pt_record(c);
-  return 0;
+  return P->rg.tick() ? pt_record(c) : 0;
 }
 
 int nq_particles_attach(nq_ctx* c, int n, const double* x, const double* y, double Lx, double Ly, int record_every, int capacity,
@@ -3087,42 +3125,31 @@ int nq_particles_attach(nq_ctx* c, int n, const double* x, const double* y, doub
   c->pt = new NqParticles();
   NqParticles* P = c->pt;
   P->n = n;
-  P->every = record_every;
-  P->cap = record_every > 0 ? capacity : 0;
+  P->rg.init(record_every > 0 ? capacity : 0, record_every);
   P->ncol = ncol;
   P->names.assign(names, names + nnames);
   const size_t plane = (size_t)c->N * c->N;
-  int rc = pt_alloc(c, &P->x, (size_t)n);
-  if (!rc) rc = pt_alloc(c, &P->y, (size_t)n);
-  if (!rc) rc = pt_alloc(c, &P->uv[0], plane);
-  if (!rc && !c->ybj) rc = pt_alloc(c, &P->uv[1], plane);
+  const char* what = "nq_particles_attach";
+  int rc = att_alloc(c, P, &P->x, (size_t)n, what);
+  if (!rc) rc = att_alloc(c, P, &P->y, (size_t)n, what);
+  if (!rc) rc = att_alloc(c, P, &P->uv[0], plane, what);
+  if (!rc && !c->ybj) rc = att_alloc(c, P, &P->uv[1], plane, what);
   if (!rc && c->ybj) P->uv[1] = P->uv[0];
-  if (!rc && P->cap > 0) {
-    rc = pt_alloc(c, &P->ring, (size_t)P->cap * (2 + ncol) * n);
-    P->ring_step.assign((size_t)P->cap, 0);
-  }
-  if (rc) {
-    const std::string e = c->err;
-    pt_release(c);
-    NQ_FAIL(c, rc, "%s", e.c_str());
-  }
+  if (!rc && P->rg.cap > 0) rc = att_alloc(c, P, &P->ring, (size_t)P->rg.cap * (2 + ncol) * n, what);
+  if (rc) return att_fail(c, c->pt, rc);
   // (hipMemcpy from pageable memory returns once the source is consumed)
   HIPCHK(c, hipMemcpyAsync(P->x, x, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(P->y, y, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
-  if (P->every > 0) {
+  if (P->rg.every > 0) {
     rc = pt_record(c);
-    if (rc) {
-      const std::string e = c->err;
-      pt_release(c);
-      NQ_FAIL(c, rc, "%s", e.c_str());
-    }
+    if (rc) return att_fail(c, c->pt, rc);
   }
   return nq_sync(c);
 }
 int nq_particles_detach(nq_ctx* c) {
   NQ_SINGLE_RANK(c, "nq_particles_detach");
   if (!c->pt) NQ_FAIL(c, -4, "nq_particles_detach: no particles attached");
-  pt_release(c);
+  att_release(c, c->pt);
   return 0;
 }
 int nq_particles_get(nq_ctx* c, double* x, double* y) {
@@ -3145,7 +3172,7 @@ int nq_particles_sample(nq_ctx* c, int nnames, const int* names, double* out) {
   }
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = (size_t)P->n;
-  if (!P->samp) { int rc = pt_alloc(c, &P->samp, 2 * n); if (rc) return rc; }
+  if (!P->samp) { int rc = att_alloc(c, P, &P->samp, 2 * n, "nq_particles_sample"); if (rc) return rc; }
   size_t col = 0;
   for (int i = 0; i < nnames; ++i) {
     const int w = names[i] == PT_PHI ? 2 : 1;
@@ -3162,57 +3189,23 @@ int nq_particles_records(nq_ctx* c, long long* info, long long* steps, double* o
   NqParticles* P = c->pt;
   if (!P) NQ_FAIL(c, -4, "nq_particles_records: no particles attached");
   if (!info) return -1;
-  const long long m = P->count < P->cap ? P->count : P->cap;
-  info[0] = P->count;
+  const long long m = P->rg.held();
+  info[0] = P->rg.count;
   info[1] = m;
   info[2] = 2 + P->ncol;
-  info[3] = P->steps;
+  info[3] = P->rg.steps;
   if (!steps && !out) return 0;
   HIPCHK(c, hipSetDevice(c->device));
   const size_t rec = (size_t)(2 + P->ncol) * P->n;
   for (long long r = 0; r < m; ++r) {
-    const long long idx = P->count - m + r;
-    const int slot = (int)(idx % P->cap);
-    if (steps) steps[r] = P->ring_step[slot];
+    const int slot = P->rg.oldest(r);
+    if (steps) steps[r] = P->rg.ring_step[slot];
     if (out) HIPCHK(c, hipMemcpyAsync(out + (size_t)r * rec, P->ring + (size_t)slot * rec, sizeof(double) * rec, hipMemcpyDeviceToHost, c->stream));
   }
   return nq_sync(c);
 }
 
 // ---- stochastic forcing (kernels and the generator: nq_forcing.hpp) --------------------------------
-struct NqForcing {
-  double *Aq = nullptr, *Aphi = nullptr;   // amplitude planes: (N, N/2+1) and (N, N), contiguous
-  FcBox bq = {}, bphi = {};                // bounding boxes of A > 0 (nrows = 0: nothing to add)
-  dim3 gq, gphi;                           // launch grids over the boxes
-  int npq = 0, npphi = 0;                  // workgroups = work partials of each kernel
-  double *partq = nullptr, *partphi = nullptr, *work = nullptr;   // partials [workgroups][2]; work_q, work_phi
-  unsigned long long seed = 0;
-  long long s = 0;                         // index of the next forced step
-  std::vector<void*> mem;
-  long long bytes = 0;
-};
-static int fc_alloc_raw(nq_ctx* c, void** out, size_t bytes) {
-  NqForcing* F = c->fc;
-  void* p = nullptr;
-  HIPCHK(c, hipMalloc(&p, bytes));
-  F->mem.push_back(p);
-  F->bytes += (long long)bytes;
-  c->bytes += (long long)bytes;
-  HIPCHK(c, hipMemsetAsync(p, 0, bytes, c->stream));
-  *out = p;
-  return 0;
-}
-#define fc_alloc(c, pptr, count) fc_alloc_raw((c), reinterpret_cast<void**>(pptr), (size_t)(count) * sizeof(**(pptr)))
-static void fc_release(nq_ctx* c) {
-  NqForcing* F = c->fc;
-  if (!F) return;
-  (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);
-  for (void* p : F->mem) (void)hipFree(p);
-  c->bytes -= F->bytes;
-  delete F;
-  c->fc = nullptr;
-}
 // bounding box of A > 0 on a (N, cols) host plane: cols = N/2+1 (half: k itself) or N (full: |k| as |l|)
 static FcBox fc_box(const double* A, int N, int cols) {
   int L = -1, K = -1;
@@ -3280,26 +3273,23 @@ int nq_forcing_attach(nq_ctx* c, const double* Aq, const double* Aphi, unsigned 
   NqForcing* F = c->fc;
   F->seed = seed;
   F->s = step0;
-  int rc = fc_alloc(c, &F->work, 2);
+  const char* what = "nq_forcing_attach";
+  int rc = att_alloc(c, F, &F->work, 2, what);
   if (!rc && Aq) {
     F->bq = fc_box(Aq, N, Wh);
     F->gq = fc_grid(F->bq);
     F->npq = (int)(F->gq.x * F->gq.y);
-    rc = fc_alloc(c, &F->Aq, (size_t)N * Wh);
-    if (!rc && F->npq > 0) rc = fc_alloc(c, &F->partq, (size_t)2 * F->npq);
+    rc = att_alloc(c, F, &F->Aq, (size_t)N * Wh, what);
+    if (!rc && F->npq > 0) rc = att_alloc(c, F, &F->partq, (size_t)2 * F->npq, what);
   }
   if (!rc && Aphi) {
     F->bphi = fc_box(Aphi, N, N);
     F->gphi = fc_grid(F->bphi);
     F->npphi = (int)(F->gphi.x * F->gphi.y);
-    rc = fc_alloc(c, &F->Aphi, (size_t)N * N);
-    if (!rc && F->npphi > 0) rc = fc_alloc(c, &F->partphi, (size_t)2 * F->npphi);
+    rc = att_alloc(c, F, &F->Aphi, (size_t)N * N, what);
+    if (!rc && F->npphi > 0) rc = att_alloc(c, F, &F->partphi, (size_t)2 * F->npphi, what);
   }
-  if (rc) {
-    const std::string e = c->err;
-    fc_release(c);
-    NQ_FAIL(c, rc, "%s", e.c_str());
-  }
+  if (rc) return att_fail(c, c->fc, rc);
   if (Aq) HIPCHK(c, hipMemcpyAsync(F->Aq, Aq, sizeof(double) * (size_t)N * Wh, hipMemcpyHostToDevice, c->stream));
   if (Aphi) HIPCHK(c, hipMemcpyAsync(F->Aphi, Aphi, sizeof(double) * (size_t)N * N, hipMemcpyHostToDevice, c->stream));
   return nq_sync(c);
@@ -3307,7 +3297,7 @@ int nq_forcing_attach(nq_ctx* c, const double* Aq, const double* Aphi, unsigned 
 int nq_forcing_detach(nq_ctx* c) {
   NQ_SINGLE_RANK(c, "nq_forcing_detach");
   if (!c->fc) NQ_FAIL(c, -4, "nq_forcing_detach: no forcing attached");
-  fc_release(c);
+  att_release(c, c->fc);
   return 0;
 }
 int nq_forcing_apply(nq_ctx* c) {
@@ -5553,48 +5543,12 @@ int nq_any_etdrk4_patch(nq_any* e, void* const* out6, int cols, int count, const
 // kernels: csrc/nq_freq.hpp, included here because k_fq_bin walks the shells with shell_run above)
 // ==================================================================================================================
 #include "nq_freq.hpp"
+static_assert(NqFreq::NF == FQ_NFIELDS, "NqFreq holds one ring per recordable field");
 
-struct NqFreq {
-  int K = 0, every = 1, length = 0, nf = 0;
-  int field[FQ_NFIELDS] = {0, 0, 0}, ncols[FQ_NFIELDS] = {0, 0, 0};
-  cd* ring[FQ_NFIELDS] = {nullptr, nullptr, nullptr};     // [record][row][col] of each attached field
-  std::vector<long long> ring_step;                        // steps since attach of each slot
-  long long count = 0, steps = 0;                          // records written, steps since attach
-  cd* work = nullptr;                                      // (length, modes of the widest field): allocated by the first spectrum
-  double *win = nullptr, *tab = nullptr;                   // window (length), table (length, nb)
-  nq_any* eng = nullptr;                                   // the any-length transform of the record axis runs on an engine of its own
-  long long eng_bytes = 0;
-  std::vector<void*> mem;
-  long long bytes = 0;
-};
-static int fq_alloc_raw(nq_ctx* c, void** out, size_t bytes, const char* what) {
-  NqFreq* F = c->fq;
-  void* p = nullptr;
-  if (hipMalloc(&p, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    NQ_FAIL(c, -5, "%s: cannot allocate %zu bytes of device memory", what, bytes);
-  }
-  F->mem.push_back(p);
-  F->bytes += (long long)bytes;
-  c->bytes += (long long)bytes;
-  *out = p;
-  return 0;
-}
-static void fq_release(nq_ctx* c) {
-  NqFreq* F = c->fq;
-  if (!F) return;
-  (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);
-  if (F->eng) (void)nq_any_destroy(F->eng);
-  for (void* p : F->mem) (void)hipFree(p);
-  c->bytes -= F->bytes + F->eng_bytes;
-  delete F;
-  c->fq = nullptr;
-}
 // one record of every attached field from the buffers that hold the current state (what nq_get_field reads), one launch
 static int fq_record(nq_ctx* c) {
   NqFreq* F = c->fq;
-  const int slot = (int)(F->count % F->length), R = 2 * F->K + 1;
+  const int slot = F->rg.slot(), R = 2 * F->K + 1;
   FqRecord a = {};
   int maxc = 0;
   for (int f = 0; f < F->nf; ++f) {
@@ -5608,15 +5562,11 @@ static int fq_record(nq_ctx* c) {
   }
   hipLaunchKernelGGL(k_fq_record, dim3((maxc + 63) / 64, (R + 3) / 4, F->nf), dim3(64, 4), 0, c->stream, a, c->N, F->K);
   HIPCHK(c, hipGetLastError());
-  F->ring_step[slot] = F->steps;
-  ++F->count;
+  F->rg.wrote();
   return 0;
 }
 static int fq_after_step(nq_ctx* c) {
-  NqFreq* F = c->fq;
-  ++F->steps;
-  if (F->steps % F->every == 0) return fq_record(c);
-  return 0;
+  return c->fq->rg.tick() ? fq_record(c) : 0;
 }
 static int fq_find(const NqFreq* F, int field) {
   for (int f = 0; f < F->nf; ++f)
@@ -5643,6 +5593,20 @@ static int fq_spectrum_run(nq_any* e, const cd* ring, int N, int K, int ncols, i
   return nq_any_sync(e);
 }
 
+// ---- nq_step's hooks (declared below dev_alloc) ----------------------------------------------------------------------------
+// Before the step the particles form U0 from the state it starts from.  After it: the forcing first -- the forced, re-inverted
+// state is what the particles' U1 and the next step see -- then the particles, then the recorder, whose record of this step
+// is that same forced, re-inverted state.  The first non-zero return code ends the call.
+static void attachments_before_step(nq_ctx* c) {
+  if (c->pt) pt_before_step(c);
+}
+static int attachments_after_step(nq_ctx* c) {
+  int rc = c->fc ? fc_apply(c) : 0;
+  if (!rc && c->pt) rc = pt_after_step(c);
+  if (!rc && c->fq) rc = fq_after_step(c);
+  return rc;
+}
+
 extern "C" {
 
 int nq_freq_attach(nq_ctx* c, int kmax, int every, int length, int nfields, const int* fields) {
@@ -5662,30 +5626,24 @@ int nq_freq_attach(nq_ctx* c, int kmax, int every, int length, int nfields, cons
   c->fq = new NqFreq();
   NqFreq* F = c->fq;
   F->K = kmax;
-  F->every = every;
-  F->length = length;
   F->nf = nfields;
-  F->ring_step.assign((size_t)length, 0);
+  F->rg.init(length, every);
   const size_t R = 2 * (size_t)kmax + 1;
   int rc = 0;
   for (int f = 0; f < nfields && !rc; ++f) {
     F->field[f] = fields[f];
     F->ncols[f] = fields[f] == FQ_PHI ? 2 * kmax + 1 : kmax + 1;
-    rc = fq_alloc_raw(c, reinterpret_cast<void**>(&F->ring[f]), sizeof(cd) * (size_t)length * R * F->ncols[f], "nq_freq_attach");
+    rc = att_alloc(c, F, &F->ring[f], (size_t)length * R * F->ncols[f], "nq_freq_attach");
   }
   if (!rc) rc = fq_record(c);                     // record 0: the state at attach
   if (!rc) rc = nq_sync(c);
-  if (rc) {
-    const std::string e = c->err;
-    fq_release(c);
-    NQ_FAIL(c, rc, "%s", e.c_str());
-  }
+  if (rc) return att_fail(c, c->fq, rc);
   return 0;
 }
 int nq_freq_detach(nq_ctx* c) {
   NQ_SINGLE_RANK(c, "nq_freq_detach");
   if (!c->fq) NQ_FAIL(c, -4, "nq_freq_detach: no recorder attached");
-  fq_release(c);
+  att_release(c, c->fq);
   return 0;
 }
 int nq_freq_info(nq_ctx* c, long long* info3) {
@@ -5693,9 +5651,9 @@ int nq_freq_info(nq_ctx* c, long long* info3) {
   NqFreq* F = c->fq;
   if (!F) NQ_FAIL(c, -4, "nq_freq_info: no recorder attached");
   if (!info3) return -1;
-  info3[0] = F->count;
-  info3[1] = F->count < F->length ? F->count : F->length;
-  info3[2] = F->steps;
+  info3[0] = F->rg.count;
+  info3[1] = F->rg.held();
+  info3[2] = F->rg.steps;
   return 0;
 }
 int nq_freq_series(nq_ctx* c, int field, long long* steps, double* out_cplx) {
@@ -5705,11 +5663,11 @@ int nq_freq_series(nq_ctx* c, int field, long long* steps, double* out_cplx) {
   const int f = fq_find(F, field);
   if (f < 0) NQ_FAIL(c, -1, "nq_freq_series: field %d is not recorded", field);
   HIPCHK(c, hipSetDevice(c->device));
-  const long long m = F->count < F->length ? F->count : F->length;
+  const long long m = F->rg.held();
   const size_t rec = (size_t)(2 * F->K + 1) * F->ncols[f];
   for (long long r = 0; r < m; ++r) {
-    const int slot = (int)((F->count - m + r) % F->length);
-    if (steps) steps[r] = F->ring_step[slot];
+    const int slot = F->rg.oldest(r);
+    if (steps) steps[r] = F->rg.ring_step[slot];
     if (out_cplx)
       HIPCHK(c, hipMemcpyAsync(out_cplx + 2 * (size_t)r * rec, F->ring[f] + (size_t)slot * rec, sizeof(cd) * rec, hipMemcpyDeviceToHost, c->stream));
   }
@@ -5722,32 +5680,28 @@ int nq_freq_spectrum(nq_ctx* c, int field, const double* window, int demean, dou
   if (!window || !out) return -1;
   const int f = fq_find(F, field);
   if (f < 0) NQ_FAIL(c, -1, "nq_freq_spectrum: field %d is not recorded", field);
-  const int T = (int)(F->count < F->length ? F->count : F->length);
+  const int T = (int)F->rg.held(), length = F->rg.cap;
   if (T < 2) NQ_FAIL(c, -1, "nq_freq_spectrum: %d record held (at least 2)", T);
   if (nb != nq_shell_of(F->K, F->K) + 1) NQ_FAIL(c, -1, "nq_freq_spectrum: nb = %d, the block has %d shells", nb, nq_shell_of(F->K, F->K) + 1);
   for (int n = 0; n < T; ++n)
     if (!std::isfinite(window[n])) NQ_FAIL(c, -1, "nq_freq_spectrum: the window is not finite at record %d", n);
   if (!std::isfinite(dk) || !(dk > 0.0)) NQ_FAIL(c, -1, "nq_freq_spectrum: dk = %g", dk);
   HIPCHK(c, hipSetDevice(c->device));
+  const long long eng_before = F->eng ? nq_any_device_bytes(F->eng) : 0;
   if (!F->work) {                                   // first call: the work plane of a full ring of the widest field, window, table
     int maxc = 0;
     for (int g = 0; g < F->nf; ++g) maxc = F->ncols[g] > maxc ? F->ncols[g] : maxc;
-    const size_t have = F->mem.size();
-    const long long before = F->bytes;
-    int rc = fq_alloc_raw(c, reinterpret_cast<void**>(&F->work), sizeof(cd) * (size_t)F->length * (2 * (size_t)F->K + 1) * maxc, "nq_freq_spectrum");
-    if (!rc) rc = fq_alloc_raw(c, reinterpret_cast<void**>(&F->win), sizeof(double) * (size_t)F->length, "nq_freq_spectrum");
-    if (!rc) rc = fq_alloc_raw(c, reinterpret_cast<void**>(&F->tab), sizeof(double) * (size_t)F->length * nb, "nq_freq_spectrum");
+    const char* what = "nq_freq_spectrum";
+    const DevMark before = F->mark();
+    int rc = att_alloc(c, F, &F->work, (size_t)length * (2 * (size_t)F->K + 1) * maxc, what);
+    if (!rc) rc = att_alloc(c, F, &F->win, (size_t)length, what);
+    if (!rc) rc = att_alloc(c, F, &F->tab, (size_t)length * nb, what);
     if (!rc && !F->eng) {
       rc = nq_any_create(c->device, &F->eng);
       if (rc) c->err = g_last_error;
     }
     if (rc) {                                       // the recorder stays as it was
-      while (F->mem.size() > have) {
-        (void)hipFree(F->mem.back());
-        F->mem.pop_back();
-      }
-      c->bytes -= F->bytes - before;
-      F->bytes = before;
+      c->bytes -= F->rollback(before);
       F->work = nullptr;
       F->win = F->tab = nullptr;
       return rc;
@@ -5755,12 +5709,11 @@ int nq_freq_spectrum(nq_ctx* c, int field, const double* window, int demean, dou
   }
   int rc = nq_sync(c);                              // every record queued on the context's stream is in the ring
   if (rc) return rc;
-  const int first = (int)((F->count - T) % F->length);
-  rc = fq_spectrum_run(F->eng, F->ring[f], c->N, F->K, F->ncols[f], field == FQ_PHI ? 1 : 0, field == FQ_PSI ? 1 : 0, F->length, first, T, window,
+  rc = fq_spectrum_run(F->eng, F->ring[f], c->N, F->K, F->ncols[f], field == FQ_PHI ? 1 : 0, field == FQ_PSI ? 1 : 0, length, F->rg.oldest(0), T, window,
                        demean, dk, nb, F->work, F->win, F->tab, out);
-  const long long eb = nq_any_device_bytes(F->eng);      // the engine's work rows count as the recorder's
-  c->bytes += eb - F->eng_bytes;
-  F->eng_bytes = eb;
+  const long long grown = nq_any_device_bytes(F->eng) - eng_before;      // the engine's work rows count as the recorder's
+  F->bytes += grown;
+  c->bytes += grown;
   if (rc) NQ_FAIL(c, rc, "nq_freq_spectrum: %s", nq_any_last_error(F->eng));
   return 0;
 }

@@ -22,7 +22,7 @@ phi: the change of ke_niw, sum [Re(conj(phih) D) + |D|^2 / 2] / M^2, with psi-ha
 """
 import numpy as np
 
-from . import _lib
+from . import _attach, _lib
 
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 _MASK = np.uint64(0xFFFFFFFF)
@@ -120,16 +120,16 @@ def _plane(a, shape, what):
     return np.ascontiguousarray(a)
 
 
-class Forcing(object):
+class Forcing(_attach.Attachment):
     """A forcing attached to one model (``attach``); see the module's doc"""
+    SLOT, LABEL = "_forcing", "forcing"
+    ALREADY = (ValueError, "forcing.attach: this model has a forcing attached already (detach it first)")
+    NO_SLAB = ("forcing.attach: slab-decomposed models have no forcing yet (every rank would draw its own "
+               "columns and the work partials would need an all-reduce; DESIGN.md section 7)")
 
     def __init__(self, m, Aq, Aphi, seed, step0):
         self.m, self.seed = m, seed
         self.forced = tuple(nm for nm, a in (("q", Aq), ("phi", Aphi)) if a is not None)
-
-    def _check(self):
-        if self.m is None:
-            raise RuntimeError("forcing: detached")
 
     def kick(self):
         """one increment and re-inversion now, outside a step (advances the step index)"""
@@ -157,16 +157,6 @@ class Forcing(object):
         if isinstance(step, bool) or int(step) != step or step < 0:
             raise ValueError("forcing.increment: step = %r (an integer >= 0)" % (step,))
         return self._increment(STREAMS[name], int(step))
-
-    def detach(self):
-        """frees every device buffer the forcing allocated"""
-        if self.m is None:
-            return
-        try:
-            self._detach()
-        finally:
-            self.m.__dict__.pop("_forcing", None)
-            self.m = None
 
 
 class _Fused(Forcing):
@@ -302,14 +292,4 @@ def attach(m, q=None, phi=None, seed=0, step0=0):
     if isinstance(step0, bool) or int(step0) != step0 or step0 < 0:
         raise ValueError("forcing.attach: step0 = %r (an integer >= 0)" % (step0,))
     seed, step0 = int(seed), int(step0)
-    if m.__dict__.get("_forcing") is not None:
-        raise ValueError("forcing.attach: this model has a forcing attached already (detach it first)")
-    if getattr(m, "_any_size", False):
-        F = _AnySize(m, Aq, Aphi, seed, step0)
-    elif isinstance(m._ctx, _lib.Context):
-        F = _Fused(m, Aq, Aphi, seed, step0)
-    else:
-        raise NotImplementedError("forcing.attach: slab-decomposed models have no forcing yet (every rank would draw its own "
-                                  "columns and the work partials would need an all-reduce; DESIGN.md section 7)")
-    m.__dict__["_forcing"] = F
-    return F
+    return _attach.attach(m, _AnySize, _Fused, Aq, Aphi, seed, step0)

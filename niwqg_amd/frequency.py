@@ -37,7 +37,7 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _attach, _lib
 from .spectra import shell_of
 
 FIELDS = ("phi", "q", "psi")                      # ids of the library (include/niwqg_amd.h: nq_freq_attach)
@@ -206,16 +206,19 @@ def _class_id(m):
     return _lib.QG if isinstance(m, QG) else m.model_id
 
 
-class Recorder(object):
+class Recorder(_attach.Attachment):
     """A recorder attached to one model (``attach``); see the module's doc"""
+    SLOT, LABEL = "_frequency", "frequency"
+    ALREADY = (ValueError, "frequency.attach: this model has a recorder attached already (detach it first)")
+    NO_SLAB = ("frequency.attach: slab-decomposed models have no recorder yet (every rank would gather the columns "
+               "it owns and the block would be assembled at read-out; DESIGN.md section 7)")
 
     def __init__(self, m, K, every, length, fields):
         self.m, self.kmax, self.every, self.length, self.fields = m, K, every, length, fields
         self.t0, self.dt = float(m.t), float(m.dt)
 
     def _check(self, name=None):
-        if self.m is None:
-            raise RuntimeError("frequency: detached")
+        _attach.Attachment._check(self)
         if name is not None and name not in self.fields:
             raise ValueError("frequency: %r is not recorded; recorded: %s" % (name, ", ".join(self.fields)))
 
@@ -247,16 +250,6 @@ class Recorder(object):
         values = {n: self._spectrum(n, w, bool(demean), dk, nb)[order] for n in names}
         step = self._series(names[0], 0, 0, steps_only=True)
         return FrequencySpectra(2.0 * np.pi * f[order], np.arange(nb, dtype=np.int64), dk, block_modes(K), K * dk, values, step)
-
-    def detach(self):
-        """frees every device buffer the recorder allocated"""
-        if self.m is None:
-            return
-        try:
-            self._detach()
-        finally:
-            self.m.__dict__.pop("_frequency", None)
-            self.m = None
 
 
 class _Fused(Recorder):
@@ -297,8 +290,7 @@ class _AnySize(Recorder):
         R = 2 * K + 1
         self.cols = [R if n == "phi" else K + 1 for n in fields]
         self.rings = [e.zeros((length * R, c)) for c in self.cols]
-        self.ring_step = [0] * length
-        self.count = self.steps = 0
+        self.rg = _attach.Ring(length, every)
         nf = len(fields)
         self._rings_c = (ctypes.c_void_p * nf)(*[r.ptr for r in self.rings])
         self._full_c = (ctypes.c_int * nf)(*[1 if n == "phi" else 0 for n in fields])
@@ -307,28 +299,25 @@ class _AnySize(Recorder):
     def _record(self):
         e, m, nf = self.eng, self.m, len(self.fields)
         planes = [m._d[self._PLANES[n]] for n in self.fields]
-        slot = self.count % self.length
+        slot = self.rg.slot()
         e.chk(e.L.nq_any_freq_record(e.h, nf, self._rings_c, (ctypes.c_void_p * nf)(*[p.ptr for p in planes]),
                                      (ctypes.c_int * nf)(*[p.shape[1] for p in planes]), self._full_c, m.nx, self.kmax, self.length, slot),
               "nq_any_freq_record")
-        self.ring_step[slot] = self.steps
-        self.count += 1
+        self.rg.wrote()
 
     def _after_step(self):
-        self.steps += 1
-        if self.steps % self.every == 0:
+        if self.rg.tick():
             self._record()
 
     def _info(self):
-        return self.count, min(self.count, self.length), self.steps
+        return self.rg.count, self.rg.held(), self.rg.steps
 
     def _slots(self):
-        held = min(self.count, self.length)
-        return [(self.count - held + r) % self.length for r in range(held)]
+        return [self.rg.oldest(r) for r in range(self.rg.held())]
 
     def _series(self, name, rows, cols, steps_only=False):
         slots = self._slots()
-        step = np.array([self.ring_step[s] for s in slots], np.int64)
+        step = np.array([self.rg.ring_step[s] for s in slots], np.int64)
         if steps_only:
             return step
         ring = self.rings[self.fields.index(name)].get().reshape(self.length, rows, cols)
@@ -354,14 +343,4 @@ def attach(m, kmax, every=1, length=256, fields=None):
     records, one at attach and one after every ``every``-th step.  Argument errors raise ValueError before the device is touched;
     slab-decomposed models raise NotImplementedError."""
     K, every, length, fields = check(int(m.nx), _class_id(m), kmax, every, length, fields)
-    if m.__dict__.get("_frequency") is not None:
-        raise ValueError("frequency.attach: this model has a recorder attached already (detach it first)")
-    if getattr(m, "_any_size", False):
-        R = _AnySize(m, K, every, length, fields)
-    elif isinstance(m._ctx, _lib.Context):
-        R = _Fused(m, K, every, length, fields)
-    else:
-        raise NotImplementedError("frequency.attach: slab-decomposed models have no recorder yet (every rank would gather the columns "
-                                  "it owns and the block would be assembled at read-out; DESIGN.md section 7)")
-    m.__dict__["_frequency"] = R
-    return R
+    return _attach.attach(m, _AnySize, _Fused, K, every, length, fields)

@@ -21,7 +21,7 @@ only buffers of their own: every model output is bit-identical to a run without 
 """
 import numpy as np
 
-from . import _lib
+from . import _attach
 
 NAMES = ("u", "v", "q", "phi")
 _CODES = dict(u=0, v=1, q=2, phi=3)
@@ -115,17 +115,17 @@ class Trajectory(object):
         return "Trajectory(T=%d, n=%d, names=%s)" % (self.x.shape[0], self.x.shape[1], sorted(self.values))
 
 
-class Particles(object):
+class Particles(_attach.Attachment):
     """A particle set attached to one model (``attach``); see the module's doc"""
+    SLOT, LABEL = "_particles", "particles"
+    ALREADY = (RuntimeError, "particles.attach: this model has particles attached already (detach them first)")
+    NO_SLAB = ("particles.attach: slab-decomposed models have no particles yet (they need the interpolation "
+               "partials exchanged between the ranks at every stage; DESIGN.md section 7)")
 
     def __init__(self, m, n, record_every, capacity, record):
         self.m, self.n = m, n
         self.record_every, self.capacity, self.record = record_every, capacity, tuple(record)
         self.tc0, self.t0 = m.tc, m.t
-
-    def _check(self):
-        if self.m is None:
-            raise RuntimeError("particles: detached")
 
     def positions(self):
         """(x, y): the unwrapped coordinates (host copies)"""
@@ -157,16 +157,6 @@ class Particles(object):
         order = np.argsort(offsets, kind="stable")
         assert np.all(order == np.arange(len(order)))
         return Trajectory(offsets + self.tc0, self._times(offsets), x, y, vals)
-
-    def detach(self):
-        """frees every device buffer the set allocated"""
-        if self.m is None:
-            return
-        try:
-            self._detach()
-        finally:
-            self.m.__dict__.pop("_particles", None)
-            self.m = None
 
     @staticmethod
     def _split(names, cols):
@@ -215,8 +205,8 @@ class _AnySize(Particles):
         self.eng = m._eng
         self.pos = self.eng.plane((x + 1j * y).reshape(1, -1), real=False)
         self.U, self.src = None, None       # velocity plane of the state src (the psi-hat Plane it was formed from)
-        self.ring = [None] * (capacity if record_every > 0 else 0)
-        self.count, self.steps = 0, 0
+        self.rg = _attach.Ring(capacity if record_every > 0 else 0, record_every)
+        self.ring = [None] * self.rg.cap
         self._Plane = Plane
         if record_every > 0:
             self._record()
@@ -256,8 +246,8 @@ class _AnySize(Particles):
     def _record(self):
         if not self.ring:
             return
-        self.ring[self.count % len(self.ring)] = (self.steps, self.pos.copy(), self._planes(self.record))
-        self.count += 1
+        self.ring[self.rg.slot()] = (self.pos.copy(), self._planes(self.record))
+        self.rg.wrote()
 
     def _before_step(self):
         self.U0 = self._current_U()
@@ -268,8 +258,7 @@ class _AnySize(Particles):
         e.chk(e.L.nq_any_particles_rk4(e.h, self.pos.ptr, self.n, self.U0.ptr, U1.ptr, m.nx, float(m.L), float(m.W), float(m.U),
                                        float(m.dt)), "nq_any_particles_rk4")
         self.U0 = None
-        self.steps += 1
-        if self.record_every > 0 and self.steps % self.record_every == 0:
+        if self.rg.tick():
             self._record()
 
     def _positions(self):
@@ -281,13 +270,15 @@ class _AnySize(Particles):
         return {nm: (pl[nm].get().reshape(-1) if nm == "phi" else pl[nm].get().reshape(-1).real.copy()) for nm in names}
 
     def _records(self):
-        m = min(self.count, len(self.ring))
-        recs = [self.ring[(self.count - m + r) % len(self.ring)] for r in range(m)]
-        steps = np.array([r[0] for r in recs], np.int64)
-        pos = np.array([r[1].get().reshape(-1) for r in recs]).reshape(m, self.n)
+        rg = self.rg
+        m = rg.held()
+        slots = [rg.oldest(r) for r in range(m)]
+        recs = [self.ring[s] for s in slots]
+        steps = np.array([rg.ring_step[s] for s in slots], np.int64)
+        pos = np.array([r[0].get().reshape(-1) for r in recs]).reshape(m, self.n)
         vals = {}
         for nm in self.record:
-            a = np.array([r[2][nm].get().reshape(-1) for r in recs]).reshape(m, self.n)
+            a = np.array([r[1][nm].get().reshape(-1) for r in recs]).reshape(m, self.n)
             vals[nm] = a if nm == "phi" else a.real.copy()
         return steps, pos.real.copy(), pos.imag.copy(), vals
 
@@ -310,14 +301,4 @@ def attach(m, x, y, record_every=0, capacity=1024, record=()):
     record = tuple(_names(m, record, "attach"))
     if len(set(record)) != len(record):
         raise ValueError("particles.attach: a name appears twice in record: %s" % (record,))
-    if m.__dict__.get("_particles") is not None:
-        raise RuntimeError("particles.attach: this model has particles attached already (detach them first)")
-    if getattr(m, "_any_size", False):
-        P = _AnySize(m, x, y, record_every, capacity, record)
-    elif isinstance(m._ctx, _lib.Context):
-        P = _Fused(m, x, y, record_every, capacity, record)
-    else:
-        raise NotImplementedError("particles.attach: slab-decomposed models have no particles yet (they need the interpolation "
-                                  "partials exchanged between the ranks at every stage; DESIGN.md section 7)")
-    m.__dict__["_particles"] = P
-    return P
+    return _attach.attach(m, _AnySize, _Fused, x, y, record_every, capacity, record)
