@@ -329,6 +329,27 @@ int nq_freq_info(nq_ctx* ctx, long long* info3);
 int nq_freq_series(nq_ctx* ctx, int field, long long* steps, double* out_cplx);
 int nq_freq_spectrum(nq_ctx* ctx, int field, const double* window, int demean, double dk, int nb, double* out);
 
+/* Time-mean and covariance maps of the physical fields, accumulated in the step, single-rank contexts only
+ * (slab contexts refuse every call with -4).  The attachment keeps one running-sum plane per listed field and per listed product,
+ * (ny, nx) float64 in physical order (NQ_AVG_PHI: complex128), zero at attach.  Fields: NQ_AVG_Q, NQ_AVG_QPSI, NQ_AVG_PHI2 (= |phi|^2)
+ * and NQ_AVG_PHI on the Kernel family, NQ_AVG_Q and (with its passive scalar) NQ_AVG_C on QGModel, each at most once; the values
+ * are those nq_field_hist bins (the rows of the last inversion; dual_q contexts: the mean of the two q-hat copies).  pairs: 2 x
+ * nproducts field ids, unordered pairs of REAL fields of the list (a pair of one field: its second moment), each pair once; -1
+ * otherwise.  A sample adds x to every field's plane and x y to every product's, in fp64, one thread per point (no atomics: two
+ * runs are bit-identical; x y may be contracted into the add).  every >= 0: every `every`-th step of a step call since attach
+ * ends with one sample, taken last (after the forcing, the particles and the recorder); 0: never.  attach takes no sample;
+ * sample takes one now; reset zeroes the sums and the sample count, not the step count.  One set per context (-4 while one is
+ * attached).  Every allocation is counted by nq_device_bytes and freed by detach; one that fails is an error (-5) that leaves
+ * nothing attached.  info3 = {samples in the sums, steps since attach, planes}; read: plane `plane_index` (fields in the order of
+ * the attach call, then the products) into out, nx ny doubles (NQ_AVG_PHI: 2 nx ny).                                          */
+enum { NQ_AVG_Q = 0, NQ_AVG_QPSI = 1, NQ_AVG_PHI2 = 2, NQ_AVG_C = 3, NQ_AVG_PHI = 4 };      /* the first four: NQ_PDF_* */
+int nq_avg_attach(nq_ctx* ctx, int nfields, const int* fields, int nproducts, const int* pairs, int every);
+int nq_avg_detach(nq_ctx* ctx);
+int nq_avg_sample(nq_ctx* ctx);
+int nq_avg_reset(nq_ctx* ctx);
+int nq_avg_info(nq_ctx* ctx, long long* info3);
+int nq_avg_read(nq_ctx* ctx, int plane_index, double* out);
+
 /* copy of one ETDRK4 coefficient plane (0:E 1:Eh 2:Q 3:f0 4:fab 5:fc) of equation eq (0: q, (nx, nx/2+1) complex;
  * 1: phi, (nx, nx) complex; 2: QGModel's passive scalar, (nx, nx/2+1)), without the filter folded in; values as the
  * reference's expch, expch_h, Qh, f0, fab, fc (Kernel.py:417-454, QGModel.py:426-461).                           */
@@ -578,6 +599,11 @@ int nq_any_freq_record(nq_any* eng, int nf, void* const* rings, const void* cons
                        int length, int slot);
 int nq_any_freq_spectrum(nq_any* eng, const void* ring, int rows, int kmax, int full, int kappa, int length, int first, int T,
                          const double* window, int demean, double dk, int nb, double* out);
+/* One sample of the averages on engine planes (nq_avg_attach above: the same rule, QGModel's kernel).  src[i]: complex planes of
+ * `elems` values read as what[i] (0: Re, 1: |a|^2, 2: the complex value, at most once and in no product) and added to sums[i]
+ * (elems doubles; what 2: elems complex); pairs: 2 x nproducts indices into src, psums[p] += the product.  Not synchronous.  */
+int nq_any_moments(nq_any* eng, long long elems, int nfields, const void* const* src, const int* what, void* const* sums, int nproducts,
+                   const int* pairs, void* const* psums);
 /* E = exp(c dt), Eh = exp(c dt / 2), Q, f0, fab, fc of the linear operator c(l, k) on a (n, cols) plane, WITHOUT the filter
  * (Kernel.py:417-454, QGModel.py:426-466); eq 0: q of the Kernel family, 1: phi, 2: QGModel's q (beta term), 3: its passive
  * scalar.  The entries within delta of the contour are listed (near_*; at most cap) for the host to recompute exactly as the

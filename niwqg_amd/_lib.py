@@ -20,7 +20,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # NIWQG_AMD_LIB: another build of the same sources (A/B experiments with compile-time knobs, tools/); default: the in-tree library
 LIB_PATH = os.environ.get("NIWQG_AMD_LIB") or os.path.join(HERE, "libniwqg_amd.so")
 SRC = os.path.join(HERE, "csrc", "nq_lib.hip")
-HEADERS = [os.path.join(HERE, "csrc", h) for h in ("nq_fft.hpp", "nq_generic.hpp", "nq_step.hpp", "nq_anysize.hpp", "nq_particles.hpp", "nq_forcing.hpp", "nq_hist.hpp", "nq_freq.hpp")] + [
+HEADERS = [os.path.join(HERE, "csrc", h) for h in ("nq_fft.hpp", "nq_generic.hpp", "nq_step.hpp", "nq_anysize.hpp", "nq_particles.hpp", "nq_forcing.hpp", "nq_hist.hpp", "nq_freq.hpp", "nq_avg.hpp")] + [
     os.path.join(os.path.dirname(HERE), "include", "niwqg_amd.h")]
 
 COUPLED, UNCOUPLED, QG, YBJ = 0, 1, 2, 3
@@ -34,6 +34,7 @@ EXPORTS = ["nq_create", "nq_destroy", "nq_last_error", "nq_set_q", "nq_set_c", "
            "nq_particles_attach", "nq_particles_detach", "nq_particles_get", "nq_particles_sample", "nq_particles_records",
            "nq_forcing_attach", "nq_forcing_detach", "nq_forcing_apply", "nq_forcing_increment", "nq_forcing_state", "nq_any_forcing",
            "nq_freq_attach", "nq_freq_detach", "nq_freq_info", "nq_freq_series", "nq_freq_spectrum", "nq_any_freq_record", "nq_any_freq_spectrum",
+           "nq_avg_attach", "nq_avg_detach", "nq_avg_sample", "nq_avg_reset", "nq_avg_info", "nq_avg_read", "nq_any_moments",
            "nq_stream_copy_gbs", "nq_timer_start", "nq_timer_stop", "nq_event_record", "nq_event_elapsed", "nq_profile_enable", "nq_profile_read", "nq_profile_read_all", "nq_group_elems", "nq_overlap_grid", "nq_overlap_default_cus", "nq_overlap_info", "nq_create_slab",
            "nq_slab_info", "nq_group_buffers", "nq_upload_spectral", "nq_download_spectral", "nq_phase",
            "nq_reduce_buffer", "nq_reduce_read", "nq_reduce_write", "nq_device_bytes", "nq_stream",
@@ -48,6 +49,8 @@ EXPORTS = ["nq_create", "nq_destroy", "nq_last_error", "nq_set_q", "nq_set_c", "
 (PDF_Q, PDF_QPSI, PDF_PHI2, PDF_C) = range(4)      # fields of nq_field_hist (include/niwqg_amd.h: NQ_PDF_*)
 PDF_MAX_BINS, PDF_MAX_JOINT_BINS = 1024, 128
 PDF_DEVICE_BYTES = (3 * (PDF_MAX_BINS + 3) + PDF_MAX_JOINT_BINS ** 2 + 1) * 8 + 6 * 8192 * 8     # NQ_PDF_DEVICE_BYTES
+
+(AVG_Q, AVG_QPSI, AVG_PHI2, AVG_C, AVG_PHI) = range(5)      # fields of nq_avg_attach (include/niwqg_amd.h: NQ_AVG_*)
 
 TRANSFER_ROWS = 6                 # rows of nq_transfer_binned (include/niwqg_amd.h: NQ_TRANSFER_ROWS)
 
@@ -151,6 +154,13 @@ def lib():
                                      ctypes.c_int]
     L.nq_any_freq_spectrum.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp,
                                        ctypes.c_int, ctypes.c_double, ctypes.c_int, dp]
+    L.nq_avg_attach.argtypes = [vp, ctypes.c_int, ip, ctypes.c_int, ip, ctypes.c_int]
+    for name in ("nq_avg_detach", "nq_avg_sample", "nq_avg_reset"):
+        getattr(L, name).argtypes = [vp]
+    L.nq_avg_info.argtypes = [vp, llp]
+    L.nq_avg_read.argtypes = [vp, ctypes.c_int, dp]
+    L.nq_any_moments.argtypes = [vp, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(vp), ip, ctypes.POINTER(vp), ctypes.c_int, ip,
+                                 ctypes.POINTER(vp)]
     L.nq_get_coeff.argtypes = [vp, ctypes.c_int, ctypes.c_int, dp]
     L.nq_coeff_near_contour.argtypes = [vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     L.nq_coeff_patch.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, dp]
@@ -642,4 +652,31 @@ class Context:
         w = np.ascontiguousarray(window, np.float64)
         out = np.empty((len(w), nb))
         self._chk(self.L.nq_freq_spectrum(self.h, int(field), _dptr(w), int(bool(demean)), float(dk), int(nb), _dptr(out)), "nq_freq_spectrum")
+        return out
+
+    # ---- time-mean and covariance maps (include/niwqg_amd.h: nq_avg_*; niwqg_amd/averages.py) ---------------------------------------
+    def avg_attach(self, fields, pairs, every):
+        f = (ctypes.c_int * len(fields))(*fields)
+        flat = [i for p in pairs for i in p]
+        pr = (ctypes.c_int * max(1, len(flat)))(*flat)
+        self._chk(self.L.nq_avg_attach(self.h, len(fields), f, len(pairs), pr, int(every)), "nq_avg_attach")
+
+    def avg_detach(self):
+        self._chk(self.L.nq_avg_detach(self.h), "nq_avg_detach")
+
+    def avg_sample(self):
+        self._chk(self.L.nq_avg_sample(self.h), "nq_avg_sample")
+
+    def avg_reset(self):
+        self._chk(self.L.nq_avg_reset(self.h), "nq_avg_reset")
+
+    def avg_info(self):
+        """(samples in the sums, steps since attach, planes)"""
+        out = (ctypes.c_longlong * 3)()
+        self._chk(self.L.nq_avg_info(self.h, out), "nq_avg_info")
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def avg_read(self, index, cplx=False):
+        out = np.empty((self.nx, self.nx), np.complex128 if cplx else np.float64)
+        self._chk(self.L.nq_avg_read(self.h, int(index), _dptr(out.view(np.float64))), "nq_avg_read")
         return out

@@ -116,14 +116,15 @@ template <int N> constexpr size_t hist_lds_bytes(int words) {
 // min q, max q, min q_psi, max q_psi, min |phi|^2, max |phi|^2 (NaN when any value is).
 // The tables alias the exchange: the row's values are in registers after the second transform and nothing reads the exchange
 // or the twiddles after it.
-template <int N, int MODE, bool SLAB, bool MINMAX>
-__global__ void __launch_bounds__(XPlan<N>::THREADS, XPlan<N>::MIN_WAVES)
-k_x_hist(MArr Mq, MArr Mqw, MArr Mphi, const cd* __restrict__ tw, const double* __restrict__ kk, HistArgs h,
-         double* __restrict__ part) {
+// The part both k_x_hist and k_x_moments (nq_avg.hpp) run: the loads, the packing and the two transforms of one row block, up to
+// "values in registers": q[t], qpsi[t] and phi[t] of point j + t * T of the thread's row.  On return every wave is through its
+// last exchange: the LDS (the twiddles included) is free.
+template <int N, int MODE, bool SLAB>
+__device__ __forceinline__ void x_row_values(const MArr& Mq, const MArr& Mqw, const MArr& Mphi, const cd* __restrict__ tw,
+                                             const double* __restrict__ kk, double (&q)[XPlan<N>::P], double (&qpsi)[XPlan<N>::P],
+                                             cd (&w)[XPlan<N>::P]) {
   typedef XPlan<N> X;
   typedef typename X::F F;
-  static_assert(hist_lds_bytes<N>(HIST_MAX_WORDS) <= 160 * 1024, "row plan or LDS tables exceed the 160 KB of a CU");
-  static_assert(X::LDS_BYTES >= 16 * 6 * sizeof(double), "min/max scratch");
   constexpr int P = X::P, T = X::T;
   const int j = threadIdx.x % T, c = threadIdx.x / T;
   const size_t row = (size_t)blockIdx.x * X::C + c;
@@ -133,14 +134,12 @@ k_x_hist(MArr Mq, MArr Mqw, MArr Mphi, const cd* __restrict__ tw, const double* 
   typename F::TwLds twr;
   twr.base = twl;
   wg_barrier_all();
-  cd w[P];
   HsRegs<P> h1;
   hs_load<N, P, T, MODE == MODE_COUPLED>(h1, xrow<SLAB>(Mq, row), xrow<SLAB>(MODE == MODE_COUPLED ? Mqw : Mq, row), j);
   NQ_PHASE_FENCE();
   hs_pack<N, P, T, F, MODE == MODE_COUPLED>(w, h1, j, c, lds, kk, false, false);
   NQ_PHASE_FENCE();
   F::template run<true>(w, j, c, lds, twr);
-  double q[P], qpsi[P];
 #pragma unroll
   for (int t = 0; t < P; ++t) {
     q[t] = w[t].x;
@@ -155,6 +154,19 @@ k_x_hist(MArr Mq, MArr Mqw, MArr Mphi, const cd* __restrict__ tw, const double* 
   F::template run<true>(w, j, c, lds, twr);
   NQ_PHASE_FENCE();
   wg_barrier_all();                                  // every wave is through its last exchange: the LDS is free
+}
+
+template <int N, int MODE, bool SLAB, bool MINMAX>
+__global__ void __launch_bounds__(XPlan<N>::THREADS, XPlan<N>::MIN_WAVES)
+k_x_hist(MArr Mq, MArr Mqw, MArr Mphi, const cd* __restrict__ tw, const double* __restrict__ kk, HistArgs h,
+         double* __restrict__ part) {
+  typedef XPlan<N> X;
+  static_assert(hist_lds_bytes<N>(HIST_MAX_WORDS) <= 160 * 1024, "row plan or LDS tables exceed the 160 KB of a CU");
+  static_assert(X::LDS_BYTES >= 16 * 6 * sizeof(double), "min/max scratch");
+  constexpr int P = X::P;
+  double q[P], qpsi[P];
+  cd w[P];
+  x_row_values<N, MODE, SLAB>(Mq, Mqw, Mphi, tw, kk, q, qpsi, w);
   if (MINMAX) {
     double mn[3] = {q[0], qpsi[0], 0.0}, mx[3] = {q[0], qpsi[0], 0.0};
     mn[2] = mx[2] = w[0].x * w[0].x + w[0].y * w[0].y;

@@ -13,6 +13,7 @@
 #include "nq_anysize.hpp"
 #include "nq_particles.hpp"
 #include "nq_hist.hpp"
+#include "nq_avg.hpp"
 #include "nq_forcing.hpp"
 
 using namespace nq;
@@ -108,6 +109,14 @@ struct NqFreq : DevOwned {                 // low-mode recorder (section 5j)
   double *win = nullptr, *tab = nullptr;   // window (rg.cap), table (rg.cap, nb)
   nq_any* eng = nullptr;                   // the any-length transform of the record axis runs on an engine of its own
   ~NqFreq() { if (eng) (void)nq_any_destroy(eng); }
+};
+
+struct NqAvg : DevOwned {                  // time-mean and covariance maps (section 5l)
+  int nf = 0, np = 0;
+  int field[AVG_SLOTS + 1] = {0, 0, 0, 0};          // public ids, in the order of the attach call: the planes nq_avg_read counts
+  void* plane[AVG_SLOTS + 1 + AVG_MAX_PRODUCTS] = {};       // fields first (phi: a complex plane), then the products
+  AvgArgs args = {};
+  RecordRing rg;                           // cap = 1: only tick() and the two counters are used (count = samples in the sums)
 };
 
 struct nq_ctx {
@@ -249,6 +258,7 @@ struct nq_ctx {
   double pt_L[2] = {0.0, 0.0};       // their domain, Lx and Ly
   NqForcing* fc = nullptr;            // stochastic forcing (nq_forcing_attach): null when none
   NqFreq* fq = nullptr;               // low-mode time-series recorder (nq_freq_attach): null when none
+  NqAvg* av = nullptr;                // time-mean and covariance maps (nq_avg_attach): null when none
 };
 
 // Device arrays start at staggered offsets inside their allocations.  hipMalloc hands out large blocks at addresses that
@@ -298,7 +308,7 @@ static int att_alloc(nq_ctx* c, DevOwned* o, Tp** out, size_t count, const char*
   *out = static_cast<Tp*>(p);
   return 0;
 }
-// detach: the stream drains, the memory goes back, the slot (c->pt, c->fc, c->fq) is null again
+// detach: the stream drains, the memory goes back, the slot (c->pt, c->fc, c->fq, c->av) is null again
 template <typename A>
 static void att_release(nq_ctx* c, A*& slot) {
   if (!slot) return;
@@ -2277,6 +2287,19 @@ static void launch_xhist(nq_ctx* c, const HistArgs& h, double* part) {
   if (c->p.model == NQ_MODEL_COUPLED) launch_xhist_t<MODE_COUPLED, false, MINMAX>(c, h, part);
   else launch_xhist_t<MODE_UNCOUPLED, false, MINMAX>(c, h, part);
 }
+// time-mean and covariance maps (csrc/nq_avg.hpp): the same row pass with the read-add-write of the sum planes after it
+template <int MODE>
+static void launch_xmoments_t(nq_ctx* c, const AvgArgs& a) {
+  with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    typedef XPlan<N> X;
+    hipLaunchKernelGGL((k_x_moments<N, MODE, false>), dim3(c->Nloc / X::C), dim3(X::THREADS), X::LDS_BYTES, c->stream, c->mQ, c->mQw, c->mPhi, c->twx, c->kk, a);
+  });
+}
+static void launch_xmoments(nq_ctx* c, const AvgArgs& a) {
+  if (c->p.model == NQ_MODEL_COUPLED) launch_xmoments_t<MODE_COUPLED>(c, a);
+  else launch_xmoments_t<MODE_UNCOUPLED>(c, a);
+}
 static int hist_plane_grid(size_t n) { return (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024); }
 
 // 1 read + 1 write stream copy, 16 B per lane: the rate a copy kernel reaches on THIS device, the second denominator of
@@ -2739,6 +2762,7 @@ int nq_destroy(nq_ctx* c) {
   att_release(c, c->pt);
   att_release(c, c->fc);
   att_release(c, c->fq);
+  att_release(c, c->av);
   for (void* p : c->allocs) hipFree(p);
   for (auto& pt : c->patch) { (void)hipFree(pt.l); (void)hipFree(pt.k); (void)hipFree(pt.v); }
   for (hipEvent_t e : c->prof_ev) hipEventDestroy(e);
@@ -5593,10 +5617,38 @@ static int fq_spectrum_run(nq_any* e, const cd* ring, int N, int K, int ncols, i
   return nq_any_sync(e);
 }
 
+// ---- time-mean and covariance maps (kernels: csrc/nq_avg.hpp) ----------------------------------------
+// slot of a public field id: hist_slot's for the real fields, AVG_PHI for the Kernel family's phi
+static int av_slot(const nq_ctx* c, int field) {
+  if (field == NQ_AVG_PHI) return c->kernel_family ? AVG_PHI : -1;
+  return hist_slot(c, field);
+}
+// one sample: the current state (what nq_field_hist bins) is added to every sum plane, one launch
+static int av_sample(nq_ctx* c, const char* what) {
+  NqAvg* A = c->av;
+  if (c->kernel_family ? !c->have_phi : !c->have_q) NQ_FAIL(c, -4, "%s: %s has not been called", what, c->kernel_family ? "set_phi" : "set_q");
+  if (c->kernel_family) {
+    launch_xmoments(c, A->args);
+  } else {
+    AvgSrc s = {};
+    hist_qg_planes(c, A->args.mask, &s.p[0], &s.p[1]);
+    s.stride[0] = s.stride[1] = 1;
+    const size_t n = (size_t)c->N * c->N;
+    hipLaunchKernelGGL(k_moments_plane, dim3(hist_plane_grid(n)), dim3(256), 0, c->stream, s, n, A->args);
+  }
+  HIPCHK(c, hipGetLastError());
+  ++A->rg.count;
+  return 0;
+}
+static int av_after_step(nq_ctx* c) {
+  return c->av->rg.tick() ? av_sample(c, "nq_step (averages)") : 0;
+}
+
 // ---- nq_step's hooks (declared below dev_alloc) ----------------------------------------------------------------------------
 // Before the step the particles form U0 from the state it starts from.  After it: the forcing first -- the forced, re-inverted
 // state is what the particles' U1 and the next step see -- then the particles, then the recorder, whose record of this step
-// is that same forced, re-inverted state.  The first non-zero return code ends the call.
+// is that same forced, re-inverted state, then the averages, which add that state to their sums.  The first non-zero return
+// code ends the call.
 static void attachments_before_step(nq_ctx* c) {
   if (c->pt) pt_before_step(c);
 }
@@ -5604,6 +5656,7 @@ static int attachments_after_step(nq_ctx* c) {
   int rc = c->fc ? fc_apply(c) : 0;
   if (!rc && c->pt) rc = pt_after_step(c);
   if (!rc && c->fq) rc = fq_after_step(c);
+  if (!rc && c->av) rc = av_after_step(c);
   return rc;
 }
 
@@ -5715,6 +5768,158 @@ int nq_freq_spectrum(nq_ctx* c, int field, const double* window, int demean, dou
   F->bytes += grown;
   c->bytes += grown;
   if (rc) NQ_FAIL(c, rc, "nq_freq_spectrum: %s", nq_any_last_error(F->eng));
+  return 0;
+}
+
+// ---- time-mean and covariance maps ---------------------------------------------------------------------
+int nq_avg_attach(nq_ctx* c, int nfields, const int* fields, int nproducts, const int* pairs, int every) {
+  NQ_SINGLE_RANK(c, "nq_avg_attach");
+  if (c->av) NQ_FAIL(c, -4, "nq_avg_attach: averages are attached already (nq_avg_detach first)");
+  if (!fields || nfields < 1 || nfields > AVG_SLOTS + 1) NQ_FAIL(c, -1, "nq_avg_attach: %d fields (1 to %d)", nfields, AVG_SLOTS + 1);
+  if (nproducts < 0 || nproducts > AVG_MAX_PRODUCTS || (nproducts > 0 && !pairs)) NQ_FAIL(c, -1, "nq_avg_attach: %d products (0 to %d)", nproducts, AVG_MAX_PRODUCTS);
+  if (every < 0) NQ_FAIL(c, -1, "nq_avg_attach: every = %d (>= 0)", every);
+  int mask = 0;
+  for (int i = 0; i < nfields; ++i) {
+    const int s = av_slot(c, fields[i]);
+    if (s < 0)
+      NQ_FAIL(c, -1, "nq_avg_attach: field %d is not available here (Kernel family: NQ_AVG_Q, NQ_AVG_QPSI, NQ_AVG_PHI2, NQ_AVG_PHI; QGModel: NQ_AVG_Q, with its passive scalar NQ_AVG_C)", fields[i]);
+    if (mask & (1 << s)) NQ_FAIL(c, -1, "nq_avg_attach: field %d listed twice", fields[i]);
+    mask |= 1 << s;
+  }
+  int pa[AVG_MAX_PRODUCTS], pb[AVG_MAX_PRODUCTS];
+  for (int p = 0; p < nproducts; ++p) {
+    int s[2];
+    for (int k = 0; k < 2; ++k) {
+      const int f = pairs[2 * p + k];
+      s[k] = f == NQ_AVG_PHI ? -1 : av_slot(c, f);
+      if (s[k] < 0 || !(mask & (1 << s[k])))
+        NQ_FAIL(c, -1, "nq_avg_attach: product %d names field %d, which is not a real field of the list", p, f);
+    }
+    pa[p] = s[0] < s[1] ? s[0] : s[1];
+    pb[p] = s[0] < s[1] ? s[1] : s[0];
+    for (int o = 0; o < p; ++o)
+      if (pa[o] == pa[p] && pb[o] == pb[p]) NQ_FAIL(c, -1, "nq_avg_attach: the pair (%d, %d) is listed twice", pairs[2 * p], pairs[2 * p + 1]);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  c->av = new NqAvg();
+  NqAvg* A = c->av;
+  A->nf = nfields;
+  A->np = nproducts;
+  A->rg.init(1, every);
+  A->args.mask = mask;
+  A->args.np = nproducts;
+  const size_t n = (size_t)c->N * c->N;
+  int rc = 0;
+  for (int i = 0; i < nfields && !rc; ++i) {
+    const int s = av_slot(c, fields[i]);
+    A->field[i] = fields[i];
+    if (s == AVG_PHI) {
+      rc = att_alloc(c, A, &A->args.sum_phi, n, "nq_avg_attach");
+      A->plane[i] = A->args.sum_phi;
+    } else {
+      rc = att_alloc(c, A, &A->args.sum[s], n, "nq_avg_attach");
+      A->plane[i] = A->args.sum[s];
+    }
+  }
+  for (int p = 0; p < nproducts && !rc; ++p) {
+    A->args.pa[p] = pa[p];
+    A->args.pb[p] = pb[p];
+    rc = att_alloc(c, A, &A->args.prod[p], n, "nq_avg_attach");
+    A->plane[nfields + p] = A->args.prod[p];
+  }
+  if (rc) return att_fail(c, c->av, rc);
+  return 0;
+}
+int nq_avg_detach(nq_ctx* c) {
+  NQ_SINGLE_RANK(c, "nq_avg_detach");
+  if (!c->av) NQ_FAIL(c, -4, "nq_avg_detach: no averages attached");
+  att_release(c, c->av);
+  return 0;
+}
+int nq_avg_sample(nq_ctx* c) {
+  NQ_SINGLE_RANK(c, "nq_avg_sample");
+  if (!c->av) NQ_FAIL(c, -4, "nq_avg_sample: no averages attached");
+  HIPCHK(c, hipSetDevice(c->device));
+  return av_sample(c, "nq_avg_sample");
+}
+int nq_avg_reset(nq_ctx* c) {
+  NQ_SINGLE_RANK(c, "nq_avg_reset");
+  NqAvg* A = c->av;
+  if (!A) NQ_FAIL(c, -4, "nq_avg_reset: no averages attached");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n = (size_t)c->N * c->N;
+  for (int i = 0; i < A->nf + A->np; ++i)
+    HIPCHK(c, hipMemsetAsync(A->plane[i], 0, (A->plane[i] == (void*)A->args.sum_phi ? sizeof(cd) : sizeof(double)) * n, c->stream));
+  A->rg.count = 0;
+  return 0;
+}
+int nq_avg_info(nq_ctx* c, long long* info3) {
+  NQ_SINGLE_RANK(c, "nq_avg_info");
+  NqAvg* A = c->av;
+  if (!A) NQ_FAIL(c, -4, "nq_avg_info: no averages attached");
+  if (!info3) return -1;
+  info3[0] = A->rg.count;
+  info3[1] = A->rg.steps;
+  info3[2] = A->nf + A->np;
+  return 0;
+}
+int nq_avg_read(nq_ctx* c, int plane_index, double* out) {
+  NQ_SINGLE_RANK(c, "nq_avg_read");
+  NqAvg* A = c->av;
+  if (!A) NQ_FAIL(c, -4, "nq_avg_read: no averages attached");
+  if (!out) return -1;
+  if (plane_index < 0 || plane_index >= A->nf + A->np) NQ_FAIL(c, -1, "nq_avg_read: plane %d of %d", plane_index, A->nf + A->np);
+  HIPCHK(c, hipSetDevice(c->device));
+  const void* src = A->plane[plane_index];
+  const size_t bytes = (src == (const void*)A->args.sum_phi ? sizeof(cd) : sizeof(double)) * (size_t)c->N * c->N;
+  HIPCHK(c, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  return nq_sync(c);
+}
+// One sample on engine planes (the any-size path steps from Python and calls this after its own step): the rule and the kernel of
+// QGModel's fused contexts.  src[i] (complex engine planes of `elems` values) read as what[i] (0: Re, 1: |a|^2, 2: the complex
+// value itself, at most once and in no product) is added to sums[i] (elems doubles; what 2: elems complex); pairs: 2 x nproducts
+// indices into src (what 0 or 1), psums[p] += their product.
+int nq_any_moments(nq_any* e, long long elems, int nfields, const void* const* src, const int* what, void* const* sums, int nproducts,
+                   const int* pairs, void* const* psums) {
+  if (!e || !src || !what || !sums || elems <= 0 || (nproducts > 0 && (!pairs || !psums))) return -1;
+  if (nfields < 1 || nfields > AVG_SLOTS + 1) ANYFAIL(e, -1, "nq_any_moments: %d fields (1 to %d)", nfields, AVG_SLOTS + 1);
+  if (nproducts < 0 || nproducts > AVG_MAX_PRODUCTS) ANYFAIL(e, -1, "nq_any_moments: %d products (0 to %d)", nproducts, AVG_MAX_PRODUCTS);
+  AvgSrc s = {};
+  AvgArgs a = {};
+  int slot_of[AVG_SLOTS + 1], nreal = 0;
+  for (int i = 0; i < nfields; ++i) {
+    if (!src[i] || !sums[i]) return -1;
+    if (what[i] == 2) {
+      if (a.mask & (1 << AVG_PHI)) ANYFAIL(e, -1, "nq_any_moments: more than one complex field");
+      a.mask |= 1 << AVG_PHI;
+      s.phi = reinterpret_cast<const cd*>(src[i]);
+      a.sum_phi = reinterpret_cast<cd*>(sums[i]);
+      slot_of[i] = -1;
+    } else if (what[i] == 0 || what[i] == 1) {
+      if (nreal == AVG_SLOTS) ANYFAIL(e, -1, "nq_any_moments: more than %d real fields", AVG_SLOTS);
+      a.mask |= 1 << nreal;
+      s.p[nreal] = reinterpret_cast<const double*>(src[i]);
+      s.stride[nreal] = 2;
+      s.what[nreal] = what[i];
+      a.sum[nreal] = reinterpret_cast<double*>(sums[i]);
+      slot_of[i] = nreal++;
+    } else {
+      ANYFAIL(e, -1, "nq_any_moments: what = %d (0: Re, 1: |a|^2, 2: complex)", what[i]);
+    }
+  }
+  a.np = nproducts;
+  for (int p = 0; p < nproducts; ++p) {
+    const int ia = pairs[2 * p], ib = pairs[2 * p + 1];
+    if (ia < 0 || ia >= nfields || ib < 0 || ib >= nfields || slot_of[ia] < 0 || slot_of[ib] < 0 || !psums[p])
+      ANYFAIL(e, -1, "nq_any_moments: product %d does not name two real fields of the list", p);
+    a.pa[p] = slot_of[ia];
+    a.pb[p] = slot_of[ib];
+    a.prod[p] = reinterpret_cast<double*>(psums[p]);
+  }
+  ANYCHK(e, hipSetDevice(e->device));
+  const size_t n = (size_t)elems;
+  hipLaunchKernelGGL(k_moments_plane, dim3(hist_plane_grid(n)), dim3(256), 0, e->stream, s, n, a);
+  ANYCHK(e, hipGetLastError());
   return 0;
 }
 
