@@ -33,6 +33,12 @@ if case == "particles":
     from niwqg_amd import particles
     rng = np.random.default_rng(5)
     P = particles.attach(m, rng.uniform(0, m.L, 1000), rng.uniform(0, m.L, 1000))
+F = R = A = None
+if case == "attachments":                               # the forcing tail, the recorder and the averages, in their hook order
+    from niwqg_amd import forcing, frequency, averages
+    F = forcing.attach(m, q=forcing.ring(m, 16 * m.dk, 2 * m.dk, 8e-11), phi=forcing.ring(m, 12 * m.dk, 2 * m.dk, 1e-9, field="phi"), seed=17)
+    R = frequency.attach(m, 8, every=2, length=3)
+    A = averages.attach(m, ("q_psi", "phi2"), (("q_psi", "phi2"),), every=2)
 # the increments themselves: m.Ke, m.Pw, m.Kw start from set_q / set_phi's atomic device sums, whose last bits differ between
 # any two runs
 bud, cfl = [], []
@@ -49,6 +55,14 @@ res.update(qh=np.array(m.qh), phih=np.array(m.phih), budgets=np.array(bud), cfl=
 if P is not None:
     x, y = P.positions()
     res.update(px=np.array(x), py=np.array(y))
+if F is not None:
+    w = F.work()
+    res.update(work=np.array([w["q"], w["phi"]]), forcing_step=np.array(F.state()["step"]))
+    for n in R.fields:
+        ts = R.series(n)
+        res["series_" + n], res["series_step_" + n] = ts.values, ts.step
+    S = A.result()
+    res.update(avg_n=np.array(S.n), **{"avg_" + k.replace("*", "_"): v for k, v in S.sums.items() if k != "phi2*q_psi"})
 np.savez(out, **res)
 """
 
@@ -67,7 +81,7 @@ def run_case(tmp_path, case, setting):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("case", ["plain", "particles", "ticks"])
+@pytest.mark.parametrize("case", ["plain", "particles", "ticks", "attachments"])
 def test_default_step_equals_the_serial_step_bit_for_bit(tmp_path, case):
     a = run_case(tmp_path, case, None)
     b = run_case(tmp_path, case, "0")
@@ -78,6 +92,12 @@ def test_default_step_equals_the_serial_step_bit_for_bit(tmp_path, case):
     assert list(b["info"]) == [0, 0, 0]
     assert a["budgets"].shape == (8, 3) and np.isfinite(a["budgets"]).all() and np.abs(a["budgets"]).max() > 0 and np.abs(a["qh"]).max() > 0 and (a["cfl"][[3, 7]] > 0).all()
     names = ["qh", "phih", "budgets", "cfl", "cfl_now"] + (["px", "py"] if case == "particles" else [])
+    if case == "attachments":
+        # the forcing writes the q-hat the second stream has just produced and re-inverts; the recorder (records 4, 6, 8 after the
+        # wrap) and the averages (four samples) read what that leaves
+        assert np.all(a["work"] != 0) and a["forcing_step"] == 8 and a["avg_n"] == 4
+        assert np.array_equal(a["series_step_phi"], [4, 6, 8]) and np.abs(a["series_q"]).max() > 0 and np.abs(a["avg_q_psi_phi2"]).max() > 0
+        names += ["work", "forcing_step"] + sorted(k for k in a.files if k.startswith(("series_", "avg_")))
     for k in names:
         print(case, k, "max |default - serial| =", np.abs(a[k] - b[k]).max())
     for k in names:
