@@ -245,8 +245,17 @@ int nq_transfer_binned(nq_ctx* ctx, int nb, double* out);
  * Integer counters only (32-bit in LDS per workgroup, 64-bit in global memory): bit-reproducible.  The Kernel family writes no
  * physical plane; QGModel goes through the scratch planes of nq_get_field.  The first call allocates the tables of the largest
  * configuration and the min/max partials, NQ_PDF_DEVICE_BYTES in all (counted by nq_device_bytes, freed with the context).
- * Reads the state, writes only these buffers.  Single-rank contexts (-4 on slab contexts).                                    */
+ * Reads the state, writes only these buffers.  Single-rank contexts (-4 on slab contexts).
+ *
+ * Flow fields, Kernel family only, one numbering for nq_field_minmax, nq_field_hist and nq_avg_attach:
+ * NQ_FLOW_U u, NQ_FLOW_V v, NQ_FLOW_SN the normal strain 2 u_x, NQ_FLOW_SS the shear strain 2 v_x - q_psi, NQ_FLOW_STRAIN2 = sn^2 +
+ * ss^2, NQ_FLOW_OW = strain2 - q_psi^2 (Okubo-Weiss), NQ_FLOW_GRADPHI2 = |phi_x|^2 + |phi_y|^2 of the current phi-hat; all of the
+ * last inversion's rows, like NQ_PDF_QPSI.  They may be mixed with the three fields above; a list that names one runs ONE row
+ * pass (k_x_flow_hist / k_x_flow_moments) for all of its fields, a list that names none runs the kernels it always ran.  A flow
+ * field on a QGModel context is -1.  At nx = 8192 a device thread holds one value and every field of such a list runs in a launch
+ * of its own: a joint table, or a product of two different fields in nq_avg_attach, is -1 there.                              */
 enum { NQ_PDF_Q = 0, NQ_PDF_QPSI = 1, NQ_PDF_PHI2 = 2, NQ_PDF_C = 3 };
+enum { NQ_FLOW_U = 16, NQ_FLOW_V = 17, NQ_FLOW_SN = 18, NQ_FLOW_SS = 19, NQ_FLOW_STRAIN2 = 20, NQ_FLOW_OW = 21, NQ_FLOW_GRADPHI2 = 22 };
 #define NQ_PDF_MAX_BINS 1024
 #define NQ_PDF_MAX_JOINT_BINS 128
 #define NQ_PDF_DEVICE_BYTES ((3 * (NQ_PDF_MAX_BINS + 3) + NQ_PDF_MAX_JOINT_BINS * NQ_PDF_MAX_JOINT_BINS + 1) * 8 + 6 * 8192 * 8)
@@ -341,7 +350,8 @@ int nq_freq_spectrum(nq_ctx* ctx, int field, const double* window, int demean, d
  * sample takes one now; reset zeroes the sums and the sample count, not the step count.  One set per context (-4 while one is
  * attached).  Every allocation is counted by nq_device_bytes and freed by detach; one that fails is an error (-5) that leaves
  * nothing attached.  info3 = {samples in the sums, steps since attach, planes}; read: plane `plane_index` (fields in the order of
- * the attach call, then the products) into out, nx ny doubles (NQ_AVG_PHI: 2 nx ny).                                          */
+ * the attach call, then the products) into out, nx ny doubles (NQ_AVG_PHI: 2 nx ny).  The Kernel family also takes the NQ_FLOW_*
+ * fields above (at most three real fields in all, as ever).                                                                   */
 enum { NQ_AVG_Q = 0, NQ_AVG_QPSI = 1, NQ_AVG_PHI2 = 2, NQ_AVG_C = 3, NQ_AVG_PHI = 4 };      /* the first four: NQ_PDF_* */
 int nq_avg_attach(nq_ctx* ctx, int nfields, const int* fields, int nproducts, const int* pairs, int every);
 int nq_avg_detach(nq_ctx* ctx);

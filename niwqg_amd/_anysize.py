@@ -348,6 +348,28 @@ class _Stepping(object):
             save_diagnostics(self)
 
 
+def _flow_planes(names, ph, K, to_real, q_psi, ifft=None, phih=None):
+    """{name: (plane, what)} of the flow fields (niwqg_amd/flow.py: reference states them) from psi-hat, the
+    class's own inverse transform to a real plane and its q_psi plane; gradphi2 from phi-hat through the complex inverse"""
+    out, need = {}, set(names)
+    if "u" in need:
+        out["u"] = (to_real(K["mil"] * ph), 0)
+    if "v" in need:
+        out["v"] = (to_real(K["ik"] * ph), 0)
+    if need & {"sn", "ss", "strain2", "ow"}:
+        sn = to_real(K["ik"] * (K["mil"] * ph)) * 2.0
+        ss = to_real(K["ik"] * (K["ik"] * ph)) * 2.0 - q_psi
+        strain2 = sn * sn + ss * ss
+        for n, v in (("sn", sn), ("ss", ss), ("strain2", strain2)):
+            if n in need:
+                out[n] = (v, 0)
+        if "ow" in need:
+            out["ow"] = (strain2 - q_psi * q_psi, 0)
+    if "gradphi2" in need:
+        out["gradphi2"] = (ifft(K["ik"] * phih).abs2() + ifft(K["il"] * phih).abs2(), 0)
+    return out
+
+
 class KernelFamily(_Stepping):
     """Mix-in over niwqg_amd.Kernel.Kernel (CoupledModel / UnCoupledModel / YBJModel) for grids without a fused plan: every
     method that touches the device is restated on planes, in the reference's own order of operations."""
@@ -718,6 +740,10 @@ class KernelFamily(_Stepping):
                 out[n] = (d["q"] - self._ifft(d["qwh"]).real if self.model_id == _lib.COUPLED else d["q"], 0)
             elif n == "phi2":
                 out[n] = (d["phi"], 1)
+        flow = [n for n in names if n not in out]
+        if flow:
+            q_psi = out["q_psi"][0] if "q_psi" in out else self._pdf_planes(["q_psi"])["q_psi"][0]
+            out.update(_flow_planes(flow, d["ph"], self._K, lambda a: self._ifft(a).real, q_psi, self._ifft, d["phih"]))
         return out
 
     # ---- spectral transfer (niwqg_amd/transfer.py) ----------------------------------------------
@@ -1115,7 +1141,11 @@ class QGFamily(_Stepping):
     # ---- PDFs of the physical fields (niwqg_amd/pdfs.py) ------------------------------------------
     def _pdf_planes(self, names):
         """{name: (plane, what)} for nq_any_hist: q and c are the real planes this path holds (current after every step)"""
-        return {n: (self._d[n], 0) for n in names}
+        out = {n: (self._d[n], 0) for n in names if n in ("q", "c")}
+        flow = [n for n in names if n not in out]
+        if flow:                           # q_psi = q here: the vorticity of psi
+            out.update(_flow_planes(flow, self._d["ph"], self._K, self._irfft, self._d["q"]))
+        return out
 
     def _calc_derived_fields(self):     # ref: niwqg/QGModel.py:724-737
         if self.passive_scalar:

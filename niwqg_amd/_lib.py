@@ -20,7 +20,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # NIWQG_AMD_LIB: another build of the same sources (A/B experiments with compile-time knobs, tools/); default: the in-tree library
 LIB_PATH = os.environ.get("NIWQG_AMD_LIB") or os.path.join(HERE, "libniwqg_amd.so")
 SRC = os.path.join(HERE, "csrc", "nq_lib.hip")
-HEADERS = [os.path.join(HERE, "csrc", h) for h in ("nq_fft.hpp", "nq_generic.hpp", "nq_step.hpp", "nq_anysize.hpp", "nq_particles.hpp", "nq_forcing.hpp", "nq_hist.hpp", "nq_freq.hpp", "nq_avg.hpp")] + [
+HEADERS = [os.path.join(HERE, "csrc", h) for h in ("nq_fft.hpp", "nq_generic.hpp", "nq_step.hpp", "nq_anysize.hpp", "nq_particles.hpp", "nq_forcing.hpp", "nq_hist.hpp", "nq_freq.hpp", "nq_avg.hpp", "nq_flow.hpp")] + [
     os.path.join(os.path.dirname(HERE), "include", "niwqg_amd.h")]
 
 COUPLED, UNCOUPLED, QG, YBJ = 0, 1, 2, 3
@@ -51,6 +51,7 @@ PDF_MAX_BINS, PDF_MAX_JOINT_BINS = 1024, 128
 PDF_DEVICE_BYTES = (3 * (PDF_MAX_BINS + 3) + PDF_MAX_JOINT_BINS ** 2 + 1) * 8 + 6 * 8192 * 8     # NQ_PDF_DEVICE_BYTES
 
 (AVG_Q, AVG_QPSI, AVG_PHI2, AVG_C, AVG_PHI) = range(5)      # fields of nq_avg_attach (include/niwqg_amd.h: NQ_AVG_*)
+(FLOW_U, FLOW_V, FLOW_SN, FLOW_SS, FLOW_STRAIN2, FLOW_OW, FLOW_GRADPHI2) = range(16, 23)      # NQ_FLOW_*: PDFs and averages alike
 
 TRANSFER_ROWS = 6                 # rows of nq_transfer_binned (include/niwqg_amd.h: NQ_TRANSFER_ROWS)
 

@@ -29,10 +29,12 @@ import ctypes
 
 import numpy as np
 
-from . import _attach, _lib, pdfs
+from . import _attach, _lib, flow, pdfs
 
 _CODES = {"q": _lib.AVG_Q, "q_psi": _lib.AVG_QPSI, "phi2": _lib.AVG_PHI2, "c": _lib.AVG_C, "phi": _lib.AVG_PHI}
+_CODES.update(flow.CODES)           # the flow fields (flow.py): taken by name only
 MAX_PRODUCTS = 6
+MAX_REAL = 3                        # real fields of one attachment: the value registers of the row pass
 
 
 def available(m):
@@ -70,6 +72,8 @@ def check(valid, fields, products=(), every=1):
     bad = [n for n in fields if n not in valid]
     if bad or not fields or len(set(fields)) != len(fields):
         raise ValueError("averages.attach: fields %r; valid names (each once): %s" % (fields, ", ".join(valid)))
+    if len([n for n in fields if n != "phi"]) > MAX_REAL:
+        raise ValueError("averages.attach: fields %r; valid: at most %d real fields (and phi)" % (fields, MAX_REAL))
     pairs, seen = [], set()
     for p in products:
         p = tuple(p) if not isinstance(p, str) else (p,)
@@ -257,6 +261,8 @@ def attach(m, fields, products=(), every=1):
     ``products``, zero at attach, a sample after every ``every``-th step (0: only ``sample()``).  The largest configuration, four
     fields and six products, is eleven real planes: 88 bytes per grid point.  Argument errors raise ValueError before the device
     is touched, a second attach RuntimeError, slab-decomposed models NotImplementedError."""
-    fields, products, every = check(available(m), fields, products, every)
+    if any(n in flow.NAMES for n in ([fields] if isinstance(fields, str) else fields) if isinstance(n, str)):
+        flow.refuse(m, "averages.attach", linked=any(len(set(p)) > 1 for p in products if not isinstance(p, str)))
+    fields, products, every = check(available(m) + flow.available(m), fields, products, every)
     return _attach.attach(m, _AnySize, _Fused, fields, products, every)
 

@@ -14,6 +14,7 @@
 #include "nq_particles.hpp"
 #include "nq_hist.hpp"
 #include "nq_avg.hpp"
+#include "nq_flow.hpp"
 #include "nq_forcing.hpp"
 
 using namespace nq;
@@ -116,6 +117,8 @@ struct NqAvg : DevOwned {                  // time-mean and covariance maps (sec
   int field[AVG_SLOTS + 1] = {0, 0, 0, 0};          // public ids, in the order of the attach call: the planes nq_avg_read counts
   void* plane[AVG_SLOTS + 1 + AVG_MAX_PRODUCTS] = {};       // fields first (phi: a complex plane), then the products
   AvgArgs args = {};
+  bool flow = false;                       // a flow field is listed: the samples run k_x_flow_moments with `sel` (section 5m)
+  FlowSel sel = {};
   RecordRing rg;                           // cap = 1: only tick() and the two counters are used (count = samples in the sums)
 };
 
@@ -198,7 +201,7 @@ struct nq_ctx {
   // allocated by the first call; the configuration of the last binning call (what nq_field_hist_read copies out)
   unsigned long long* hist_tab = nullptr;
   double* hist_part = nullptr;
-  struct HistCfg { int nf = 0, fields[4] = {0, 0, 0, 0}, bins = 0, jbins = 0, ja = -1, jb = -1; double lo[4] = {}, hi[4] = {}; } hist_cfg;
+  struct HistCfg { int nf = 0, fields[4] = {0, 0, 0, 0}, slot[4] = {0, 0, 0, 0}, bins = 0, jbins = 0, ja = -1, jb = -1; double lo[4] = {}, hi[4] = {}; } hist_cfg;
   cd *tr_h = nullptr, *tr_f = nullptr;               // its planes on slab contexts (two half, one full-width; P == 1: scr_*)
   double *carryW = nullptr, *carryQ = nullptr;    // spectral sums of the state at the start of the next step
   double *gradS1 = nullptr, *acc = nullptr;       // stale-aware sum wv2|phih_grad|^2 ; Ke,Pw,Kw increments
@@ -2299,6 +2302,33 @@ static void launch_xmoments_t(nq_ctx* c, const AvgArgs& a) {
 static void launch_xmoments(nq_ctx* c, const AvgArgs& a) {
   if (c->p.model == NQ_MODEL_COUPLED) launch_xmoments_t<MODE_COUPLED>(c, a);
   else launch_xmoments_t<MODE_UNCOUPLED>(c, a);
+}
+// the same two on the selected values of x_flow_values (csrc/nq_flow.hpp)
+template <int MODE, bool MINMAX>
+static void launch_xflow_hist_t(nq_ctx* c, const FlowSel& sel, const HistArgs& h, double* part) {
+  const int words = MINMAX ? 0 : hist_words(h.bins, h.jbins);
+  with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    typedef XPlan<N> X;
+    hipLaunchKernelGGL((k_x_flow_hist<N, MODE, false, MINMAX>), dim3(c->Nloc / X::C), dim3(X::THREADS), hist_lds_bytes<N>(words), c->stream, c->mQ, c->mQw, c->mU, c->mP, c->mPhi, c->mPhiy, c->twx, c->kk, sel, h, part);
+  });
+}
+template <bool MINMAX>
+static void launch_xflow_hist(nq_ctx* c, const FlowSel& sel, const HistArgs& h, double* part) {
+  if (c->p.model == NQ_MODEL_COUPLED) launch_xflow_hist_t<MODE_COUPLED, MINMAX>(c, sel, h, part);
+  else launch_xflow_hist_t<MODE_UNCOUPLED, MINMAX>(c, sel, h, part);
+}
+template <int MODE>
+static void launch_xflow_moments_t(nq_ctx* c, const FlowSel& sel, const AvgArgs& a) {
+  with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    typedef XPlan<N> X;
+    hipLaunchKernelGGL((k_x_flow_moments<N, MODE, false>), dim3(c->Nloc / X::C), dim3(X::THREADS), X::LDS_BYTES, c->stream, c->mQ, c->mQw, c->mU, c->mP, c->mPhi, c->mPhiy, c->twx, c->kk, sel, a);
+  });
+}
+static void launch_xflow_moments(nq_ctx* c, const FlowSel& sel, const AvgArgs& a) {
+  if (c->p.model == NQ_MODEL_COUPLED) launch_xflow_moments_t<MODE_COUPLED>(c, sel, a);
+  else launch_xflow_moments_t<MODE_UNCOUPLED>(c, sel, a);
 }
 static int hist_plane_grid(size_t n) { return (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024); }
 
@@ -4492,12 +4522,86 @@ static int hist_slot(const nq_ctx* c, int field) {
   if (field == NQ_PDF_Q) return 0;
   return (field == NQ_PDF_C && c->passive) ? 1 : -1;
 }
+// flow fields (csrc/nq_flow.hpp): Kernel family only, one numbering for the PDFs and the averages
+static_assert(NQ_FLOW_U == FLOW_U && NQ_FLOW_V == FLOW_V && NQ_FLOW_SN == FLOW_SN && NQ_FLOW_SS == FLOW_SS && NQ_FLOW_STRAIN2 == FLOW_STRAIN2 &&
+              NQ_FLOW_OW == FLOW_OW && NQ_FLOW_GRADPHI2 == FLOW_GRADPHI2 && NQ_PDF_Q == FLOW_Q && NQ_PDF_QPSI == FLOW_QPSI && NQ_PDF_PHI2 == FLOW_PHI2,
+              "public field ids and the kernel's value codes");
+static bool is_flow(int field) { return field >= FLOW_FIRST && field <= FLOW_LAST; }
+static bool any_flow(int nfields, const int* fields) {
+  for (int i = 0; i < nfields; ++i)
+    if (is_flow(fields[i])) return true;
+  return false;
+}
+// A list of old fields keeps hist_slot's fixed slots and the old kernels.  A list that names a flow field goes through
+// k_x_flow_hist for ALL of its fields: slot i is the i-th field of the list, and the selection says what each slot holds.
+static FlowSel flow_sel_none(const nq_ctx* c) {
+  FlowSel sel = {{FLOW_NONE, FLOW_NONE, FLOW_NONE}, 0, c->ph + (size_t)(c->N / 2) * c->Ph + c->N / 2, c->ll};
+  return sel;
+}
+// values one launch holds per point (csrc/nq_flow.hpp: flow_nv): a call that selects more is issued as one launch per value
+static int flow_nv_of(const nq_ctx* c) { return c->N >= 8192 ? 1 : HIST_SLOTS; }
+// the range pass (part[block][2 i], [2 i + 1] = minimum and maximum of fields[i]) or the counting pass (`h` is the call's: slot i
+// = field i) of a list that names a flow field
+static void flow_hist_launch(nq_ctx* c, bool minmax, const FlowSel& sel, const HistArgs& h, double* part) {
+  if (minmax) launch_xflow_hist<true>(c, sel, h, part);
+  else launch_xflow_hist<false>(c, sel, h, part);
+}
+static void flow_hist(nq_ctx* c, bool minmax, int nfields, const int* fields, const HistArgs& h, double* part) {
+  if (nfields <= flow_nv_of(c)) {
+    FlowSel sel = flow_sel_none(c);
+    for (int i = 0; i < nfields; ++i) sel.code[i] = fields[i];
+    flow_hist_launch(c, minmax, sel, h, part);
+    return;
+  }
+  for (int i = 0; i < nfields; ++i) {               // one value per launch, in the launch's slot 0 (no joint table: refused before)
+    FlowSel sel = flow_sel_none(c);
+    sel.code[0] = fields[i];
+    HistArgs g = {};
+    if (!minmax) {
+      g.bins = h.bins;
+      g.mask = 1;
+      g.lo[0] = h.lo[i];
+      g.hi[0] = h.hi[i];
+      g.s[0] = h.s[i];
+      g.tab = h.tab + (size_t)i * (h.bins + 3);
+    }
+    flow_hist_launch(c, minmax, sel, g, minmax ? part + 2 * i : nullptr);
+  }
+}
+// one sample of the averages of an attachment that names a flow field (`a`, `sel`: slot s = its s-th real field)
+static void flow_moments(nq_ctx* c, const FlowSel& sel, const AvgArgs& a) {
+  int nreal = 0;
+  for (int i = 0; i < HIST_SLOTS; ++i) nreal += sel.code[i] != FLOW_NONE;
+  if (nreal <= flow_nv_of(c)) {
+    launch_xflow_moments(c, sel, a);
+    return;
+  }
+  for (int f = 0; f < nreal; ++f) {                 // one value per launch: its sum and its own second moment (mixed products: refused)
+    FlowSel s = flow_sel_none(c);
+    s.code[0] = sel.code[f];
+    AvgArgs g = {};
+    if (a.mask & (1 << f)) {
+      g.mask = 1;
+      g.sum[0] = a.sum[f];
+    }
+    for (int p = 0; p < a.np; ++p)
+      if (a.pa[p] == f && a.pb[p] == f) g.prod[g.np++] = a.prod[p];       // pa = pb = 0
+    if (f == 0 && (a.mask & (1 << AVG_PHI))) {
+      g.mask |= 1 << AVG_PHI;
+      g.sum_phi = a.sum_phi;
+      s.phi = 1;
+    }
+    launch_xflow_moments(c, s, g);
+  }
+}
 static int hist_check_fields(nq_ctx* c, const char* what, int nfields, const int* fields) {
   NQ_SINGLE_RANK(c, "nq_field_hist");
   if (!fields || nfields < 1 || nfields > HIST_SLOTS) NQ_FAIL(c, -1, "%s: %d fields (1 to %d)", what, nfields, HIST_SLOTS);
   for (int i = 0; i < nfields; ++i) {
-    if (hist_slot(c, fields[i]) < 0)
-      NQ_FAIL(c, -1, "%s: field %d is not available here (Kernel family: NQ_PDF_Q, NQ_PDF_QPSI, NQ_PDF_PHI2; QGModel: NQ_PDF_Q, with its passive scalar NQ_PDF_C)", what, fields[i]);
+    if (is_flow(fields[i]) && !c->kernel_family)
+      NQ_FAIL(c, -1, "%s: flow field %d (NQ_FLOW_*) on a QGModel context: its plane route has no velocity or strain values yet (DESIGN.md section 7)", what, fields[i]);
+    if (!is_flow(fields[i]) && hist_slot(c, fields[i]) < 0)
+      NQ_FAIL(c, -1, "%s: field %d is not available here (Kernel family: NQ_PDF_Q, NQ_PDF_QPSI, NQ_PDF_PHI2 and the NQ_FLOW_* fields; QGModel: NQ_PDF_Q, with its passive scalar NQ_PDF_C)", what, fields[i]);
     for (int k = 0; k < i; ++k)
       if (fields[k] == fields[i]) NQ_FAIL(c, -1, "%s: field %d listed twice", what, fields[i]);
   }
@@ -4536,11 +4640,13 @@ int nq_field_minmax(nq_ctx* c, int nfields, const int* fields, double* out) {
     if (rc) return rc;
   }
   int nblk, per;
+  const bool flow = any_flow(nfields, fields);
   if (c->kernel_family) {
     HistArgs h = {};
     nblk = xdiag_blocks(c);
     per = 6;
-    launch_xhist<true>(c, h, c->hist_part);
+    if (flow) flow_hist(c, true, nfields, fields, h, c->hist_part);
+    else launch_xhist<true>(c, h, c->hist_part);
   } else {
     int mask = 0;
     for (int i = 0; i < nfields; ++i) mask |= 1 << hist_slot(c, fields[i]);
@@ -4559,7 +4665,7 @@ int nq_field_minmax(nq_ctx* c, int nfields, const int* fields, double* out) {
     if (rc) return rc;
   }
   for (int i = 0; i < nfields; ++i) {
-    const int s = hist_slot(c, fields[i]);
+    const int s = flow ? i : hist_slot(c, fields[i]);
     double lo = part[2 * s], hi = part[2 * s + 1];
     for (int k = 1; k < nblk; ++k) {                    // NaN in any workgroup's slot stays (min and max: order is irrelevant)
       const double a = part[(size_t)k * per + 2 * s], b = part[(size_t)k * per + 2 * s + 1];
@@ -4594,6 +4700,9 @@ int nq_field_hist(nq_ctx* c, int nfields, const int* fields, const double* lo, c
   for (int i = 0; i < nfields; ++i)
     if (!std::isfinite(lo[i]) || !std::isfinite(hi[i]) || !(lo[i] < hi[i]))
       NQ_FAIL(c, -1, "nq_field_hist: range [%g, %g] of field %d (finite, lo < hi)", lo[i], hi[i], fields[i]);
+  const bool flow = any_flow(nfields, fields);
+  if (flow && joint && nfields > flow_nv_of(c))
+    NQ_FAIL(c, -1, "nq_field_hist: a joint table with flow fields (NQ_FLOW_*) at nx = %d: a thread of that row plan holds one value, the pair needs two (DESIGN.md section 7)", c->N);
   nq_ctx::HistCfg cfg;
   cfg.nf = nfields;
   cfg.bins = bins;
@@ -4602,6 +4711,7 @@ int nq_field_hist(nq_ctx* c, int nfields, const int* fields, const double* lo, c
   cfg.jb = jb;
   for (int i = 0; i < nfields; ++i) {
     cfg.fields[i] = fields[i];
+    cfg.slot[i] = flow ? i : hist_slot(c, fields[i]);
     cfg.lo[i] = lo[i];
     cfg.hi[i] = hi[i];
   }
@@ -4621,22 +4731,23 @@ int nq_field_hist(nq_ctx* c, int nfields, const int* fields, const double* lo, c
   h.jbins = cfg.jbins;
   h.tab = c->hist_tab;
   for (int i = 0; i < nfields; ++i) {
-    const int s = hist_slot(c, fields[i]);
+    const int s = cfg.slot[i];
     h.mask |= 1 << s;
     h.lo[s] = lo[i];
     h.hi[s] = hi[i];
     h.s[s] = (double)bins / (hi[i] - lo[i]);
   }
   if (joint) {
-    h.ja = hist_slot(c, joint_a);
-    h.jb = hist_slot(c, joint_b);
+    h.ja = cfg.slot[ja];
+    h.jb = cfg.slot[jb];
     h.js[0] = (double)joint_bins / (hi[ja] - lo[ja]);
     h.js[1] = (double)joint_bins / (hi[jb] - lo[jb]);
   }
   const int words = hist_words(h.bins, h.jbins);
   if (!accumulate) HIPCHK(c, hipMemsetAsync(c->hist_tab, 0, sizeof(unsigned long long) * words, c->stream));
   if (c->kernel_family) {
-    launch_xhist<false>(c, h, nullptr);
+    if (flow) flow_hist(c, false, nfields, fields, h, nullptr);
+    else launch_xhist<false>(c, h, nullptr);
   } else {
     const double *a, *b;
     hist_qg_planes(c, h.mask, &a, &b);
@@ -4656,7 +4767,7 @@ int nq_field_hist_read(nq_ctx* c, unsigned long long* out) {
   HIPCHK(c, hipSetDevice(c->device));
   const size_t per = (size_t)g.bins + 3;
   for (int i = 0; i < g.nf; ++i)
-    HIPCHK(c, hipMemcpyAsync(out + i * per, c->hist_tab + hist_slot(c, g.fields[i]) * per, sizeof(unsigned long long) * per, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out + i * per, c->hist_tab + g.slot[i] * per, sizeof(unsigned long long) * per, hipMemcpyDeviceToHost, c->stream));
   if (g.jbins)
     HIPCHK(c, hipMemcpyAsync(out + g.nf * per, c->hist_tab + HIST_SLOTS * per, sizeof(unsigned long long) * ((size_t)g.jbins * g.jbins + 1), hipMemcpyDeviceToHost, c->stream));
   return nq_sync(c);
@@ -5628,7 +5739,8 @@ static int av_sample(nq_ctx* c, const char* what) {
   NqAvg* A = c->av;
   if (c->kernel_family ? !c->have_phi : !c->have_q) NQ_FAIL(c, -4, "%s: %s has not been called", what, c->kernel_family ? "set_phi" : "set_q");
   if (c->kernel_family) {
-    launch_xmoments(c, A->args);
+    if (A->flow) flow_moments(c, A->sel, A->args);
+    else launch_xmoments(c, A->args);
   } else {
     AvgSrc s = {};
     hist_qg_planes(c, A->args.mask, &s.p[0], &s.p[1]);
@@ -5778,12 +5890,29 @@ int nq_avg_attach(nq_ctx* c, int nfields, const int* fields, int nproducts, cons
   if (!fields || nfields < 1 || nfields > AVG_SLOTS + 1) NQ_FAIL(c, -1, "nq_avg_attach: %d fields (1 to %d)", nfields, AVG_SLOTS + 1);
   if (nproducts < 0 || nproducts > AVG_MAX_PRODUCTS || (nproducts > 0 && !pairs)) NQ_FAIL(c, -1, "nq_avg_attach: %d products (0 to %d)", nproducts, AVG_MAX_PRODUCTS);
   if (every < 0) NQ_FAIL(c, -1, "nq_avg_attach: every = %d (>= 0)", every);
-  int mask = 0;
+  // slots: a list of old fields keeps av_slot's; one that names a flow field (Kernel family) takes the real fields in list order
+  const bool flow = any_flow(nfields, fields);
+  int mask = 0, slot[AVG_SLOTS + 1], nreal = 0;
+  FlowSel sel = flow_sel_none(c);
   for (int i = 0; i < nfields; ++i) {
-    const int s = av_slot(c, fields[i]);
+    if (is_flow(fields[i]) && !c->kernel_family)
+      NQ_FAIL(c, -1, "nq_avg_attach: flow field %d (NQ_FLOW_*) on a QGModel context: its plane route has no velocity or strain values yet (DESIGN.md section 7)", fields[i]);
+    int s = is_flow(fields[i]) ? 0 : av_slot(c, fields[i]);
     if (s < 0)
-      NQ_FAIL(c, -1, "nq_avg_attach: field %d is not available here (Kernel family: NQ_AVG_Q, NQ_AVG_QPSI, NQ_AVG_PHI2, NQ_AVG_PHI; QGModel: NQ_AVG_Q, with its passive scalar NQ_AVG_C)", fields[i]);
-    if (mask & (1 << s)) NQ_FAIL(c, -1, "nq_avg_attach: field %d listed twice", fields[i]);
+      NQ_FAIL(c, -1, "nq_avg_attach: field %d is not available here (Kernel family: NQ_AVG_Q, NQ_AVG_QPSI, NQ_AVG_PHI2, NQ_AVG_PHI and the NQ_FLOW_* fields; QGModel: NQ_AVG_Q, with its passive scalar NQ_AVG_C)", fields[i]);
+    for (int k = 0; k < i; ++k)
+      if (fields[k] == fields[i]) NQ_FAIL(c, -1, "nq_avg_attach: field %d listed twice", fields[i]);
+    if (s != AVG_PHI) {
+      if (nreal == AVG_SLOTS) NQ_FAIL(c, -1, "nq_avg_attach: more than %d real fields", AVG_SLOTS);
+      if (flow) {
+        s = nreal;
+        sel.code[s] = fields[i];
+      }
+      ++nreal;
+    } else {
+      sel.phi = 1;
+    }
+    slot[i] = s;
     mask |= 1 << s;
   }
   int pa[AVG_MAX_PRODUCTS], pb[AVG_MAX_PRODUCTS];
@@ -5791,12 +5920,16 @@ int nq_avg_attach(nq_ctx* c, int nfields, const int* fields, int nproducts, cons
     int s[2];
     for (int k = 0; k < 2; ++k) {
       const int f = pairs[2 * p + k];
-      s[k] = f == NQ_AVG_PHI ? -1 : av_slot(c, f);
-      if (s[k] < 0 || !(mask & (1 << s[k])))
+      s[k] = -1;
+      for (int i = 0; i < nfields; ++i)
+        if (fields[i] == f && slot[i] != AVG_PHI) s[k] = slot[i];
+      if (s[k] < 0)
         NQ_FAIL(c, -1, "nq_avg_attach: product %d names field %d, which is not a real field of the list", p, f);
     }
     pa[p] = s[0] < s[1] ? s[0] : s[1];
     pb[p] = s[0] < s[1] ? s[1] : s[0];
+    if (flow && pa[p] != pb[p] && nreal > flow_nv_of(c))
+      NQ_FAIL(c, -1, "nq_avg_attach: a product of two different fields with flow fields (NQ_FLOW_*) at nx = %d: a thread of that row plan holds one value (DESIGN.md section 7)", c->N);
     for (int o = 0; o < p; ++o)
       if (pa[o] == pa[p] && pb[o] == pb[p]) NQ_FAIL(c, -1, "nq_avg_attach: the pair (%d, %d) is listed twice", pairs[2 * p], pairs[2 * p + 1]);
   }
@@ -5808,10 +5941,12 @@ int nq_avg_attach(nq_ctx* c, int nfields, const int* fields, int nproducts, cons
   A->rg.init(1, every);
   A->args.mask = mask;
   A->args.np = nproducts;
+  A->flow = flow;
+  A->sel = sel;
   const size_t n = (size_t)c->N * c->N;
   int rc = 0;
   for (int i = 0; i < nfields && !rc; ++i) {
-    const int s = av_slot(c, fields[i]);
+    const int s = slot[i];
     A->field[i] = fields[i];
     if (s == AVG_PHI) {
       rc = att_alloc(c, A, &A->args.sum_phi, n, "nq_avg_attach");

@@ -18,11 +18,12 @@ first step exactly as it does ``m.q_psi`` (quirk Q2).  UnCoupledModel and YBJMod
 """
 import numpy as np
 
-from . import _lib
+from . import _lib, flow
 
 KERNEL_NAMES = ("q", "q_psi", "phi2")
 MAX_BINS, MAX_JOINT_BINS = _lib.PDF_MAX_BINS, _lib.PDF_MAX_JOINT_BINS
 _CODES = {"q": _lib.PDF_Q, "q_psi": _lib.PDF_QPSI, "phi2": _lib.PDF_PHI2, "c": _lib.PDF_C}
+_CODES.update(flow.CODES)           # the flow fields (flow.py): taken by name only, never a default
 
 
 def bin_index(x, lo, hi, bins):
@@ -125,9 +126,15 @@ def _validate(m, names, bins, ranges, joint, joint_bins, need_ranges=False):
         names = list(valid)
     else:
         names = [names] if isinstance(names, str) else list(names)
-    bad = [n for n in names if n not in valid]
+    if any(n in flow.NAMES for n in names if isinstance(n, str)):
+        flow.refuse(m, "field_pdfs", linked=joint is not None and len(names) > 1)
+    by_name = flow.available(m)
+    bad = [n for n in names if n not in valid and n not in by_name]
     if bad or not names or len(set(names)) != len(names):
-        raise ValueError("field_pdfs: names %r; valid names for %s (each once): %s" % (names, type(m).__module__, ", ".join(valid)))
+        raise ValueError("field_pdfs: names %r; valid names for %s (each once): %s%s" % (names, type(m).__module__, ", ".join(valid),
+                         "; by name only (flow.py): " + ", ".join(by_name) if by_name else ""))
+    if len(names) > 3:
+        raise ValueError("field_pdfs: %d names; valid: 1 to 3 per call (the value registers of the row pass)" % len(names))
     if not (isinstance(bins, (int, np.integer)) and 1 <= bins <= MAX_BINS):
         raise ValueError("field_pdfs: bins = %r; valid: 1 to %d (the LDS tables of a workgroup)" % (bins, MAX_BINS))
     if joint is not None:
