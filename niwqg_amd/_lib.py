@@ -4,12 +4,14 @@ The library is built in-tree by ``build()`` (hipcc, gfx950) and loaded from this
 no CPU fallback: if the library is missing or no GPU is present, constructing a model raises.
 """
 import ctypes
+import glob
 import os
+import re
 import subprocess
 
 import numpy as np
 
-from . import _etdrk4
+from . import _abi, _etdrk4
 
 try:                      # torch bundles its own libamdhip64.so.7; load it first so that our library
     import torch          # binds to the same HIP runtime instance (one runtime per process)
@@ -20,40 +22,15 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # NIWQG_AMD_LIB: another build of the same sources (A/B experiments with compile-time knobs, tools/); default: the in-tree library
 LIB_PATH = os.environ.get("NIWQG_AMD_LIB") or os.path.join(HERE, "libniwqg_amd.so")
 SRC = os.path.join(HERE, "csrc", "nq_lib.hip")
-HEADERS = [os.path.join(HERE, "csrc", h) for h in ("nq_fft.hpp", "nq_generic.hpp", "nq_step.hpp", "nq_anysize.hpp", "nq_particles.hpp", "nq_forcing.hpp", "nq_hist.hpp", "nq_freq.hpp", "nq_avg.hpp", "nq_flow.hpp")] + [
-    os.path.join(os.path.dirname(HERE), "include", "niwqg_amd.h")]
+HEADER = os.path.join(os.path.dirname(HERE), "include", "niwqg_amd.h")
+HEADERS = sorted(glob.glob(os.path.join(HERE, "csrc", "*.hpp"))) + [HEADER]
 
-COUPLED, UNCOUPLED, QG, YBJ = 0, 1, 2, 3
-(F_Q, F_QH, F_P, F_PH, F_PHI, F_PHIH, F_U, F_V, F_QPSI, F_QW, F_QWH, F_PHIX, F_PHIY, F_QH_MINUS, F_C, F_CH, F_QH_STAGE4,
- F_PHIH_STAGE4, F_QH_MINUS_STAGE4, F_QH_TICK, F_PHIH_TICK, F_QH_MINUS_TICK, F_QWH_TICK) = range(23)
-(S_KE, S_PW, S_KW, S_KE_QG, S_KE_NIW, S_PE_NIW, S_CFL, S_MAX_PHI) = range(8)
-
-EXPORTS = ["nq_create", "nq_destroy", "nq_last_error", "nq_set_q", "nq_set_c", "nq_set_phi", "nq_invert", "nq_refresh_grad_phi",
-           "nq_step", "nq_profile_stride", "nq_request_stage4_max", "nq_get_stage4_max", "nq_tick_snapshot", "nq_sync", "nq_get_field", "nq_get_qh_passenger", "nq_get_scalar", "nq_fft2", "nq_ifft2", "nq_rfft2",
-           "nq_irfft2", "nq_jacobian_psi_q", "nq_jacobian_psi_c", "nq_jacobian_psi_phi", "nq_jacobian_phic_phi", "nq_products_uq_vq", "nq_refraction", "nq_field_doubles", "nq_get_coeff", "nq_coeff_near_contour", "nq_coeff_patch", "nq_diagnostics", "nq_spectrum_shells", "nq_diagnostics_binned", "nq_transfer_binned",
-           "nq_particles_attach", "nq_particles_detach", "nq_particles_get", "nq_particles_sample", "nq_particles_records",
-           "nq_forcing_attach", "nq_forcing_detach", "nq_forcing_apply", "nq_forcing_increment", "nq_forcing_state", "nq_any_forcing",
-           "nq_freq_attach", "nq_freq_detach", "nq_freq_info", "nq_freq_series", "nq_freq_spectrum", "nq_any_freq_record", "nq_any_freq_spectrum",
-           "nq_avg_attach", "nq_avg_detach", "nq_avg_sample", "nq_avg_reset", "nq_avg_info", "nq_avg_read", "nq_any_moments",
-           "nq_stream_copy_gbs", "nq_timer_start", "nq_timer_stop", "nq_event_record", "nq_event_elapsed", "nq_profile_enable", "nq_profile_read", "nq_profile_read_all", "nq_group_elems", "nq_overlap_grid", "nq_overlap_default_cus", "nq_overlap_info", "nq_create_slab",
-           "nq_slab_info", "nq_group_buffers", "nq_upload_spectral", "nq_download_spectral", "nq_phase",
-           "nq_reduce_buffer", "nq_reduce_read", "nq_reduce_write", "nq_device_bytes", "nq_stream",
-           "nq_comm_probe", "nq_comm_unique_id", "nq_comm_init", "nq_slab_attach_peers", "nq_slab_set_callbacks", "nq_slab_set_null_link", "nq_slab_config", "nq_slab_set_stage_buffers", "nq_slab_spectral", "nq_slab_spectral_read",
-           "nq_slab_step", "nq_slab_put_rows", "nq_slab_commit", "nq_slab_get_rows", "nq_slab_diagnostics", "nq_slab_diagnostics_binned", "nq_slab_transfer_binned",
-           "nq_slab_local_max", "nq_slab_counters", "nq_slab_allreduce_ms", "nq_snapshot_begin", "nq_snapshot_end",
-           "nq_any_create", "nq_any_destroy", "nq_any_last_error", "nq_any_sync", "nq_any_device_bytes", "nq_any_alloc", "nq_any_free",
-           "nq_any_upload", "nq_any_download", "nq_any_fft", "nq_any_ew", "nq_any_reduce", "nq_any_expand_half", "nq_any_take_cols",
-           "nq_field_minmax", "nq_field_hist", "nq_field_hist_read", "nq_any_hist", "nq_any_hist2", "nq_any_minmax",
-           "nq_any_set_elem", "nq_any_bin", "nq_any_etdrk4", "nq_any_etdrk4_patch", "nq_any_particles_rk4", "nq_any_interp"]
-
-(PDF_Q, PDF_QPSI, PDF_PHI2, PDF_C) = range(4)      # fields of nq_field_hist (include/niwqg_amd.h: NQ_PDF_*)
-PDF_MAX_BINS, PDF_MAX_JOINT_BINS = 1024, 128
-PDF_DEVICE_BYTES = (3 * (PDF_MAX_BINS + 3) + PDF_MAX_JOINT_BINS ** 2 + 1) * 8 + 6 * 8192 * 8     # NQ_PDF_DEVICE_BYTES
-
-(AVG_Q, AVG_QPSI, AVG_PHI2, AVG_C, AVG_PHI) = range(5)      # fields of nq_avg_attach (include/niwqg_amd.h: NQ_AVG_*)
-(FLOW_U, FLOW_V, FLOW_SN, FLOW_SS, FLOW_STRAIN2, FLOW_OW, FLOW_GRADPHI2) = range(16, 23)      # NQ_FLOW_*: PDFs and averages alike
-
-TRANSFER_ROWS = 6                 # rows of nq_transfer_binned (include/niwqg_amd.h: NQ_TRANSFER_ROWS)
+# The header is the one statement of the C ABI: the entry points with their signatures, every NQ_X constant (here: X) and struct
+# nq_params are read from it.  A new entry point is declared there and defined in the library; nothing here lists it.
+PROTOTYPES, _CONSTANTS, _PARAMS_FIELDS = _abi.read(open(HEADER).read())
+EXPORTS = [name for name, _, _ in PROTOTYPES]
+globals().update({name[3:]: value for name, value in _CONSTANTS.items()})
+COUPLED, UNCOUPLED, QG, YBJ = MODEL_COUPLED, MODEL_UNCOUPLED, MODEL_QG, MODEL_YBJ        # noqa: F821
 
 FUSED_SIZES = (64, 128, 256, 512, 1024, 2048, 4096, 8192)       # grids the fused ETDRK4 kernels have a plan for (csrc: NQ_FOR_SIZES)
 
@@ -66,14 +43,30 @@ EXCHANGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctyp
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int)
 
 
+# C spelling (const dropped) -> ctypes; a spelling the header starts to use and this table lacks fails lib() (TypeError)
+_CTYPES = {"int": ctypes.c_int, "double": ctypes.c_double, "float": ctypes.c_float, "long long": ctypes.c_longlong,
+           "unsigned long long": ctypes.c_ulonglong}
+
+
 class Params(ctypes.Structure):
-    _fields_ = [("model", ctypes.c_int), ("nx", ctypes.c_int), ("budgets", ctypes.c_int),
-                ("dual_q", ctypes.c_int), ("dt", ctypes.c_double), ("U", ctypes.c_double),
-                ("f", ctypes.c_double), ("kappa2", ctypes.c_double), ("nu", ctypes.c_double),
-                ("nu4", ctypes.c_double), ("mu", ctypes.c_double), ("nuw", ctypes.c_double),
-                ("nu4w", ctypes.c_double), ("muw", ctypes.c_double), ("beta", ctypes.c_double),
-                ("passive_scalar", ctypes.c_int), ("nu4c", ctypes.c_double), ("nuc", ctypes.c_double),
-                ("muc", ctypes.c_double)]
+    _fields_ = [(name, _CTYPES[c_type]) for name, c_type in _PARAMS_FIELDS]
+
+
+_CTYPES.update({c_type + "*": ctypes.POINTER(t) for c_type, t in list(_CTYPES.items())})
+_CTYPES.update({"char*": ctypes.c_char_p, "nq_params*": ctypes.POINTER(Params), "nq_exchange_fn": EXCHANGE_FN, "nq_allreduce_fn": ALLREDUCE_FN})
+for _opaque in ("void", "nq_ctx", "nq_any"):
+    _CTYPES.update({_opaque + "*": ctypes.c_void_p, _opaque + "**": ctypes.POINTER(ctypes.c_void_p)})
+
+
+def signature(prototype):
+    """(argtypes, restype) of one prototype of the header"""
+    def ctype(c_type, what):
+        try:
+            return _CTYPES[_abi.spelling(re.sub(r"\bconst\b", " ", c_type))]
+        except KeyError:
+            raise TypeError("%s: no ctypes type for %s of C type '%s' (niwqg_amd/_lib.py: _CTYPES)" % (name, what, c_type)) from None
+    name, ret, params = prototype
+    return [ctype(c_type, "parameter '%s'" % pname) for c_type, pname in params], ctype(ret, "the return value")
 
 
 def needs_build():
@@ -107,146 +100,13 @@ def lib():
         raise RuntimeError("niwqg_amd: %s is missing - run niwqg_amd._lib.build() (hipcc, gfx950); "
                            "there is no CPU fallback" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    dp = ctypes.POINTER(ctypes.c_double)
-    vp = ctypes.c_void_p
-    L.nq_create.argtypes = [ctypes.POINTER(Params), dp, dp, dp, dp, ctypes.c_int, ctypes.POINTER(vp)]
-    L.nq_last_error.argtypes = [vp]
-    L.nq_last_error.restype = ctypes.c_char_p
-    for name in ("nq_destroy", "nq_invert", "nq_refresh_grad_phi", "nq_sync", "nq_timer_start"):
-        getattr(L, name).argtypes = [vp]
-    for name in ("nq_set_q", "nq_set_c", "nq_set_phi", "nq_jacobian_psi_q", "nq_jacobian_psi_c", "nq_jacobian_psi_phi", "nq_jacobian_phic_phi",
-                 "nq_products_uq_vq", "nq_refraction", "nq_diagnostics"):
-        getattr(L, name).argtypes = [vp, dp]
-    for name in ("nq_fft2", "nq_ifft2", "nq_rfft2", "nq_irfft2"):
-        getattr(L, name).argtypes = [vp, dp, dp]
-    L.nq_step.argtypes = [vp, ctypes.c_int]
-    L.nq_request_stage4_max.argtypes = [vp]
-    L.nq_profile_stride.argtypes = [vp, ctypes.c_int]
-    L.nq_tick_snapshot.argtypes = [vp]
-    L.nq_get_stage4_max.argtypes = [vp, dp]
-    L.nq_get_field.argtypes = [vp, ctypes.c_int, dp]
-    L.nq_field_doubles.argtypes = [vp, ctypes.c_int]
-    L.nq_field_doubles.restype = ctypes.c_longlong
-    L.nq_get_qh_passenger.argtypes = [vp, dp]
-    L.nq_get_scalar.argtypes = [vp, ctypes.c_int, dp]
-    L.nq_spectrum_shells.argtypes = [vp]
-    L.nq_diagnostics_binned.argtypes = [vp, ctypes.c_int, dp]
-    L.nq_transfer_binned.argtypes = [vp, ctypes.c_int, dp]
-    ip, llp = ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_longlong)
-    L.nq_particles_attach.argtypes = [vp, ctypes.c_int, dp, dp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int,
-                                      ctypes.c_int, ip]
-    L.nq_particles_detach.argtypes = [vp]
-    L.nq_particles_get.argtypes = [vp, dp, dp]
-    L.nq_particles_sample.argtypes = [vp, ctypes.c_int, ip, dp]
-    L.nq_particles_records.argtypes = [vp, llp, llp, dp]
-    L.nq_forcing_attach.argtypes = [vp, dp, dp, ctypes.c_ulonglong, ctypes.c_longlong]
-    L.nq_forcing_detach.argtypes = [vp]
-    L.nq_forcing_apply.argtypes = [vp]
-    L.nq_forcing_increment.argtypes = [vp, ctypes.c_int, ctypes.c_longlong, dp]
-    L.nq_forcing_state.argtypes = [vp, dp]
-    L.nq_any_forcing.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_longlong, ctypes.c_int,
-                                 ctypes.c_double, vp, dp]
-    L.nq_freq_attach.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ip]
-    L.nq_freq_detach.argtypes = [vp]
-    L.nq_freq_info.argtypes = [vp, llp]
-    L.nq_freq_series.argtypes = [vp, ctypes.c_int, llp, dp]
-    L.nq_freq_spectrum.argtypes = [vp, ctypes.c_int, dp, ctypes.c_int, ctypes.c_double, ctypes.c_int, dp]
-    L.nq_any_freq_record.argtypes = [vp, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(vp), ip, ip, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                     ctypes.c_int]
-    L.nq_any_freq_spectrum.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp,
-                                       ctypes.c_int, ctypes.c_double, ctypes.c_int, dp]
-    L.nq_avg_attach.argtypes = [vp, ctypes.c_int, ip, ctypes.c_int, ip, ctypes.c_int]
-    for name in ("nq_avg_detach", "nq_avg_sample", "nq_avg_reset"):
-        getattr(L, name).argtypes = [vp]
-    L.nq_avg_info.argtypes = [vp, llp]
-    L.nq_avg_read.argtypes = [vp, ctypes.c_int, dp]
-    L.nq_any_moments.argtypes = [vp, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(vp), ip, ctypes.POINTER(vp), ctypes.c_int, ip,
-                                 ctypes.POINTER(vp)]
-    L.nq_get_coeff.argtypes = [vp, ctypes.c_int, ctypes.c_int, dp]
-    L.nq_coeff_near_contour.argtypes = [vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-    L.nq_coeff_patch.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, dp]
-    L.nq_stream_copy_gbs.argtypes = [vp, ctypes.c_longlong, ctypes.c_int, dp]
-    L.nq_timer_stop.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
-    L.nq_event_record.argtypes = [vp, ctypes.c_int]
-    L.nq_event_elapsed.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_float)]
-    L.nq_profile_enable.argtypes = [vp, ctypes.c_int]
-    L.nq_profile_read.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float)]
-    L.nq_profile_read_all.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_float)]
-    L.nq_group_elems.argtypes = [ctypes.POINTER(Params), ctypes.c_int, ctypes.c_int]
-    L.nq_group_elems.restype = ctypes.c_longlong
-    L.nq_overlap_grid.argtypes = [ctypes.c_int, ctypes.c_int]
-    L.nq_overlap_default_cus.argtypes = [ctypes.c_int]
-    L.nq_overlap_info.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
-    L.nq_create_slab.argtypes = [ctypes.POINTER(Params), dp, dp, dp, dp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                 ctypes.POINTER(vp), vp, ctypes.POINTER(vp)]
-    L.nq_slab_info.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
-    L.nq_group_buffers.argtypes = [vp, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(vp),
-                                   ctypes.POINTER(ctypes.c_longlong)]
-    L.nq_upload_spectral.argtypes = [vp, ctypes.c_int, dp]
-    L.nq_download_spectral.argtypes = [vp, ctypes.c_int, dp]
-    L.nq_phase.argtypes = [vp, ctypes.c_int, ctypes.c_int]
-    L.nq_reduce_buffer.argtypes = [vp, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int)]
-    L.nq_reduce_read.argtypes = [vp, ctypes.c_int, dp]
-    L.nq_reduce_write.argtypes = [vp, ctypes.c_int, dp]
-    L.nq_comm_probe.argtypes = []
-    L.nq_comm_unique_id.argtypes = [vp]
-    L.nq_comm_init.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int]
-    L.nq_slab_attach_peers.argtypes = [ctypes.POINTER(vp), ctypes.c_int]
-    L.nq_slab_set_callbacks.argtypes = [vp, EXCHANGE_FN, ALLREDUCE_FN, vp]
-    L.nq_slab_set_null_link.argtypes = [vp]
-    L.nq_slab_config.argtypes = [vp, ctypes.c_int]
-    L.nq_slab_set_stage_buffers.argtypes = [vp, vp, vp]
-    L.nq_slab_spectral.argtypes = [vp, ctypes.c_int]
-    L.nq_slab_spectral_read.argtypes = [vp, ctypes.c_int, dp]
-    L.nq_slab_step.argtypes = [vp, ctypes.c_int]
-    L.nq_slab_put_rows.argtypes = [vp, ctypes.c_int, dp]
-    L.nq_slab_commit.argtypes = [vp, ctypes.c_int]
-    L.nq_slab_get_rows.argtypes = [vp, ctypes.c_int, dp]
-    L.nq_slab_diagnostics.argtypes = [vp, dp]
-    L.nq_slab_diagnostics_binned.argtypes = [vp, ctypes.c_int, dp]
-    L.nq_slab_transfer_binned.argtypes = [vp, ctypes.c_int, dp]
-    L.nq_slab_local_max.argtypes = [vp, dp]
-    L.nq_slab_counters.argtypes = [vp, dp, ctypes.c_int]
-    L.nq_slab_allreduce_ms.argtypes = [vp, dp]
-    L.nq_snapshot_begin.argtypes = [vp, ctypes.c_int]
-    L.nq_snapshot_end.argtypes = [vp, dp, dp]
-    # the any-size engine (include/niwqg_amd.h: nq_any_*)
-    ip = ctypes.POINTER(ctypes.c_int)
-    L.nq_any_create.argtypes = [ctypes.c_int, ctypes.POINTER(vp)]
-    L.nq_any_destroy.argtypes = [vp]
-    L.nq_any_last_error.argtypes = [vp]
-    L.nq_any_last_error.restype = ctypes.c_char_p
-    L.nq_any_sync.argtypes = [vp]
-    L.nq_any_device_bytes.argtypes = [vp]
-    L.nq_any_device_bytes.restype = ctypes.c_longlong
-    L.nq_any_alloc.argtypes = [vp, ctypes.c_longlong, ctypes.POINTER(vp)]
-    L.nq_any_free.argtypes = [vp, vp, ctypes.c_longlong]
-    L.nq_any_upload.argtypes = [vp, vp, dp, ctypes.c_longlong]
-    L.nq_any_download.argtypes = [vp, vp, dp, ctypes.c_longlong]
-    L.nq_any_fft.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    L.nq_any_ew.argtypes = [vp, ctypes.c_int, vp, vp, vp, vp, ctypes.c_longlong, dp]
-    L.nq_any_reduce.argtypes = [vp, ctypes.c_int, vp, vp, ctypes.c_longlong, dp]
-    L.nq_any_expand_half.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    L.nq_any_take_cols.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    L.nq_any_set_elem.argtypes = [vp, vp, ctypes.c_longlong, ctypes.c_double, ctypes.c_double]
-    L.nq_any_bin.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, dp]
-    ullp = ctypes.POINTER(ctypes.c_ulonglong)
-    L.nq_field_minmax.argtypes = [vp, ctypes.c_int, ip, dp]
-    L.nq_field_hist.argtypes = [vp, ctypes.c_int, ip, dp, dp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    L.nq_field_hist_read.argtypes = [vp, ullp]
-    L.nq_any_hist.argtypes = [vp, vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, ullp]
-    L.nq_any_hist2.argtypes = [vp, vp, vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, dp, dp, ctypes.c_int, ullp]
-    L.nq_any_minmax.argtypes = [vp, vp, ctypes.c_longlong, ctypes.c_int, dp]
-    L.nq_any_particles_rk4.argtypes = [vp, vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                       ctypes.c_double]
-    L.nq_any_interp.argtypes = [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double]
-    L.nq_any_etdrk4.argtypes = [vp, ctypes.c_int, ctypes.POINTER(Params), dp, dp, dp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp),
-                                ctypes.c_double, ctypes.c_int, ip, ip, ip]
-    L.nq_any_etdrk4_patch.argtypes = [vp, ctypes.POINTER(vp), ctypes.c_int, ctypes.c_int, ip, ip, dp]
-    L.nq_device_bytes.argtypes = [vp]
-    L.nq_device_bytes.restype = ctypes.c_longlong
-    L.nq_stream.argtypes = [vp]
-    L.nq_stream.restype = vp
+    for prototype in PROTOTYPES:
+        try:
+            fn = getattr(L, prototype[0])
+        except AttributeError:
+            raise RuntimeError("niwqg_amd: %s does not export %s, which %s declares (a stale build, or a library of other "
+                               "sources)" % (LIB_PATH, prototype[0], HEADER)) from None
+        fn.argtypes, fn.restype = signature(prototype)
     _lib = L
     return L
 
@@ -255,12 +115,16 @@ def _dptr(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
 
+def _iptr(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+
+
 def coeff_near_contour(L, h, eq, delta):
     """(l, k) index arrays (k global) of the entries of equation eq within delta of the ETDRK4 contour (nq_coeff_near_contour)"""
     cap = 1 << 16
     while True:
         li, ki = np.empty(cap, np.int32), np.empty(cap, np.int32)
-        n = L.nq_coeff_near_contour(h, eq, float(delta), cap, li.ctypes.data, ki.ctypes.data)
+        n = L.nq_coeff_near_contour(h, eq, float(delta), cap, _iptr(li), _iptr(ki))
         if n < 0:
             raise RuntimeError("nq_coeff_near_contour failed (%d): %s" % (n, L.nq_last_error(h).decode()))
         if n <= cap:
@@ -273,7 +137,7 @@ def coeff_patch(L, h, eq, li, ki, vals):
     vals = np.ascontiguousarray(vals, np.complex128)
     if vals.shape != (len(li), 4) or len(ki) != len(li):
         raise ValueError("coeff_patch: %d entries, values of shape %s" % (len(li), vals.shape))
-    rc = L.nq_coeff_patch(h, eq, len(li), li.ctypes.data, ki.ctypes.data, _dptr(vals.view(np.float64)))
+    rc = L.nq_coeff_patch(h, eq, len(li), _iptr(li), _iptr(ki), _dptr(vals.view(np.float64)))
     if rc != 0:
         raise RuntimeError("nq_coeff_patch failed (%d): %s" % (rc, L.nq_last_error(h).decode()))
 

@@ -22,8 +22,8 @@ import numpy as np
 
 from . import _etdrk4, _lib
 
-(PH_PRODUCTS, PH_UPDATE, PH_WAVEPV, PH_INVERT, PH_EMIT_PHI, PH_INVERT_NOW, PH_BUDGET_SUMS,
- PH_BUDGET_FINISH) = range(8)
+from ._lib import (PH_PRODUCTS, PH_UPDATE, PH_WAVEPV, PH_INVERT, PH_EMIT_PHI, PH_INVERT_NOW, PH_BUDGET_SUMS,      # noqa: F401
+                   PH_BUDGET_FINISH)
 
 _REAL_ROWS = (_lib.F_Q, _lib.F_P, _lib.F_U, _lib.F_V, _lib.F_QW, _lib.F_C)
 _CPLX_ROWS = (_lib.F_PHI, _lib.F_PHIX, _lib.F_PHIY)
