@@ -521,7 +521,7 @@ __global__ void k_expand_half(const cd* __restrict__ f1, const cd* __restrict__ 
 // kind 3: max |a| over complex plane (out[0] as max via atomicMax on bits, values >= 0).  NaN propagates (nan_max): a NaN
 //         with either sign bit orders above +inf as an unsigned bit pattern, so the atomicMax keeps it too
 __global__ void k_reduce(const cd* __restrict__ a, int width, int pitch, int N, int kind, const double* __restrict__ kk,
-                         const double* __restrict__ ll, double* out) {
+                         const double* __restrict__ ll, double* out, double* __restrict__ part = nullptr) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x, l = blockIdx.y;
   double v = 0.0;
   if (k < width) {
@@ -547,8 +547,24 @@ __global__ void k_reduce(const cd* __restrict__ a, int width, int pitch, int N, 
   }
   if (threadIdx.x == 0) {
     if (kind == 3) atomicMax(reinterpret_cast<unsigned long long*>(out), (unsigned long long)__double_as_longlong(sh[0]));
+    else if (part) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = sh[0];      // one slot per workgroup, added up by k_sum_slots
     else atomicAdd(out, sh[0]);
   }
+}
+// out[0] = sum of part[0..n) in a fixed order (one workgroup).  The sums of k_reduce go through it: an atomicAdd per workgroup adds
+// in the order the workgroups happen to finish, and the energies then differ in the last bit from one call to the next -- and
+// between a run and the same run in other units (tests/test_gpu_magnitudes.py).
+__global__ void k_sum_slots(const double* __restrict__ part, int n, double* out) {
+  double v = 0.0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) v += part[i];
+  __shared__ double sh[256];
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = sh[0];
 }
 // max |a| of a real plane into out[0] (atomicMax on bits as kind 3 of k_reduce: NaN propagates)
 __global__ void k_reduce_real_max(const double* __restrict__ a, size_t n, double* out) {
@@ -4162,7 +4178,10 @@ int nq_get_scalar(nq_ctx* c, int id, double* out) {
   HIPCHK(c, hipSetDevice(c->device));
   const int N = c->N;
   const double M = (double)N * N;
-  double* d = reinterpret_cast<double*>(c->scr_h0);    // 2 doubles of scratch for the reductions
+  // scratch of the reductions: d[0..1] the results, d[2 ..] one partial-sum slot per workgroup of k_reduce, at most
+  // ceil(N / 256) * N doubles.  scr_h0 holds N * Ph complex entries (2 N (N/2 + 1) doubles) on a single rank; the 64-entry
+  // allocation of a slab rank is never reached, the sums sit behind NQ_SINGLE_RANK below
+  double* d = reinterpret_cast<double*>(c->scr_h0);
   double h[2] = {0, 0};
   HIPCHK(c, hipMemsetAsync(d, 0, sizeof(double) * 2, c->stream));
   if (id == NQ_S_KE || id == NQ_S_PW || id == NQ_S_KW) {
@@ -4176,7 +4195,8 @@ int nq_get_scalar(nq_ctx* c, int id, double* out) {
   }
   NQ_SINGLE_RANK(c, "nq_get_scalar (ids other than the budget increments)");
   if (id == NQ_S_KE_QG) {
-    hipLaunchKernelGGL(k_reduce, dim3((c->Wh + 255) / 256, N), dim3(256), 0, c->stream, c->ph, c->Wh, c->Ph, N, c->kernel_family ? 4 : 1, c->kk, c->ll, d);
+    hipLaunchKernelGGL(k_reduce, dim3((c->Wh + 255) / 256, N), dim3(256), 0, c->stream, c->ph, c->Wh, c->Ph, N, c->kernel_family ? 4 : 1, c->kk, c->ll, d, d + 2);
+    hipLaunchKernelGGL(k_sum_slots, dim3(1), dim3(256), 0, c->stream, d + 2, ((c->Wh + 255) / 256) * N, d);
     HIPCHK(c, hipMemcpyAsync(h, d, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     int rc = nq_sync(c);
     *out = 0.5 * h[0] / (M * M);
@@ -4197,7 +4217,8 @@ int nq_get_scalar(nq_ctx* c, int id, double* out) {
   if (!c->kernel_family) NQ_FAIL(c, -4, "scalar %d needs the wave field", id);
   const cd* phih = c->w.y[c->w.cur];
   if (id == NQ_S_KE_NIW || id == NQ_S_PE_NIW) {
-    hipLaunchKernelGGL(k_reduce, dim3((N + 255) / 256, N), dim3(256), 0, c->stream, phih, N, N, N, id == NQ_S_KE_NIW ? 0 : 2, c->kk, c->ll, d);
+    hipLaunchKernelGGL(k_reduce, dim3((N + 255) / 256, N), dim3(256), 0, c->stream, phih, N, N, N, id == NQ_S_KE_NIW ? 0 : 2, c->kk, c->ll, d, d + 2);
+    hipLaunchKernelGGL(k_sum_slots, dim3(1), dim3(256), 0, c->stream, d + 2, ((N + 255) / 256) * N, d);
     HIPCHK(c, hipMemcpyAsync(h, d, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     int rc = nq_sync(c);
     *out = (id == NQ_S_KE_NIW) ? 0.5 * h[0] / (M * M) : 0.25 * h[0] / (M * M) / c->p.kappa2;

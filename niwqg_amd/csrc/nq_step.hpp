@@ -137,11 +137,14 @@ __device__ __forceinline__ void hs_load(HsRegs<P>& r, const Row& rowA, const Row
 // owner of position N-m through LDS (the double fetch was 0.5 GB per launch, profiles/r01_c_pmc.txt).
 template <int N, int P, int T, typename F, bool PAIR>
 __device__ __forceinline__ void hs_pack(cd (&w)[P], const HsRegs<P>& r, int j, int c, cd* lds,
-                                        const double* __restrict__ kk, bool b_mul_ik, bool b_zero_nyq) {
+                                        const double* __restrict__ kk, bool b_mul_ik, bool b_zero_nyq, double b_scale = 1.0) {
+  // b_scale: the power of two of pair_scale, applied on the way (scaling r itself would hold the loop-carried prefetch
+  // registers of the persistent kernels live in a second copy: eight spills in k_x_products<4096>)
 #pragma unroll
   for (int t = 0; t < P / 2; ++t) {
     const int m = j + t * T;
     cd a = r.a[t], b = r.b[t];
+    if (PAIR) b = cscale(b, b_scale);
     if (PAIR && b_mul_ik) b = cscale(cmul_i(b), kk[m]);
     if (m == 0) {
       a.y = 0.0;
@@ -152,6 +155,7 @@ __device__ __forceinline__ void hs_pack(cd (&w)[P], const HsRegs<P>& r, int j, i
   }
   if (j == 0) {                                                             // self-mirrored m = N/2
     cd a = r.an, b = r.bn;
+    if (PAIR) b = cscale(b, b_scale);
     if (PAIR && b_mul_ik) b = cscale(cmul_i(b), kk[N / 2]);
     a.y = 0.0;
     b.y = 0.0;
@@ -186,6 +190,22 @@ __device__ __forceinline__ void row_atomic_max(unsigned long long* mx, double ma
     atomicMax(&mx[0], (unsigned long long)__double_as_longlong(ma));
     atomicMax(&mx[1], (unsigned long long)__double_as_longlong(mb));
   }
+}
+
+// Per-row rescale of the second operand of a packed pair, from the row's two maxima (mx[0..1], as row_atomic_max leaves them):
+// scale = 2^e brings it to the first operand's magnitude, unscale = 2^-e undoes that exactly after the transform.  Where either
+// operand vanishes on the row e = 0, and where the SECOND one does unscale = 0: its share of the transform's output is the
+// other's roundoff, and the field it stands for (a passive scalar that was never set, q_w without waves) is exactly zero.
+struct PairScale { double scale, unscale; };
+__device__ __forceinline__ PairScale pair_scale(const unsigned long long* mx) {
+  const double ma = __longlong_as_double((long long)mx[0]), mb = __longlong_as_double((long long)mx[1]);
+  int e = 0;
+  if (ma > 0.0 && mb > 0.0) e = ilogb(ma) - ilogb(mb);
+  e = e > 900 ? 900 : (e < -900 ? -900 : e);
+  PairScale r;
+  r.scale = ldexp(1.0, e);
+  r.unscale = mb > 0.0 ? ldexp(1.0, -e) : 0.0;
+  return r;
 }
 
 // After a forward row FFT of z = a + i*b (a, b real), split into the two half spectra and store
@@ -425,18 +445,26 @@ k_x_products(MArr Mu, MArr Mp, MArr Mq, MArr Mqw, MArr Mphi, MArr Mgx, MArr Mgy,
   HsRegs<P> h2;
   hs_load<N, P, T, true>(h2, xrow<SLAB>(Mu, row), xrow<SLAB>(Mp, row), j);
   NQ_PHASE_FENCE();
-  double c_unscale = 1.0;
-  if constexpr (MODE == MODE_QGC) {
+  double c_unscale = 1.0, c_scale = 1.0;
+  if constexpr (PAIRQ) {
     // q and the passive scalar share one complex transform, but c has arbitrary units (|c| ~ 1 against |q| ~ 1e-5 in
     // the reference's examples): the roundoff of the larger would swamp the smaller (2e-11 in q after 20 steps).
     // Rescale c per row by a power of two, exactly undone after the transform (as k_x_wavepv does for its pair).
+    // CoupledModel's partner q_w gets the same treatment: under strong waves |q_w| exceeds |q| by any factor (a weak or
+    // vanishing vortex field is what the model is for) and the reference transforms q alone; unscaled, q came back with
+    // eps |q_w| / |q| of roundoff (4.9e-10 at |q_w| / |q| = 6e8).  The scale depends on the row's data
+    // only, so slab ranks and the single context form the same bits.
     double ma = 0.0, mb = 0.0;
 #pragma unroll
     for (int t = 0; t < P / 2; ++t) {
       ma = fmax(ma, fmax(fabs(h1.a[t].x), fabs(h1.a[t].y)));
       mb = fmax(mb, fmax(fabs(h1.b[t].x), fabs(h1.b[t].y)));
     }
-    unsigned long long* mx = reinterpret_cast<unsigned long long*>(nq_smem + X::LDS_BYTES - 512) + 2 * c;
+    ma = fmax(ma, fabs(h1.an.x));          // the self-mirrored element kx = N/2 (thread 0; zero elsewhere): hs_pack transforms its
+    mb = fmax(mb, fabs(h1.bn.x));          // real part, so a row that holds nothing else must not count as vanishing
+    // QGC: the reduction scratch (nothing else uses it in that mode); Coupled: the row's own two words in front of it, the
+    // reduction scratch still being read by the Jacobian sums of the previous row block
+    unsigned long long* mx = reinterpret_cast<unsigned long long*>(nq_smem + X::LDS_BYTES - 512 - (MODE == MODE_COUPLED ? 16 * X::C : 0)) + 2 * c;
     if (j == 0) {
       unsigned long long zero = 0ull;                    // formed here: held across the loop it is four VGPRs of zeros, spilled
       asm volatile("" : "+v"(zero));
@@ -446,25 +474,18 @@ k_x_products(MArr Mu, MArr Mp, MArr Mq, MArr Mqw, MArr Mphi, MArr Mgx, MArr Mgy,
     wg_barrier();
     row_atomic_max<T>(mx, ma, mb);
     wg_barrier();
-    ma = __longlong_as_double((long long)mx[0]);
-    mb = __longlong_as_double((long long)mx[1]);
-    int e = 0;
-    if (ma > 0.0 && mb > 0.0) e = ilogb(ma) - ilogb(mb);
-    e = e > 900 ? 900 : (e < -900 ? -900 : e);
-    const double sb = ldexp(1.0, e);
-    c_unscale = ldexp(1.0, -e);
-#pragma unroll
-    for (int t = 0; t < P / 2; ++t) h1.b[t] = cscale(h1.b[t], sb);
-    h1.bn = cscale(h1.bn, sb);
+    const PairScale ps = pair_scale(mx);
+    c_scale = ps.scale;
+    c_unscale = ps.unscale;
     wg_barrier();
   }
-  hs_pack<N, P, T, F, PAIRQ>(w, h1, j, c, lds, kk, false, false);
+  hs_pack<N, P, T, F, PAIRQ>(w, h1, j, c, lds, kk, false, false, c_scale);
   NQ_PHASE_FENCE();
   F::template run<true>(w, j, c, lds, twr);
 #pragma unroll
   for (int t = 0; t < P; ++t) {
     q[t] = w[t].x;
-    qpsi[t] = (MODE == MODE_COUPLED) ? w[t].x - w[t].y : (MODE == MODE_QGC ? w[t].y * c_unscale : w[t].x);   // QGC: c
+    qpsi[t] = (MODE == MODE_COUPLED) ? w[t].x - w[t].y * c_unscale : (MODE == MODE_QGC ? w[t].y * c_unscale : w[t].x);   // QGC: c
   }
   // (u, v) = ifft of (-il psi, ik psi): Mu already holds T_y^-1[-il psi], Mp holds T_y^-1[psi]
   NQ_PHASE_FENCE();
@@ -707,9 +728,10 @@ k_x_products_eo(MArr Mu, MArr Mp, MArr Mq, MArr Mqw, MArr Mphi, MArr Mgx, MArr M
     cd we[P], wo[P];
     double qe[P], qo[P];
     double c_unscale = 1.0, c_scale = 1.0;
-    if constexpr (MODE == MODE_QGC) {
-      // q and the passive scalar share one complex transform; c has arbitrary units: rescale it per row by a power of two
-      // (k_x_products does the same).  One extra sweep over the two rows (they are re-read from cache by the fold).
+    if constexpr (PAIRQ) {
+      // q and the passive scalar (or q_w) share one complex transform; c has arbitrary units and q_w any size against q:
+      // rescale it per row by a power of two (k_x_products does the same).  One extra sweep over the two rows (they are re-read
+      // from cache by the fold).
       const XRowT<SLAB> ra = xrow<SLAB>(Mq, Mq, row), rbw = xrow<SLAB>(Mqw, Mq, row);
       double ma = 0.0, mb = 0.0;
 #pragma unroll
@@ -725,19 +747,17 @@ k_x_products_eo(MArr Mu, MArr Mp, MArr Mq, MArr Mqw, MArr Mphi, MArr Mgx, MArr M
       }
       unsigned long long* mx = reinterpret_cast<unsigned long long*>(red + 40);
       if (j == 0) {
-        mx[0] = 0ull;
-        mx[1] = 0ull;
+        unsigned long long zero = 0ull;                  // formed here: held across the loop it is four VGPRs of zeros, spilled
+        asm volatile("" : "+v"(zero));
+        mx[0] = zero;
+        mx[1] = zero;
       }
       wg_barrier();
       row_atomic_max<T>(mx, ma, mb);
       wg_barrier();
-      ma = __longlong_as_double((long long)mx[0]);
-      mb = __longlong_as_double((long long)mx[1]);
-      int e = 0;
-      if (ma > 0.0 && mb > 0.0) e = ilogb(ma) - ilogb(mb);
-      e = e > 900 ? 900 : (e < -900 ? -900 : e);
-      c_scale = ldexp(1.0, e);
-      c_unscale = ldexp(1.0, -e);
+      const PairScale ps = pair_scale(mx);
+      c_scale = ps.scale;
+      c_unscale = ps.unscale;
       wg_barrier();
     }
     // ---- phase 1: (q, qw | c) -> q, q_psi of both parities
@@ -747,7 +767,7 @@ k_x_products_eo(MArr Mu, MArr Mp, MArr Mq, MArr Mqw, MArr Mphi, MArr Mgx, MArr M
 #pragma unroll
     for (int t = 0; t < P; ++t) {
       qe[t] = we[t].x;
-      const double qp = (MODE == MODE_COUPLED) ? we[t].x - we[t].y : (MODE == MODE_QGC ? we[t].y * c_unscale : we[t].x);
+      const double qp = (MODE == MODE_COUPLED) ? we[t].x - we[t].y * c_unscale : (MODE == MODE_QGC ? we[t].y * c_unscale : we[t].x);
       if constexpr (MODE != MODE_QG) park[j + t * T] = qp;              // q_psi, or QGModel's passive scalar
     }
     NQ_EO_FENCE();
@@ -755,7 +775,7 @@ k_x_products_eo(MArr Mu, MArr Mp, MArr Mq, MArr Mqw, MArr Mphi, MArr Mgx, MArr M
 #pragma unroll
     for (int t = 0; t < P; ++t) {
       qo[t] = wo[t].x;
-      const double qp = (MODE == MODE_COUPLED) ? wo[t].x - wo[t].y : (MODE == MODE_QGC ? wo[t].y * c_unscale : wo[t].x);
+      const double qp = (MODE == MODE_COUPLED) ? wo[t].x - wo[t].y * c_unscale : (MODE == MODE_QGC ? wo[t].y * c_unscale : wo[t].x);
       if constexpr (MODE != MODE_QG) park[M + j + t * T] = qp;
     }
     // ---- phase 2: (u, v) = ifft of (-il psi, ik psi); u q + i v q of both parities -> Muq, Mvq
@@ -1031,7 +1051,29 @@ k_x_diag(MArr Mq, MArr Mqw, MArr Mphi, const cd* __restrict__ tw, const double* 
   HsRegs<P> h1;
   hs_load<N, P, T, MODE == MODE_COUPLED>(h1, xrow<SLAB>(Mq, row), xrow<SLAB>(MODE == MODE_COUPLED ? Mqw : Mq, row), j);
   NQ_PHASE_FENCE();
-  hs_pack<N, P, T, F, MODE == MODE_COUPLED>(w, h1, j, c, lds, kk, false, false);
+  double qw_scale = 1.0, qw_unscale = 1.0;
+  if constexpr (MODE == MODE_COUPLED) {        // q_w rescaled per row against q, as in k_x_products
+    double ma = 0.0, mb = 0.0;
+#pragma unroll
+    for (int t = 0; t < P / 2; ++t) {
+      ma = fmax(ma, fmax(fabs(h1.a[t].x), fabs(h1.a[t].y)));
+      mb = fmax(mb, fmax(fabs(h1.b[t].x), fabs(h1.b[t].y)));
+    }
+    ma = fmax(ma, fabs(h1.an.x));          // the self-mirrored element kx = N/2 (thread 0; zero elsewhere): hs_pack transforms its
+    mb = fmax(mb, fabs(h1.bn.x));          // real part, so a row that holds nothing else must not count as vanishing
+    unsigned long long* mx = reinterpret_cast<unsigned long long*>(nq_smem + X::LDS_BYTES - 512 - 16 * X::C) + 2 * c;
+    if (j == 0) {
+      mx[0] = 0ull;
+      mx[1] = 0ull;
+    }
+    wg_barrier();
+    row_atomic_max<T>(mx, ma, mb);
+    wg_barrier();
+    const PairScale ps = pair_scale(mx);
+    qw_scale = ps.scale;
+    qw_unscale = ps.unscale;
+  }
+  hs_pack<N, P, T, F, MODE == MODE_COUPLED>(w, h1, j, c, lds, kk, false, false, qw_scale);
   NQ_PHASE_FENCE();
   F::template run<true>(w, j, c, lds, twr);
   double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
@@ -1039,7 +1081,7 @@ k_x_diag(MArr Mq, MArr Mqw, MArr Mphi, const cd* __restrict__ tw, const double* 
 #pragma unroll
   for (int t = 0; t < P; ++t) {
     const double q = w[t].x;
-    qpsi[t] = (MODE == MODE_COUPLED) ? w[t].x - w[t].y : w[t].x;
+    qpsi[t] = (MODE == MODE_COUPLED) ? w[t].x - w[t].y * qw_unscale : w[t].x;
     const double qc = qpsi[t] - qbar;
     s1[0] += q * q;
     s1[1] += qpsi[t] * qpsi[t];
