@@ -360,6 +360,30 @@ int nq_avg_reset(nq_ctx* ctx);
 int nq_avg_info(nq_ctx* ctx, long long* info3);
 int nq_avg_read(nq_ctx* ctx, int plane_index, double* out);
 
+/* Time-mean spectra, spectral transfer and flux, accumulated in the step, single-rank contexts only (slab
+ * contexts refuse every call with -4).  what_mask: NQ_TSPEC_SPECTRA, NQ_TSPEC_TRANSFER or both (-1 otherwise).  A sample is what
+ * nq_diagnostics_binned (NQ_TSPEC_SPECTRA) and nq_transfer_binned (NQ_TSPEC_TRANSFER) would return at that point, bit for bit: the
+ * same passes on the same state (rows: the comments of those two calls above), left on the device -- nothing is downloaded and
+ * the host does not wait.  With both, each of the tick's two products passes runs once per sample and serves the two tables.
+ * Every raw element x of a sample goes S1 += x, S2 += x x; every transfer row also c[b] = sum_{b' <= b} x[b'], added in shell
+ * order one after the other, then P1 += c, P2 += c c (the flux before its sign and factor).  fp64, in sample order, no atomics:
+ * first moments are the sequential sums exactly, x x may be contracted into the add.  every >= 0: every `every`-th step of a step
+ * call since attach ends with one sample, taken last (after the forcing, the particles, the recorder and the averages); 0: never.
+ * attach takes no sample and allocates what the selected calls allocate on their first use (context-owned, kept at detach) and
+ * the tables, (2 x 32 + 4 x NQ_TRANSFER_ROWS) x nb doubles, zero (freed by detach; one that fails is -5 and leaves nothing
+ * attached); sample takes one now; reset zeroes the sums and the sample count, not the step count.  One set per context (-4
+ * while one is attached).  info3 = {samples in the sums, steps since attach, what_mask}; read: table `which` into out, 32 x nb
+ * doubles for NQ_TSPEC_S1 / _S2 (spectra), NQ_TRANSFER_ROWS x nb for NQ_TSPEC_T1 / _T2 (transfer) and NQ_TSPEC_P1 / _P2 (running
+ * sums), nb = nq_spectrum_shells(ctx); the tables of a body that is not attached stay zero.                                    */
+enum { NQ_TSPEC_SPECTRA = 1, NQ_TSPEC_TRANSFER = 2 };
+enum { NQ_TSPEC_S1 = 0, NQ_TSPEC_S2 = 1, NQ_TSPEC_T1 = 2, NQ_TSPEC_T2 = 3, NQ_TSPEC_P1 = 4, NQ_TSPEC_P2 = 5 };
+int nq_tspec_attach(nq_ctx* ctx, int what_mask, int every);
+int nq_tspec_detach(nq_ctx* ctx);
+int nq_tspec_sample(nq_ctx* ctx);
+int nq_tspec_reset(nq_ctx* ctx);
+int nq_tspec_info(nq_ctx* ctx, long long* info3);
+int nq_tspec_read(nq_ctx* ctx, int which, double* out);
+
 /* copy of one ETDRK4 coefficient plane (0:E 1:Eh 2:Q 3:f0 4:fab 5:fc) of equation eq (0: q, (nx, nx/2+1) complex;
  * 1: phi, (nx, nx) complex; 2: QGModel's passive scalar, (nx, nx/2+1)), without the filter folded in; values as the
  * reference's expch, expch_h, Qh, f0, fab, fc (Kernel.py:417-454, QGModel.py:426-461).                           */

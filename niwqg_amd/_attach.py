@@ -1,5 +1,5 @@
-"""What the attachments of the step share: particles.py, forcing.py, frequency.py and averages.py each hang one
-object on a model, in a slot of its ``__dict__``, and every step of that model drives it -- inside ``nq_step`` on fused contexts
+"""What the attachments of the step share: particles.py, forcing.py, frequency.py, averages.py and
+timespectra.py each hang one object on a model, in a slot of its ``__dict__``, and every step of that model drives it -- inside ``nq_step`` on fused contexts
 (csrc/nq_lib.hip: attachments_before_step / attachments_after_step), from ``_anysize._step_etdrk4`` through the two hooks
 below on the any-size path.
 """
@@ -36,7 +36,7 @@ class Ring(object):
 
 
 class Attachment(object):
-    """Base of Particles, Forcing, Recorder and the averages' Accumulator: ``m`` is the model until ``detach``, then None"""
+    """Base of Particles, Forcing, Recorder and the Accumulators of the averages and the time-mean spectra: ``m`` is the model until ``detach``, then None"""
     SLOT = None           # the key in m.__dict__
     LABEL = None          # the prefix of the module's messages
     ALREADY = None        # (exception class, message) of a second attach
@@ -58,7 +58,7 @@ class Attachment(object):
 
 
 def attach(m, any_size, fused, *args):
-    """the tail of the four ``attach`` functions, after their argument checks: one attachment per slot, the any-size or the
+    """the tail of the ``attach`` functions, after their argument checks: one attachment per slot, the any-size or the
     fused flavour by the model's path, none on slab contexts"""
     if m.__dict__.get(fused.SLOT) is not None:
         raise fused.ALREADY[0](fused.ALREADY[1])
@@ -81,8 +81,9 @@ def before_step(m):
 
 def after_step(m):
     # the forcing first: the forced, re-inverted state is what the particles' U1, the record of this step, the averages' sample
-    # and the next step see
-    for slot in ("_forcing", "_particles", "_frequency", "_averages"):
+    # and the next step see; the time-mean spectra (timespectra.py) come last, after the four attachments of section 5k (whose
+    # order tests/test_averages_host.py reads from this line as it stands)
+    for slot in ("_forcing", "_particles", "_frequency", "_averages") + ("_timespectra",):
         A = m.__dict__.get(slot)
         if A is not None:
             A._after_step()

@@ -545,3 +545,29 @@ class Context:
         out = np.empty((self.nx, self.nx), np.complex128 if cplx else np.float64)
         self._chk(self.L.nq_avg_read(self.h, int(index), _dptr(out.view(np.float64))), "nq_avg_read")
         return out
+
+    # ---- time-mean spectra, transfer and flux (include/niwqg_amd.h: nq_tspec_*; niwqg_amd/timespectra.py) ---------------------------
+    def tspec_attach(self, mask, every):
+        self._chk(self.L.nq_tspec_attach(self.h, int(mask), int(every)), "nq_tspec_attach")
+
+    def tspec_detach(self):
+        self._chk(self.L.nq_tspec_detach(self.h), "nq_tspec_detach")
+
+    def tspec_sample(self):
+        self._chk(self.L.nq_tspec_sample(self.h), "nq_tspec_sample")
+
+    def tspec_reset(self):
+        self._chk(self.L.nq_tspec_reset(self.h), "nq_tspec_reset")
+
+    def tspec_info(self):
+        """(samples in the sums, steps since attach, mask)"""
+        out = (ctypes.c_longlong * 3)()
+        self._chk(self.L.nq_tspec_info(self.h, out), "nq_tspec_info")
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def tspec_read(self, which):
+        """table `which` (TSPEC_S1 .. TSPEC_P2): (32, nb) for the spectra's two, (TRANSFER_ROWS, nb) for the others"""
+        nb = int(self.L.nq_spectrum_shells(self.h))
+        out = np.zeros((32 if which in (TSPEC_S1, TSPEC_S2) else TRANSFER_ROWS, nb))
+        self._chk(self.L.nq_tspec_read(self.h, int(which), _dptr(out)), "nq_tspec_read")
+        return out

@@ -121,6 +121,8 @@ struct NqAvg : DevOwned {                  // time-mean and covariance maps (sec
   FlowSel sel = {};
   RecordRing rg;                           // cap = 1: only tick() and the two counters are used (count = samples in the sums)
 };
+#include "nq_tspec.hpp"                    // NqTspec and its kernel: time-mean spectra, transfer and flux (section 5n)
+static_assert(TSPEC_TR_ROWS == NQ_TRANSFER_ROWS, "rows of nq_transfer_binned");
 
 struct nq_ctx {
   nq_params p;
@@ -262,6 +264,7 @@ struct nq_ctx {
   NqForcing* fc = nullptr;            // stochastic forcing (nq_forcing_attach): null when none
   NqFreq* fq = nullptr;               // low-mode time-series recorder (nq_freq_attach): null when none
   NqAvg* av = nullptr;                // time-mean and covariance maps (nq_avg_attach): null when none
+  NqTspec* ts = nullptr;              // time-mean spectra, transfer and flux (nq_tspec_attach): null when none
 };
 
 // Device arrays start at staggered offsets inside their allocations.  hipMalloc hands out large blocks at addresses that
@@ -311,7 +314,7 @@ static int att_alloc(nq_ctx* c, DevOwned* o, Tp** out, size_t count, const char*
   *out = static_cast<Tp*>(p);
   return 0;
 }
-// detach: the stream drains, the memory goes back, the slot (c->pt, c->fc, c->fq, c->av) is null again
+// detach: the stream drains, the memory goes back, the slot (c->pt, c->fc, c->fq, c->av, c->ts) is null again
 template <typename A>
 static void att_release(nq_ctx* c, A*& slot) {
   if (!slot) return;
@@ -2809,6 +2812,7 @@ int nq_destroy(nq_ctx* c) {
   att_release(c, c->fc);
   att_release(c, c->fq);
   att_release(c, c->av);
+  att_release(c, c->ts);
   for (void* p : c->allocs) hipFree(p);
   for (auto& pt : c->patch) { (void)hipFree(pt.l); (void)hipFree(pt.k); (void)hipFree(pt.v); }
   for (hipEvent_t e : c->prof_ev) hipEventDestroy(e);
@@ -4802,7 +4806,8 @@ int nq_spectrum_shells(const nq_ctx* c) { return c ? nq_shell_count(c->N) : -1; 
 // The same passes as the tick (the two products passes included, so its side effects are the tick's), the binning kernels in
 // place of the workgroup sums.
 // this context's local columns: allocate, zero, and bin the spectral rows ([0..3], [6..14], [16..19]) into spec_out
-static int bin_local_spectral(nq_ctx* x, int nb) {
+// (*qh_binned, when asked for: the q-hat that was binned -- on dual-copy contexts the mean in the scratch plane)
+static int bin_local_spectral(nq_ctx* x, int nb, const cd** qh_binned = nullptr) {
   const int N = x->N;
   const bool waves = x->kernel_family;
   if (!x->spec_out) ALLOC(x, x->spec_out, (size_t)32 * nb);
@@ -4811,6 +4816,7 @@ static int bin_local_spectral(nq_ctx* x, int nb) {
   HIPCHK(x, hipMemsetAsync(d, 0, sizeof(double) * 32 * nb, x->stream));
   const cd* qh = x->q.y[x->q.cur];
   SLABTRY(mean_qh(x, &qh));                           // as the tick
+  if (qh_binned) *qh_binned = qh;
   if (waves && x->Wf > 0) {
     const BinPhi t{(const cd*)x->w.y[x->w.cur], x->Wf, x->kk, x->ll};
     hipLaunchKernelGGL(k_bin_shells<BinPhi>, dim3(nb), dim3(256), 0, x->stream, t, N, nb, 1, x->kf0, x->Wf, d);
@@ -4836,9 +4842,9 @@ static void bin_local_project(nq_ctx* x, int nb, int which) {
   hipLaunchKernelGGL(k_bin_shells<BinProj>, dim3(nb), dim3(256), 0, x->stream, t, x->N, nb, 1, x->kf0, x->Wf, x->spec_out + (size_t)(24 + 4 * which) * nb);
 }
 
-// every context bins its own columns, the products passes exchange as the tick's do, and the contexts are summed in rank order
-// on the host
-static int tick_binned(std::vector<nq_ctx*>& grp, const char* fn, int nb, double* out) {
+// every context bins its own columns, the products passes exchange as the tick's do (the device part: nothing is downloaded and
+// the host does not wait; every context's spec_out is complete in stream order), and the contexts are summed in rank order on the host
+static int tick_binned_device(std::vector<nq_ctx*>& grp, const char* fn, int nb) {
   SLABTRY(tick_need_phi(grp, fn));
   SLABTRY(slab_settle(grp));
   for (nq_ctx* x : each(grp)) SLABTRY(bin_local_spectral(x, nb));
@@ -4853,6 +4859,10 @@ static int tick_binned(std::vector<nq_ctx*>& grp, const char* fn, int nb, double
       }
     }
   }
+  return 0;
+}
+static int tick_binned(std::vector<nq_ctx*>& grp, const char* fn, int nb, double* out) {
+  SLABTRY(tick_binned_device(grp, fn, nb));
   return sum_ranks_on_host(grp, &nq_ctx::spec_out, (size_t)32 * nb, out);
 }
 int nq_diagnostics_binned(nq_ctx* c, int nb, double* out) {
@@ -4881,7 +4891,8 @@ struct TrPlanes {
   cd *h0, *h1, *f;
   const cd* qh;
 };
-static int transfer_begin(nq_ctx* x, int nb, TrPlanes* t) {
+// qh_mean: the q-hat a caller has formed already (tick_both_device: what bin_local_spectral binned); null: formed here
+static int transfer_begin(nq_ctx* x, int nb, TrPlanes* t, const cd* qh_mean = nullptr) {
   const int N = x->N;
   if (!x->tr_out) ALLOC(x, x->tr_out, (size_t)NQ_TRANSFER_ROWS * nb);
   HIPCHK(x, hipMemsetAsync(x->tr_out, 0, sizeof(double) * NQ_TRANSFER_ROWS * nb, x->stream));
@@ -4896,21 +4907,25 @@ static int transfer_begin(nq_ctx* x, int nb, TrPlanes* t) {
     t->h1 = x->tr_h ? x->tr_h + (size_t)N * x->Ph : nullptr;
     t->f = x->tr_f;
   }
-  t->qh = x->q.y[x->q.cur];
-  if (!x->ybj) SLABTRY(mean_qh(x, &t->qh));           // the q-hat the tick bins
+  t->qh = qh_mean ? qh_mean : x->q.y[x->q.cur];
+  if (!x->ybj && !qh_mean) SLABTRY(mean_qh(x, &t->qh));           // the q-hat the tick bins
   return 0;
 }
-// after the products pass `which` (0: J and the balanced / scalar products, 1: R) and its exchange: A sub-pass, B into the
-// scratch planes, bin into tr_out
-static void transfer_bin_pass(nq_ctx* x, int nb, int which, const TrPlanes& t) {
+// after the products pass `which` (0: J and the balanced / scalar products, 1: R) and its exchange: A sub-pass (transfer_A),
+// then B into the scratch planes and the bins into tr_out (transfer_B_bin); Mw stays as the A sub-pass left it
+static void transfer_A(nq_ctx* x, int which) {
+  const bool waves = x->kernel_family, balanced = !x->ybj, passive = !waves && x->passive;
+  if (which != 0) launch_A_m(x, false, {&x->mW});
+  else if (waves && balanced) launch_A_m(x, false, {&x->mUq, &x->mVq, &x->mW});
+  else if (waves) launch_A_m(x, false, {&x->mW});
+  else if (passive) launch_A_m(x, false, {&x->mUq, &x->mVq, &x->mUc, &x->mVc});
+  else launch_A_m(x, false, {&x->mUq, &x->mVq});
+}
+static void transfer_B_bin(nq_ctx* x, int nb, int which, const TrPlanes& t) {
   const int N = x->N;
   const bool waves = x->kernel_family, balanced = !x->ybj, passive = !waves && x->passive;
   double* d = x->tr_out;
   if (which == 0) {
-    if (waves && balanced) launch_A_m(x, false, {&x->mUq, &x->mVq, &x->mW});
-    else if (waves) launch_A_m(x, false, {&x->mW});
-    else if (passive) launch_A_m(x, false, {&x->mUq, &x->mVq, &x->mUc, &x->mVc});
-    else launch_A_m(x, false, {&x->mUq, &x->mVq});
     if (balanced && x->Wh > 0) {
       launch_B_p(x, false, x->mUq.ys, x->mUq.pitch, t.h0, x->Ph, x->Wh, 1.0);
       launch_B_p(x, false, x->mVq.ys, x->mVq.pitch, t.h1, x->Ph, x->Wh, 1.0);
@@ -4923,8 +4938,6 @@ static void transfer_bin_pass(nq_ctx* x, int nb, int which, const TrPlanes& t) {
       const BinTrC bc{HalfJac{t.h0, t.h1, N, x->Ph, x->kk, x->ll}, (const cd*)x->cq.y[x->cq.cur]};
       hipLaunchKernelGGL(k_bin_shells<BinTrC>, dim3(nb), dim3(256), 0, x->stream, bc, N, nb, 0, x->kh0, x->Wh, d + (size_t)4 * nb);
     }
-  } else {
-    launch_A_m(x, false, {&x->mW});
   }
   if (waves && x->Wf > 0) {
     launch_B_p(x, false, x->mW.ys, x->mW.pitch, t.f, x->Wf, x->Wf, 1.0);
@@ -4932,8 +4945,13 @@ static void transfer_bin_pass(nq_ctx* x, int nb, int which, const TrPlanes& t) {
     hipLaunchKernelGGL(k_bin_shells<BinTrW>, dim3(nb), dim3(256), 0, x->stream, bw, N, nb, 1, x->kf0, x->Wf, d + (size_t)(2 + which) * nb);
   }
 }
+static void transfer_bin_pass(nq_ctx* x, int nb, int which, const TrPlanes& t) {
+  transfer_A(x, which);
+  transfer_B_bin(x, nb, which, t);
+}
 
-static int tick_transfer(std::vector<nq_ctx*>& grp, const char* fn, int nb, double* out) {
+// the device part: every context's tr_out is complete in stream order, nothing is downloaded and the host does not wait
+static int tick_transfer_device(std::vector<nq_ctx*>& grp, const char* fn, int nb) {
   SLABTRY(tick_need_phi(grp, fn));
   SLABTRY(slab_settle(grp));
   std::vector<TrPlanes> t(grp.size());
@@ -4952,7 +4970,35 @@ static int tick_transfer(std::vector<nq_ctx*>& grp, const char* fn, int nb, doub
       transfer_bin_pass(grp[r], nb, which, t[r]);
     }
   }
+  return 0;
+}
+static int tick_transfer(std::vector<nq_ctx*>& grp, const char* fn, int nb, double* out) {
+  SLABTRY(tick_transfer_device(grp, fn, nb));
   return sum_ranks_on_host(grp, &nq_ctx::tr_out, (size_t)NQ_TRANSFER_ROWS * nb, out);
+}
+// Both tables of one single-rank context from ONE run of each products pass (the samples of nq_tspec_attach with both bodies;
+// DESIGN.md section 5n).  spec_out and tr_out end up bit for bit what the two calls above leave there one after the other:
+// the window is the whole slab either way on one rank, the mean of the two q-hat copies is formed once and serves both, the A
+// sub-pass over the transfer's list transforms Mw exactly as the one over Mw alone does (one workgroup column per array), and
+// k_s_project_bin only reads Mw, so the B pass finds it as the A sub-pass left it.
+static int tick_both_device(nq_ctx* x, const char* fn, int nb) {
+  std::vector<nq_ctx*> grp(1, x);
+  SLABTRY(tick_need_phi(grp, fn));
+  SLABTRY(slab_settle(grp));
+  const cd* qh = nullptr;
+  SLABTRY(bin_local_spectral(x, nb, &qh));
+  TrPlanes t;
+  SLABTRY(transfer_begin(x, nb, &t, x->dual ? qh : nullptr));
+  const bool waves = x->kernel_family;
+  for (int which = 0; which < (waves ? 2 : 1); ++which) {
+    set_window(x, 0, 1);
+    launch_products_pass(x, which);
+    SLABTRY(exchange_now(grp, 0, true));
+    transfer_A(x, which);
+    if (waves && x->Wf > 0) bin_local_project(x, nb, which);
+    transfer_B_bin(x, nb, which, t);
+  }
+  return 0;
 }
 int nq_transfer_binned(nq_ctx* c, int nb, double* out) {
   NQ_SINGLE_RANK(c, "nq_transfer_binned");
@@ -5777,11 +5823,34 @@ static int av_after_step(nq_ctx* c) {
   return c->av->rg.tick() ? av_sample(c, "nq_step (averages)") : 0;
 }
 
+// ---- time-mean spectra, transfer and flux (kernel: csrc/nq_tspec.hpp) -------------------------------------
+// one sample: the device parts of nq_diagnostics_binned and / or nq_transfer_binned on the current state -- with both bodies, each
+// products pass once for the two of them -- and one launch that adds what they left in spec_out / tr_out to the sums.  Nothing is
+// downloaded and the host does not wait; the planes and tables the bodies write were allocated at attach.
+static int ts_sample(nq_ctx* c, const char* what) {
+  NqTspec* T = c->ts;
+  const bool sp = T->mask & NQ_TSPEC_SPECTRA, tr = T->mask & NQ_TSPEC_TRANSFER;
+  std::vector<nq_ctx*> grp(1, c);
+  if (sp && tr) SLABTRY(tick_both_device(c, what, T->nb));
+  else if (sp) SLABTRY(tick_binned_device(grp, what, T->nb));
+  else SLABTRY(tick_transfer_device(grp, what, T->nb));
+  TspecArgs a = T->args;
+  a.spec = sp ? c->spec_out : nullptr;
+  a.tr = tr ? c->tr_out : nullptr;
+  hipLaunchKernelGGL(k_tspec_accumulate, dim3(tspec_grid(sp, tr, T->nb)), dim3(TSPEC_THREADS), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  ++T->rg.count;
+  return 0;
+}
+static int ts_after_step(nq_ctx* c) {
+  return c->ts->rg.tick() ? ts_sample(c, "nq_step (time-mean spectra)") : 0;
+}
+
 // ---- nq_step's hooks (declared below dev_alloc) ----------------------------------------------------------------------------
 // Before the step the particles form U0 from the state it starts from.  After it: the forcing first -- the forced, re-inverted
 // state is what the particles' U1 and the next step see -- then the particles, then the recorder, whose record of this step
-// is that same forced, re-inverted state, then the averages, which add that state to their sums.  The first non-zero return
-// code ends the call.
+// is that same forced, re-inverted state, then the averages, which add that state to their sums, and last the time-mean spectra,
+// whose sample is what the binned host calls would return right after this step.  The first non-zero return code ends the call.
 static void attachments_before_step(nq_ctx* c) {
   if (c->pt) pt_before_step(c);
 }
@@ -5790,6 +5859,7 @@ static int attachments_after_step(nq_ctx* c) {
   if (!rc && c->pt) rc = pt_after_step(c);
   if (!rc && c->fq) rc = fq_after_step(c);
   if (!rc && c->av) rc = av_after_step(c);
+  if (!rc && c->ts) rc = ts_after_step(c);
   return rc;
 }
 
@@ -6031,6 +6101,82 @@ int nq_avg_read(nq_ctx* c, int plane_index, double* out) {
   HIPCHK(c, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, c->stream));
   return nq_sync(c);
 }
+
+// ---- time-mean spectra, transfer and flux -----------------------------------------------------------------
+int nq_tspec_attach(nq_ctx* c, int what_mask, int every) {
+  NQ_SINGLE_RANK(c, "nq_tspec_attach");
+  if (c->ts) NQ_FAIL(c, -4, "nq_tspec_attach: time-mean spectra are attached already (nq_tspec_detach first)");
+  if (what_mask < 1 || what_mask > (NQ_TSPEC_SPECTRA | NQ_TSPEC_TRANSFER))
+    NQ_FAIL(c, -1, "nq_tspec_attach: what_mask = %d (NQ_TSPEC_SPECTRA | NQ_TSPEC_TRANSFER, at least one)", what_mask);
+  if (every < 0) NQ_FAIL(c, -1, "nq_tspec_attach: every = %d (>= 0)", every);
+  const int nb = nq_shell_count(c->N);
+  if (nb < 1 || nb > TSPEC_MAX_NB) NQ_FAIL(c, -1, "nq_tspec_attach: %d shells (1 to %d: the LDS row of the running sum)", nb, TSPEC_MAX_NB);
+  HIPCHK(c, hipSetDevice(c->device));
+  // what the selected bodies allocate on their first call: here, so that no sample allocates; context-owned, as ever
+  if ((what_mask & NQ_TSPEC_SPECTRA) && !c->spec_out) ALLOC(c, c->spec_out, (size_t)32 * nb);
+  if ((what_mask & NQ_TSPEC_SPECTRA) && c->kernel_family && !c->spec_r) ALLOC(c, c->spec_r, (size_t)2 * c->N * c->Wf);
+  if ((what_mask & NQ_TSPEC_TRANSFER) && !c->tr_out) ALLOC(c, c->tr_out, (size_t)NQ_TRANSFER_ROWS * nb);
+  c->ts = new NqTspec();
+  NqTspec* T = c->ts;
+  T->mask = what_mask;
+  T->nb = nb;
+  T->rg.init(1, every);
+  const int rc = att_alloc(c, T, &T->tab, T->doubles(), "nq_tspec_attach");
+  if (rc) return att_fail(c, c->ts, rc);
+  const size_t ns = (size_t)TSPEC_SPEC_ROWS * nb, nt = (size_t)TSPEC_TR_ROWS * nb;
+  T->args.nb = nb;
+  T->args.s1 = T->tab;
+  T->args.s2 = T->tab + ns;
+  T->args.t1 = T->tab + 2 * ns;
+  T->args.t2 = T->tab + 2 * ns + nt;
+  T->args.p1 = T->tab + 2 * ns + 2 * nt;
+  T->args.p2 = T->tab + 2 * ns + 3 * nt;
+  return 0;
+}
+int nq_tspec_detach(nq_ctx* c) {
+  NQ_SINGLE_RANK(c, "nq_tspec_detach");
+  if (!c->ts) NQ_FAIL(c, -4, "nq_tspec_detach: no time-mean spectra attached");
+  att_release(c, c->ts);
+  return 0;
+}
+int nq_tspec_sample(nq_ctx* c) {
+  NQ_SINGLE_RANK(c, "nq_tspec_sample");
+  if (!c->ts) NQ_FAIL(c, -4, "nq_tspec_sample: no time-mean spectra attached");
+  HIPCHK(c, hipSetDevice(c->device));
+  return ts_sample(c, "nq_tspec_sample");
+}
+int nq_tspec_reset(nq_ctx* c) {
+  NQ_SINGLE_RANK(c, "nq_tspec_reset");
+  NqTspec* T = c->ts;
+  if (!T) NQ_FAIL(c, -4, "nq_tspec_reset: no time-mean spectra attached");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemsetAsync(T->tab, 0, sizeof(double) * T->doubles(), c->stream));
+  T->rg.count = 0;
+  return 0;
+}
+int nq_tspec_info(nq_ctx* c, long long* info3) {
+  NQ_SINGLE_RANK(c, "nq_tspec_info");
+  NqTspec* T = c->ts;
+  if (!T) NQ_FAIL(c, -4, "nq_tspec_info: no time-mean spectra attached");
+  if (!info3) return -1;
+  info3[0] = T->rg.count;
+  info3[1] = T->rg.steps;
+  info3[2] = T->mask;
+  return 0;
+}
+int nq_tspec_read(nq_ctx* c, int which, double* out) {
+  NQ_SINGLE_RANK(c, "nq_tspec_read");
+  NqTspec* T = c->ts;
+  if (!T) NQ_FAIL(c, -4, "nq_tspec_read: no time-mean spectra attached");
+  if (!out) return -1;
+  if (which < 0 || which >= TSPEC_TABLES) NQ_FAIL(c, -1, "nq_tspec_read: table %d (NQ_TSPEC_S1 .. NQ_TSPEC_P2 = 0 .. %d)", which, TSPEC_TABLES - 1);
+  const double* src[TSPEC_TABLES] = {T->args.s1, T->args.s2, T->args.t1, T->args.t2, T->args.p1, T->args.p2};
+  const size_t n = (size_t)(which < 2 ? TSPEC_SPEC_ROWS : TSPEC_TR_ROWS) * T->nb;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(out, src[which], sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+  return nq_sync(c);
+}
+
 // One sample on engine planes (the any-size path steps from Python and calls this after its own step): the rule and the kernel of
 // QGModel's fused contexts.  src[i] (complex engine planes of `elems` values) read as what[i] (0: Re, 1: |a|^2, 2: the complex
 // value itself, at most once and in no product) is added to sums[i] (elems doubles; what 2: elems complex); pairs: 2 x nproducts
