@@ -384,6 +384,35 @@ int nq_tspec_reset(nq_ctx* ctx);
 int nq_tspec_info(nq_ctx* ctx, long long* info3);
 int nq_tspec_read(nq_ctx* ctx, int which, double* out);
 
+/* Coarse-grained (sub-filter) energy and enstrophy flux maps, formed on the device, single-rank fused
+ * contexts only (slab contexts: -4).  G is a real isotropic filter given per shell, G(l, k) = g[b] with the shell rule of
+ * nq_diagnostics_binned, an overbar is F^-1[G .].  The planes are those nq_transfer_binned bins: P = psi-hat, Q = the q-hat the
+ * tick bins (dual_q contexts: the mean of the two copies), Fu = F[u q], Fv = F[v q], W = the CURRENT phi-hat, J = the J plane of
+ * the tick's first products pass (UnCoupledModel, YBJModel: with the stale gradients of quirk Q1).  With u-bar = Re F^-1[-il G P],
+ * v-bar = Re F^-1[ik G P], q-bar and its gradient from G Q, phi-bar and its gradient from G W:
+ *   NQ_CG_KE   ke_qg       v-bar F^-1[G Fu] - u-bar F^-1[G Fv]                                    CoupledModel, UnCoupledModel, QGModel
+ *   NQ_CG_ENS  ens         -(F^-1[G Fu] - u-bar q-bar) q-bar_x - (F^-1[G Fv] - v-bar q-bar) q-bar_y   the same three
+ *   NQ_CG_NIW  ke_niw_adv  Re(conj(phi-bar) (F^-1[G J] - u-bar phi-bar_x - v-bar phi-bar_y))      CoupledModel, UnCoupledModel, YBJModel
+ * Positive: transfer towards scales below the cut.  For the sharp filter at shell B (g = 1 on b <= B, else 0) the plane mean of a
+ * map is the spectral flux through the cut, -sum_{b <= B} of the transfer nq_transfer_binned gives (ke_qg: every B < nx/2; ens,
+ * ke_niw_adv: 3 B < nx, while the resolved triple product is alias-free).
+ * NYQUIST RULE: every table is zero on the shells b >= nx/2 (-1 otherwise): row ny/2, column nx/2, the passenger row of q-hat and
+ * the Hermitian-part rules of the self-mirrored column nx/2 then have nothing in any filtered plane.
+ * g: nscales (1..NQ_CG_MAX_SCALES) tables of nb = nq_spectrum_shells(ctx) finite values.  moments[s][m][0..1]: the sum and the sum
+ * of squares over the plane of map m (0 ke_qg, 1 ens, 2 ke_niw_adv) at scale s, zero for a map that was not selected, from
+ * per-workgroup partials added in a fixed order (no floating-point atomics: two calls are bit-identical).  maps: NULL, or per
+ * scale the selected maps in bit order, (ny, nx) doubles each.  A mask the model lacks, a wrong nb, a non-finite entry, a non-zero
+ * entry from shell nx/2 on and nx = 8192 (no row plan that holds the maps in registers) are -1 before any launch.  The products
+ * pass runs once per call and serves all scales.  The first call allocates the filtered planes (two copies, spectral and mixed
+ * space, of up to six half-spectrum and three full planes), the first call with maps != NULL one plane per map of the model;
+ * counted by nq_device_bytes, freed with the context; an allocation that fails is -5 and leaves the context as it was.  Reads
+ * the state; writes only these buffers and the scratch planes nq_transfer_binned writes.                                       */
+enum { NQ_CG_KE = 1, NQ_CG_ENS = 2, NQ_CG_NIW = 4 };
+#define NQ_CG_MAX_SCALES 64
+int nq_coarse_flux(nq_ctx* ctx, int what_mask, int nscales, const double* g /* nscales x nb */, int nb,
+                   double* moments /* nscales x 3 x 2: sum, sum of squares per map; unselected: 0 */,
+                   double* maps    /* NULL, or nscales x (selected maps, in bit order) x ny x nx */);
+
 /* copy of one ETDRK4 coefficient plane (0:E 1:Eh 2:Q 3:f0 4:fab 5:fc) of equation eq (0: q, (nx, nx/2+1) complex;
  * 1: phi, (nx, nx) complex; 2: QGModel's passive scalar, (nx, nx/2+1)), without the filter folded in; values as the
  * reference's expch, expch_h, Qh, f0, fab, fc (Kernel.py:417-454, QGModel.py:426-461).                           */

@@ -17,3 +17,4 @@ from . import CoupledModel   # noqa: F401
 from . import UnCoupledModel   # noqa: F401
 from . import QGModel   # noqa: F401
 from . import YBJModel   # noqa: F401
+from . import coarse   # noqa: F401

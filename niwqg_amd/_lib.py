@@ -306,6 +306,17 @@ class Context:
         self._chk(self.L.nq_transfer_binned(self.h, nb, _dptr(out)), "nq_transfer_binned")
         return out
 
+    def coarse_flux(self, mask, tables, nmaps):
+        """(moments (nscales, 3, 2): sum and sum of squares per map, maps (nscales, nmaps, ny, nx) or None when nmaps = 0) of the
+        coarse-grained flux maps selected by mask (CG_*) for the filter tables (nscales, nb) (include/niwqg_amd.h: nq_coarse_flux)"""
+        tables = np.ascontiguousarray(tables, np.float64)
+        self._shape(tables, (tables.shape[0], int(self.L.nq_spectrum_shells(self.h))), "coarse_flux")
+        mom = np.zeros((tables.shape[0], 3, 2))
+        maps = np.empty((tables.shape[0], nmaps, self.nx, self.nx)) if nmaps else None
+        self._chk(self.L.nq_coarse_flux(self.h, int(mask), tables.shape[0], _dptr(tables), tables.shape[1], _dptr(mom),
+                                        _dptr(maps) if nmaps else None), "nq_coarse_flux")
+        return mom, maps
+
     def coeff(self, eq, which):
         n = self.nx
         w = n if eq == 1 else n // 2 + 1

@@ -265,6 +265,14 @@ struct nq_ctx {
   NqFreq* fq = nullptr;               // low-mode time-series recorder (nq_freq_attach): null when none
   NqAvg* av = nullptr;                // time-mean and covariance maps (nq_avg_attach): null when none
   NqTspec* ts = nullptr;              // time-mean spectra, transfer and flux (nq_tspec_attach): null when none
+  // coarse-grained flux maps (nq_coarse_flux): the filtered planes in spectral (s*) and mixed space (m*),
+  // half-spectrum {G P, -il G P, G Q, il G Q, G Fu, G Fv} and full {G W, il G W, G J}, the tables, the workgroup partials, the
+  // moments and the map planes; allocated by the first call (the map planes: the first that asks for maps), context-owned
+  struct Coarse {
+    cd *sh[6] = {}, *mh[6] = {}, *sf[3] = {}, *mf[3] = {};
+    double *g = nullptr, *part = nullptr, *mom = nullptr, *map[3] = {};
+    bool ready = false, have_maps = false;
+  } cg;
 };
 
 // Device arrays start at staggered offsets inside their allocations.  hipMalloc hands out large blocks at addresses that
@@ -2382,6 +2390,9 @@ __global__ void __launch_bounds__(256) k_stream_copy(const double2* __restrict__
   }
   for (; i < n; i += step) dst[i] = src[i];
 }
+#include "nq_coarse.hpp"                   // the kernels of nq_coarse_flux (section 5o); after the shell rule above
+static_assert(CG_KE == NQ_CG_KE && CG_ENS == NQ_CG_ENS && CG_NIW == NQ_CG_NIW, "map bits of nq_coarse_flux");
+
 extern "C" {
 
 const char* nq_last_error(const nq_ctx* ctx) { return ctx ? ctx->err.c_str() : g_last_error.c_str(); }
@@ -5014,6 +5025,155 @@ int nq_slab_transfer_binned(nq_ctx* c, int nb, double* out) {
   std::vector<nq_ctx*> grp;
   SLABTRY(slab_group(c, &grp));
   return tick_transfer(grp, "nq_slab_transfer_binned", nb, out);
+}
+
+// ---- coarse-grained flux maps ---------------------------------------------------------------------------
+// The tick's first products pass again, B-transformed into the scratch planes as the transfer does; then per filter scale
+// k_s_coarse into the context's own spectral planes, the inverse column passes into its own mixed-space planes, k_x_coarse.
+static int coarse_model_mask(const nq_ctx* c) { return !c->kernel_family ? (CG_KE | CG_ENS) : c->ybj ? CG_NIW : (CG_KE | CG_ENS | CG_NIW); }
+// the planes of the first call (and the map planes of the first call that asks for maps): all of them or none
+static int coarse_reserve(nq_ctx* c, int nb, bool maps) {
+  nq_ctx::Coarse& k = c->cg;
+  const size_t N = (size_t)c->N, half = N * c->Ph * sizeof(cd), full = N * N * sizeof(cd);
+  std::vector<std::pair<void**, size_t>> want;
+  if (!k.ready) {
+    for (int i = 0; i < (c->ybj ? 2 : 6); ++i) {
+      want.push_back({(void**)&k.sh[i], half});
+      want.push_back({(void**)&k.mh[i], half});
+    }
+    for (int i = 0; i < (c->kernel_family ? 3 : 0); ++i) {
+      want.push_back({(void**)&k.sf[i], full});
+      want.push_back({(void**)&k.mf[i], full});
+    }
+    want.push_back({(void**)&k.g, sizeof(double) * NQ_CG_MAX_SCALES * nb});
+    want.push_back({(void**)&k.part, sizeof(double) * 6 * N});
+    want.push_back({(void**)&k.mom, sizeof(double) * 6 * NQ_CG_MAX_SCALES});
+  }
+  if (maps && !k.have_maps)
+    for (int m = 0; m < 3; ++m)
+      if (coarse_model_mask(c) & (1 << m)) want.push_back({(void**)&k.map[m], sizeof(double) * N * N});
+  size_t got = 0, total = 0;
+  for (; got < want.size(); ++got) {
+    if (hipMalloc(want[got].first, want[got].second) != hipSuccess) break;
+    total += want[got].second;
+  }
+  if (got < want.size()) {
+    (void)hipGetLastError();
+    const size_t bytes = want[got].second;
+    for (size_t i = 0; i <= got && i < want.size(); ++i) {
+      if (i < got) (void)hipFree(*want[i].first);
+      *want[i].first = nullptr;
+    }
+    NQ_FAIL(c, -5, "nq_coarse_flux: cannot allocate %zu bytes of device memory", bytes);
+  }
+  for (auto& w : want) {
+    HIPCHK(c, hipMemsetAsync(*w.first, 0, w.second, c->stream));
+    c->allocs.push_back(*w.first);
+  }
+  c->bytes += (long long)total;
+  k.ready = true;
+  if (maps) k.have_maps = true;
+  return 0;
+}
+static MArr coarse_rows_of(cd* p, int pitch) {
+  MArr m;
+  m.xs = m.ys = p;
+  m.pitch = pitch;
+  m.W = pitch;
+  m.shift = 30;
+  m.magic = 0;
+  m.blk = 0;
+  return m;
+}
+static void coarse_columns_inverse(nq_ctx* c, cd* const* spec, cd* const* mixed, int n, bool half_planes) {
+  ArrayList al;
+  const int width = half_planes ? c->Wh : c->N, pitch = half_planes ? c->Ph : c->N;
+  for (int i = 0; i < 6; ++i) {
+    al.ptr[i] = i < n ? mixed[i] : nullptr;
+    al.width[i] = i < n ? width : 0;
+    al.pitch[i] = i < n ? pitch : 0;
+  }
+  for (int i = 0; i < n; ++i) launch_B_p(c, true, spec[i], pitch, mixed[i], pitch, width, 1.0 / ((double)c->N * c->N));
+  launch_A_list(c, true, al, n, width);
+}
+int nq_coarse_flux(nq_ctx* c, int what_mask, int nscales, const double* g, int nb, double* moments, double* maps) {
+  NQ_SINGLE_RANK(c, "nq_coarse_flux");
+  const int N = c->N, have = coarse_model_mask(c);
+  if (what_mask <= 0 || (what_mask & ~have))
+    NQ_FAIL(c, -1, "nq_coarse_flux: map mask %d; this model has mask %d (NQ_CG_KE 1, NQ_CG_ENS 2, NQ_CG_NIW 4)", what_mask, have);
+  if (nscales < 1 || nscales > NQ_CG_MAX_SCALES) NQ_FAIL(c, -1, "nq_coarse_flux: %d scales; 1 to %d per call", nscales, NQ_CG_MAX_SCALES);
+  if (!g || !moments) NQ_FAIL(c, -1, "nq_coarse_flux: null table or null moments");
+  if (nb != nq_shell_count(N)) NQ_FAIL(c, -1, "nq_coarse_flux: nb = %d, the grid has %d shells", nb, nq_shell_count(N));
+  for (int s = 0; s < nscales; ++s)
+    for (int b = 0; b < nb; ++b) {
+      const double x = g[(size_t)s * nb + b];
+      if (!std::isfinite(x)) NQ_FAIL(c, -1, "nq_coarse_flux: table %d is not finite on shell %d", s, b);
+      if (b >= N / 2 && x != 0.0) NQ_FAIL(c, -1, "nq_coarse_flux: table %d is %g on shell %d; every table is zero from shell nx/2 = %d on", s, x, b, N / 2);
+    }
+  if (N >= 8192)
+    NQ_FAIL(c, -1, "nq_coarse_flux: no coarse-grained maps at nx = %d: a thread of that row plan has 128 registers, the maps need 7 values per point (DESIGN.md section 7)", N);
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<nq_ctx*> grp(1, c);
+  SLABTRY(tick_need_phi(grp, "nq_coarse_flux"));
+  SLABTRY(slab_settle(grp));
+  SLABTRY(coarse_reserve(c, nb, maps != nullptr));
+  nq_ctx::Coarse& k = c->cg;
+  const bool waves = c->kernel_family, balanced = !c->ybj;
+  const bool need_q = (what_mask & (CG_KE | CG_ENS)) != 0, need_w = (what_mask & CG_NIW) != 0;
+  const cd* qh = c->q.y[c->q.cur];
+  if (balanced && (what_mask & CG_ENS)) SLABTRY(mean_qh(c, &qh));                 // the q-hat the tick bins
+  // the products pass, once for all scales: F[u q], F[v q] into scr_h0, scr_h1, J into scr_f0 (nq_transfer_binned's planes)
+  set_window(c, 0, 1);
+  launch_products_pass(c, 0);
+  SLABTRY(exchange_now(grp, 0, true));
+  transfer_A(c, 0);
+  if (need_q) {
+    launch_B_p(c, false, c->mUq.ys, c->mUq.pitch, c->scr_h0, c->Ph, c->Wh, 1.0);
+    launch_B_p(c, false, c->mVq.ys, c->mVq.pitch, c->scr_h1, c->Ph, c->Wh, 1.0);
+  }
+  if (need_w) launch_B_p(c, false, c->mW.ys, c->mW.pitch, c->scr_f0, c->Wf, c->Wf, 1.0);
+  HIPCHK(c, hipMemcpyAsync(k.g, g, sizeof(double) * (size_t)nscales * nb, hipMemcpyHostToDevice, c->stream));
+  const int nblocks = xdiag_blocks(c);
+  const size_t plane = (size_t)N * N;
+  size_t out_plane = 0;
+  for (int s = 0; s < nscales; ++s) {
+    CoarseSpec sp;
+    sp.P = c->ph; sp.Q = qh; sp.Fu = c->scr_h0; sp.Fv = c->scr_h1;
+    sp.W = waves ? c->w.y[c->w.cur] : nullptr; sp.J = c->scr_f0;
+    sp.gp = k.sh[0]; sp.up = k.sh[1]; sp.gq = k.sh[2]; sp.qy = k.sh[3]; sp.fu = k.sh[4]; sp.fv = k.sh[5];
+    sp.gw = k.sf[0]; sp.wy = k.sf[1]; sp.gj = k.sf[2];
+    sp.g = k.g + (size_t)s * nb; sp.ll = c->ll; sp.N = N; sp.ph = c->Ph; sp.what = what_mask;
+    const int cols = need_w ? N : N / 2 + 1;
+    hipLaunchKernelGGL(k_s_coarse, dim3((cols + 255) / 256, N), dim3(256), 0, c->stream, sp);
+    // the filtered half planes in use: G P, -il G P always; G Q, il G Q for ens; G Fu, G Fv for ke_qg and ens
+    coarse_columns_inverse(c, k.sh, k.mh, 2, true);
+    if (what_mask & CG_ENS) coarse_columns_inverse(c, k.sh + 2, k.mh + 2, 2, true);
+    if (need_q) coarse_columns_inverse(c, k.sh + 4, k.mh + 4, 2, true);
+    if (need_w) coarse_columns_inverse(c, k.sf, k.mf, 3, false);
+    CoarseRows r;
+    r.gp = coarse_rows_of(k.mh[0], c->Ph); r.up = coarse_rows_of(k.mh[1], c->Ph);
+    r.gq = coarse_rows_of(k.mh[2], c->Ph); r.qy = coarse_rows_of(k.mh[3], c->Ph);
+    r.fu = coarse_rows_of(k.mh[4], c->Ph); r.fv = coarse_rows_of(k.mh[5], c->Ph);
+    r.gw = k.mf[0]; r.wy = k.mf[1]; r.gj = k.mf[2];
+    r.what = what_mask;
+    for (int m = 0; m < 3; ++m) r.map[m] = (maps && (what_mask & (1 << m))) ? k.map[m] : nullptr;
+    r.part = k.part;
+    with_row_size(N, [&](auto n) {
+      constexpr int NN = decltype(n)::value;
+      if constexpr (NN < 8192) {
+        typedef XPlan<NN> X;
+        if (waves) hipLaunchKernelGGL((k_x_coarse<NN, true>), dim3(nblocks), dim3(X::THREADS), X::LDS_BYTES, c->stream, r, c->twx, c->kk);
+        else hipLaunchKernelGGL((k_x_coarse<NN, false>), dim3(nblocks), dim3(X::THREADS), X::LDS_BYTES, c->stream, r, c->twx, c->kk);
+      }
+    });
+    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, c->stream, (const double*)k.part, nblocks, 6, 6, k.mom + 6 * (size_t)s);
+    HIPCHK(c, hipGetLastError());
+    if (maps)
+      for (int m = 0; m < 3; ++m)
+        if (what_mask & (1 << m)) HIPCHK(c, hipMemcpyAsync(maps + plane * out_plane++, k.map[m], sizeof(double) * plane, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipMemcpyAsync(moments, k.mom, sizeof(double) * 6 * (size_t)nscales, hipMemcpyDeviceToHost, c->stream));
+  return nq_sync(c);
 }
 
 // fft(phi * q_psi), (ny, nx): the refraction source of ref Kernel.py:332, :350, :367, :385 before its -0.5j factor,
