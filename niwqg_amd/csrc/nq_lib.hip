@@ -139,6 +139,9 @@ struct nq_ctx {
   // mirrored residues launched back to back (pair_order), the second read of a line is served on chip.  NIWQG_AMD_COEF_MIRROR=0
   // keeps all N rows (A/B measurements).
   int cmirror = 0, crows = 0;
+  // k_s_phi forms the phi-hat results of stages 0 and 1 again where a later stage needs them (phi_stage_update) and w.y[(cur+1)%3]
+  // is not allocated.  NIWQG_AMD_PHI_STAGE_STORE=1 stores them and reads them back (A/B measurements, the bit-identity test).
+  int phi_stage_store = 0;
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -1451,11 +1454,22 @@ static BudgetW budget_w(nq_ctx* c, double* part, const cd* y_start) {
   return bw;
 }
 // ophi, ophiy: where phi and phiy of the stage result go, when not to Mphi, Mphiy (do_step_ybj)
-static void launch_sphi(nq_ctx* c, const EtdArrays& ea, int stage, const cd* y_start, const MArr* ophi_ = nullptr,
+// ea_: etd_arrays(c->w, stage) and y_start as the stored data flow has them; without phi_stage_store the kernel forms the
+// results of stages 0 and 1 again from y(t_n) and the stored tendencies, and their planes are neither written nor read
+static void launch_sphi(nq_ctx* c, const EtdArrays& ea_, int stage, const cd* y_start, const MArr* ophi_ = nullptr,
                         const MArr* ophiy_ = nullptr) {
   ProfScope ps(c, PK_SPHI);
   const MArr& ophi = ophi_ ? *ophi_ : c->mPhi;
   const MArr& ophiy = ophiy_ ? *ophiy_ : c->mPhiy;
+  EtdArrays ea = ea_;
+  PhiFlow pf;
+  pf.y_n = c->w.y[c->w.cur];
+  pf.store = c->phi_stage_store;
+  if (!pf.store) {
+    if (stage < 2) ea.y_out = nullptr;
+    if (stage == 2) ea.y_in = nullptr;
+    if (stage == 1 || stage == 2) y_start = nullptr;
+  }
   BudgetW bw = budget_w(c, c->partW + (size_t)stage * c->nww * NQ_PARTW, y_start);
   const cd* jpass = c->ybj ? nullptr : c->mUq.ys + c->mUq.W;     // YBJModel.jacobian_psi_phi keeps [0,0] (YBJModel.py:123-133)
   const cd* jown = (jpass && c->redir_now) ? c->mUq.xs + c->mUq.W : jpass;     // the own block was not copied across (ArrayListR)
@@ -1463,7 +1477,7 @@ static void launch_sphi(nq_ctx* c, const EtdArrays& ea, int stage, const cd* y_s
   with_col_plan(c, [&](auto s1, auto cly) {
     constexpr int S = decltype(s1)::value, CLX = decltype(cly)::value;
     typedef YPlanT<S, CLX> Y;
-    hipLaunchKernelGGL((k_s_phi<S, CLX>), dim3(c->Wf / CLX, c->S2), dim3(Y::THREADS), Y::LDS_BYTES, c->stream, c->mW, jpass, jown, own0, own1, c->mUq.pitch, ea, stage, geom_full(c), ophi, ophiy, 1.0 / ((double)c->N * c->N), c->kk, c->ll, c->tw, 1, bw);
+    hipLaunchKernelGGL((k_s_phi<S, CLX>), dim3(c->Wf / CLX, c->S2), dim3(Y::THREADS), Y::LDS_BYTES, c->stream, c->mW, jpass, jown, own0, own1, c->mUq.pitch, ea, stage, geom_full(c), ophi, ophiy, 1.0 / ((double)c->N * c->N), c->kk, c->ll, c->tw, 1, bw, pf);
   });
 }
 static void launch_emit_phi(nq_ctx* c, const cd* phih) {
@@ -2701,7 +2715,13 @@ static int create_impl(const nq_params* p_in, const double* kk, const double* ll
       ALLOC(c, c->scr_h0, (size_t)64);              // reduction scratch only
     }
     if (c->kernel_family) {
-      for (int i = 0; i < 3; ++i) ALLOC(c, c->w.y[i], full);
+      {
+        const char* e = getenv("NIWQG_AMD_PHI_STAGE_STORE");
+        c->phi_stage_store = (e && atoi(e) != 0) ? 1 : 0;
+      }
+      // slot (cur+1)%3 held the stage-0 result of phi-hat: nothing but k_s_phi's stored data flow touches it (cur never moves)
+      for (int i = 0; i < 3; ++i)
+        if (i != 1 || c->phi_stage_store) ALLOC(c, c->w.y[i], full);
       ALLOC(c, c->w.fn0, full);
       ALLOC(c, c->w.fna, full);
       for (int i = 0; i < 6; ++i) ALLOC(c, c->w.coef[i], full_c);

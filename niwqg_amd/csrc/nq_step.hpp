@@ -1384,6 +1384,73 @@ struct BudgetW {
 };
 constexpr int NQ_PARTW = 6;
 
+// ---- ETDRK4 stage update of one phi-hat element ------------------------------------------------------
+// Same recursion as etd_update, but the results a, b of stages 0 and 1 are inputs of nothing except this kernel's next
+// launches (the stage-2 operand and the `ys` of the projections), and both are Eh*u + Q*N of operands those launches load
+// anyway or can load at the price of loading a or b: stage 1 forms a from u and N1, stage 2 forms a and b from u, N1 and
+// N2, and stages 0 and 1 store no state at all.  c (stage 2) stays stored: the host reads it (NQ_F_PHIH_STAGE4) and N3 is
+// gone once it is folded into N2 + N3.
+// PhiFlow.store (NIWQG_AMD_PHI_STAGE_STORE=1) keeps the stores of a, b and reads them back.
+struct PhiFlow {
+  const cd* y_n;       // y(t_n): the operand a and b are formed from again (stage 2; stages 0, 1 have it as y_in)
+  int store;
+};
+
+// Eh*y + Q*N, the one form of a, b and c: a value formed again has the bits of the value that was stored.  Every
+// rounding is spelled out and contraction is off, so no site's context decides where a multiply and an add are fused.  The
+// shape is the one the compiler gave cadd(cmul(Eh, y), cmul(Q, N)) in etd_update (read off the ISA of k_s_phi before this
+// function existed: the imaginary parts fuse a.y*b.x in Eh*y but a.x*b.y in Q*N), so results are what they were.
+__device__ __forceinline__ cd etd_half_step(cd eh, cd q, cd y, cd n) {
+#pragma clang fp contract(off)
+  const double r1 = __builtin_fma(eh.x, y.x, -(eh.y * y.y)), i1 = __builtin_fma(eh.y, y.x, eh.x * y.y);
+  const double r2 = __builtin_fma(q.x, n.x, -(q.y * n.y)), i2 = __builtin_fma(q.x, n.y, q.y * n.x);
+  return cmake(r1 + r2, i1 + i2);
+}
+
+// returns the stage result; ys <- phih at the start of this stage (with budgets only)
+__device__ __forceinline__ cd phi_stage_update(const EtdArrays& a, const PhiFlow& pf, const BudgetW& bw, bool bud, size_t idx,
+                                               size_t ci, cd Nl, int stage, cd& ys) {
+  cd y;
+  if (stage == 3) {
+    const cd n0 = a.fn0[idx], nab = a.fna[idx];
+    if (bud) ys = bw.y_start[idx];
+    y = cadd(cadd(cmul(a.E[ci], a.y_in[idx]), cmul(a.f0[ci], n0)),
+             cadd(cscale(cmul(a.fab[ci], nab), 2.0), cmul(a.fc[ci], Nl)));
+    a.y_out[idx] = y;
+    return y;
+  }
+  const cd eh = a.Eh[ci], q = a.Q[ci];
+  if (stage == 0) {
+    const cd u = a.y_in[idx];
+    ys = u;
+    y = etd_half_step(eh, q, u, Nl);
+    a.fn0[idx] = Nl;
+    if (pf.store) a.y_out[idx] = y;
+  } else if (stage == 1) {
+    const cd u = a.y_in[idx];
+    if (bud) ys = pf.store ? bw.y_start[idx] : etd_half_step(eh, q, u, a.fn0[idx]);
+    y = etd_half_step(eh, q, u, Nl);
+    a.fna[idx] = Nl;
+    if (pf.store) a.y_out[idx] = y;
+  } else {
+    const cd n0 = a.fn0[idx], na = a.fna[idx];
+    cd ya;
+    if (pf.store) {
+      ya = a.y_in[idx];
+      if (bud) ys = bw.y_start[idx];
+    } else {
+      const cd u = pf.y_n[idx];
+      ya = etd_half_step(eh, q, u, n0);
+      if (bud) ys = etd_half_step(eh, q, u, na);
+    }
+    const cd comb = cmake(__builtin_fma(2.0, Nl.x, -n0.x), __builtin_fma(2.0, Nl.y, -n0.y));      // 2 N3 - N1, fused as it was
+    y = etd_half_step(eh, q, ya, comb);
+    a.fna[idx] = cadd(na, Nl);
+    a.y_out[idx] = y;
+  }
+  return y;
+}
+
 // a[], b[] hold y/M and i*l*y/M on return; budgets: sums over the new y
 template <int P, int T>
 __device__ __forceinline__ void phi_outputs(const cd (&y)[P], cd (&a)[P], cd (&b)[P], int l1, int S2,
@@ -1411,7 +1478,7 @@ template <int S1, int CLX = CL>
 __global__ void __launch_bounds__((YPlanT<S1, CLX>::THREADS))
 k_s_phi(MArr Hw, const cd* __restrict__ jpass, const cd* __restrict__ jpass_own, int own0, int own1, int jpitch, EtdArrays ea, int stage, YGeom g, MArr Hphi, MArr Hphiy,
         double invM, const double* __restrict__ kk, const double* __restrict__ ll, const cd* __restrict__ tw,
-        int tw_step_N, BudgetW bw) {
+        int tw_step_N, BudgetW bw, PhiFlow pf) {
   typedef YPlanT<S1, CLX> Y;
   constexpr int P = Y::P, T = Y::T;
   const int c = threadIdx.x % CLX, j = threadIdx.x / CLX;
@@ -1445,19 +1512,19 @@ k_s_phi(MArr Hw, const cd* __restrict__ jpass, const cd* __restrict__ jpass_own,
   for (int t = 0; t < P; ++t) {
     const int l = l1 + S2 * (j + t * T);
     const size_t idx = (size_t)l * g.pitch_s + k;
+    cd Nl = a[t];                                       // N_phi = -J - 0.5 i R
+    if (l == 0 && kg == 0) Nl = cmake(Nl.x + jfix[0], Nl.y + jfix[1]);
+    cd ys = cmake(0, 0);                                // phih at the start of this stage (what the tendency was computed from)
+    y[t] = phi_stage_update(ea, pf, bw, bud, idx, (size_t)crow(g, l, N) * g.pitch_s + k, Nl, stage, ys);
     if (bud) {
       // With W = F[-J - (i/2) phi q_psi] (un-zeroed), lap_h = -wv2 ys, diss_h = -d ys (ref Kernel.py:691-700):
       //   gamma1 + gamma2 = -hslash/2 sum Re(conj(lap_h) W) / (M^2 f),   xi1 + xi2 = -sum Im(conj(diss_h) W) / (M^2 f)
-      const cd ys = bw.y_start[idx];
       const double ly = ll[l];
       const double wv2 = kx * kx + ly * ly;
       const double d = bw.nu4w * wv2 * wv2 + bw.nuw * wv2 + bw.muw;
       sj[0] += -wv2 * (ys.x * a[t].x + ys.y * a[t].y);
       sj[1] += -d * (ys.x * a[t].y - ys.y * a[t].x);
     }
-    cd Nl = a[t];                                       // N_phi = -J - 0.5 i R
-    if (l == 0 && kg == 0) Nl = cmake(Nl.x + jfix[0], Nl.y + jfix[1]);
-    y[t] = etd_update(ea, idx, (size_t)crow(g, l, N) * g.pitch_s + k, Nl, stage);
   }
   double s4[4] = {0.0, 0.0, 0.0, 0.0};
   phi_outputs<P, T>(y, a, b, l1, S2, j, kg, invM, kk, ll, bud, s4);
@@ -1557,6 +1624,7 @@ k_s_invert(MArr Ha, MArr Hb, const cd* __restrict__ qh, const double* __restrict
   for (int t = 0; t < P; ++t) {
     const int l = l1 + S2 * (j + t * T);
     const size_t idx = (size_t)l * g.pitch_s + k;
+    const size_t fi = (size_t)crow(g, l, N) * g.pitch_s + k;      // cmirror: the filter's rows l and N - l are equal, read one
     const double ly = ll[l];
     const double wv2 = kx * kx + ly * ly;
     const double wv2i = (wv2 != 0.0) ? 1.0 / wv2 : 0.0;
@@ -1570,7 +1638,7 @@ k_s_invert(MArr Ha, MArr Hb, const cd* __restrict__ qh, const double* __restrict
       cd B = b[t];
       if (l == 0 && kg == 0) B = cmake(0, 0);
       const double g = 0.5 * (-wv2);
-      double fl = ok ? filt[idx] : 0.0;
+      double fl = ok ? filt[fi] : 0.0;
       if (filt_m && ok) fl = 0.5 * (fl + filt_m[idx]);     // Hermitian part of filtr * (Hermitian field)
       qw = cmake(0.5 * (g * a[t].x + B.x) / f * fl, 0.5 * (g * a[t].y + B.y) / f * fl);
       psi = cmake(wv2i * (qw.x - qv.x), wv2i * (qw.y - qv.y));
