@@ -413,6 +413,32 @@ int nq_coarse_flux(nq_ctx* ctx, int what_mask, int nscales, const double* g /* n
                    double* moments /* nscales x 3 x 2: sum, sum of squares per map; unselected: 0 */,
                    double* maps    /* NULL, or nscales x (selected maps, in bit order) x ny x nx */);
 
+/* Shell-to-shell (giver-receiver) transfers, formed on the device, single-rank fused contexts only (slab
+ * contexts: -4).  T(b | Q) is the transfer into receiver shell b with the ADVECTED field restricted to a donor band Q, a real
+ * table g_Q per shell (shell rule and NYQUIST RULE of nq_coarse_flux: zero on the shells b >= nx/2, -1 otherwise),
+ * G_Q(l, k) = g_Q[b].  The state is the one nq_transfer_binned sees: P = psi-hat, Q-hat = the q-hat the tick bins (dual_q contexts:
+ * the mean of the two copies), W = the CURRENT phi-hat, u, v and q_psi those of the tick's products pass.  With
+ * q^Q = Re F^-1[G_Q Q-hat], phi^Q = F^-1[G_Q W] and its CURRENT gradients F^-1[ik G_Q W], F^-1[il G_Q W] (also on UnCoupledModel
+ * and YBJModel, whose tick uses the stale ones of quirk Q1):
+ *   Jq^Q = ik F[u q^Q] + il F[v q^Q]      J^Q = F[u phi^Q_x + v phi^Q_y]      R^Q = i F[phi^Q q_psi]
+ *   NQ_S2S_Q    rows [0] Re(conj P Jq^Q), [1] Re(conj Q-hat Jq^Q)     CoupledModel, UnCoupledModel, QGModel
+ *   NQ_S2S_ADV  row  [2] Re(conj W J^Q)                               CoupledModel, UnCoupledModel, YBJModel
+ *   NQ_S2S_REF  row  [3] Re(conj W R^Q)                               the same three
+ * summed over the wavenumbers of shell b: raw sums, no signs and no 1/M^2, as nq_transfer_binned's rows [0..3], on which the sum
+ * over bands closes when the tables sum to one below shell nx/2 and the state has nothing from that shell on (every J is linear
+ * in the filtered field).  out[band][row][b]; rows that were not selected are zero.  No floating-point atomics and a fixed
+ * summation order: two calls are bit-identical, and a band's rows do not depend on the other bands of the call.  A mask the model
+ * lacks, nbands outside 1..NQ_S2S_MAX_BANDS, a wrong nb, a non-finite entry, a non-zero entry from shell nx/2 on and nx = 8192
+ * (the row kernel of that plan does not fit its 128 registers) are -1 before any launch.  The first call allocates the filtered planes
+ * of ONE band (two copies, spectral and mixed space, of one half-spectrum and two full planes), reused from band to band; counted by nq_device_bytes, freed with the context; an
+ * allocation that fails is -5 and leaves the context as it was.  Reads the state; writes only these buffers, the products'
+ * mixed-space planes (free between steps) and the scratch planes nq_transfer_binned writes.                                   */
+#define NQ_S2S_ROWS 4
+#define NQ_S2S_MAX_BANDS 64
+enum { NQ_S2S_Q = 1, NQ_S2S_ADV = 2, NQ_S2S_REF = 4 };
+int nq_shell_transfer(nq_ctx* ctx, int what_mask, int nbands, const double* g /* nbands x nb */, int nb,
+                      double* out /* nbands x NQ_S2S_ROWS x nb */);
+
 /* copy of one ETDRK4 coefficient plane (0:E 1:Eh 2:Q 3:f0 4:fab 5:fc) of equation eq (0: q, (nx, nx/2+1) complex;
  * 1: phi, (nx, nx) complex; 2: QGModel's passive scalar, (nx, nx/2+1)), without the filter folded in; values as the
  * reference's expch, expch_h, Qh, f0, fab, fc (Kernel.py:417-454, QGModel.py:426-461).                           */

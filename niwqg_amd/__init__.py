@@ -18,3 +18,4 @@ from . import UnCoupledModel   # noqa: F401
 from . import QGModel   # noqa: F401
 from . import YBJModel   # noqa: F401
 from . import coarse   # noqa: F401
+from . import shelltoshell   # noqa: F401

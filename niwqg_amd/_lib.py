@@ -317,6 +317,16 @@ class Context:
                                         _dptr(maps) if nmaps else None), "nq_coarse_flux")
         return mom, maps
 
+    def shell_transfer(self, mask, tables):
+        """raw shell sums (nbands, S2S_ROWS, nb) of the shell-to-shell transfers selected by mask (S2S_*) for the donor-band tables
+        (nbands, nb) (include/niwqg_amd.h: nq_shell_transfer)"""
+        tables = np.ascontiguousarray(tables, np.float64)
+        self._shape(tables, (tables.shape[0], int(self.L.nq_spectrum_shells(self.h))), "shell_transfer")
+        out = np.zeros((tables.shape[0], S2S_ROWS, tables.shape[1]))              # noqa: F821
+        self._chk(self.L.nq_shell_transfer(self.h, int(mask), tables.shape[0], _dptr(tables), tables.shape[1], _dptr(out)),
+                  "nq_shell_transfer")
+        return out
+
     def coeff(self, eq, which):
         n = self.nx
         w = n if eq == 1 else n // 2 + 1

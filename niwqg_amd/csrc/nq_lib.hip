@@ -276,6 +276,13 @@ struct nq_ctx {
     double *g = nullptr, *part = nullptr, *mom = nullptr, *map[3] = {};
     bool ready = false, have_maps = false;
   } cg;
+  // shell-to-shell transfers (nq_shell_transfer): the filtered planes of one band in spectral (s*) and mixed
+  // space (m*), half-spectrum G Q and full {G W, il G W}, the tables and the rows; allocated by the first call, context-owned
+  struct S2s {
+    cd *sq = nullptr, *mq = nullptr, *sf[2] = {}, *mf[2] = {};
+    double *g = nullptr, *out = nullptr;
+    bool ready = false;
+  } ss;
 };
 
 // Device arrays start at staggered offsets inside their allocations.  hipMalloc hands out large blocks at addresses that
@@ -2406,6 +2413,19 @@ __global__ void __launch_bounds__(256) k_stream_copy(const double2* __restrict__
 }
 #include "nq_coarse.hpp"                   // the kernels of nq_coarse_flux (section 5o); after the shell rule above
 static_assert(CG_KE == NQ_CG_KE && CG_ENS == NQ_CG_ENS && CG_NIW == NQ_CG_NIW, "map bits of nq_coarse_flux");
+#include "nq_s2s.hpp"                      // the kernels of nq_shell_transfer (section 5p)
+static_assert(S2S_Q == NQ_S2S_Q && S2S_ADV == NQ_S2S_ADV && S2S_REF == NQ_S2S_REF, "row bits of nq_shell_transfer");
+template <int MODE>
+static void launch_x_band(nq_ctx* c, const BandRows& r) {
+  const int nblocks = xdiag_blocks(c);
+  with_row_size(c->N, [&](auto n) {
+    constexpr int NN = decltype(n)::value;
+    if constexpr (NN < 8192) {                         // refused by nq_shell_transfer: that row plan spills
+      typedef XPlan<NN> X;
+      hipLaunchKernelGGL((k_x_band<NN, MODE>), dim3(nblocks), dim3(X::THREADS), X::LDS_BYTES, c->stream, r, c->twx, c->kk);
+    }
+  });
+}
 
 extern "C" {
 
@@ -5051,6 +5071,29 @@ int nq_slab_transfer_binned(nq_ctx* c, int nb, double* out) {
 // The tick's first products pass again, B-transformed into the scratch planes as the transfer does; then per filter scale
 // k_s_coarse into the context's own spectral planes, the inverse column passes into its own mixed-space planes, k_x_coarse.
 static int coarse_model_mask(const nq_ctx* c) { return !c->kernel_family ? (CG_KE | CG_ENS) : c->ybj ? CG_NIW : (CG_KE | CG_ENS | CG_NIW); }
+// every buffer of `want`, zeroed, owned by the context and counted by nq_device_bytes -- or none of them and -5
+static int alloc_all_or_none(nq_ctx* c, std::vector<std::pair<void**, size_t>>& want, const char* fn) {
+  size_t got = 0, total = 0;
+  for (; got < want.size(); ++got) {
+    if (hipMalloc(want[got].first, want[got].second) != hipSuccess) break;
+    total += want[got].second;
+  }
+  if (got < want.size()) {
+    (void)hipGetLastError();
+    const size_t bytes = want[got].second;
+    for (size_t i = 0; i <= got && i < want.size(); ++i) {
+      if (i < got) (void)hipFree(*want[i].first);
+      *want[i].first = nullptr;
+    }
+    NQ_FAIL(c, -5, "%s: cannot allocate %zu bytes of device memory", fn, bytes);
+  }
+  for (auto& w : want) {
+    HIPCHK(c, hipMemsetAsync(*w.first, 0, w.second, c->stream));
+    c->allocs.push_back(*w.first);
+  }
+  c->bytes += (long long)total;
+  return 0;
+}
 // the planes of the first call (and the map planes of the first call that asks for maps): all of them or none
 static int coarse_reserve(nq_ctx* c, int nb, bool maps) {
   nq_ctx::Coarse& k = c->cg;
@@ -5072,25 +5115,7 @@ static int coarse_reserve(nq_ctx* c, int nb, bool maps) {
   if (maps && !k.have_maps)
     for (int m = 0; m < 3; ++m)
       if (coarse_model_mask(c) & (1 << m)) want.push_back({(void**)&k.map[m], sizeof(double) * N * N});
-  size_t got = 0, total = 0;
-  for (; got < want.size(); ++got) {
-    if (hipMalloc(want[got].first, want[got].second) != hipSuccess) break;
-    total += want[got].second;
-  }
-  if (got < want.size()) {
-    (void)hipGetLastError();
-    const size_t bytes = want[got].second;
-    for (size_t i = 0; i <= got && i < want.size(); ++i) {
-      if (i < got) (void)hipFree(*want[i].first);
-      *want[i].first = nullptr;
-    }
-    NQ_FAIL(c, -5, "nq_coarse_flux: cannot allocate %zu bytes of device memory", bytes);
-  }
-  for (auto& w : want) {
-    HIPCHK(c, hipMemsetAsync(*w.first, 0, w.second, c->stream));
-    c->allocs.push_back(*w.first);
-  }
-  c->bytes += (long long)total;
+  SLABTRY(alloc_all_or_none(c, want, "nq_coarse_flux"));
   k.ready = true;
   if (maps) k.have_maps = true;
   return 0;
@@ -5193,6 +5218,103 @@ int nq_coarse_flux(nq_ctx* c, int what_mask, int nscales, const double* g, int n
         if (what_mask & (1 << m)) HIPCHK(c, hipMemcpyAsync(maps + plane * out_plane++, k.map[m], sizeof(double) * plane, hipMemcpyDeviceToHost, c->stream));
   }
   HIPCHK(c, hipMemcpyAsync(moments, k.mom, sizeof(double) * 6 * (size_t)nscales, hipMemcpyDeviceToHost, c->stream));
+  return nq_sync(c);
+}
+
+// ---- shell-to-shell transfers -----------------------------------------------------------------------------
+// Per donor band: k_s_band into the context's own spectral planes, the inverse column passes into its own mixed-space planes,
+// k_x_band into Muq, Mvq, Mw (once for Jq^Q and J^Q, once for R^Q: the tick's two passes), then the forward column passes and
+// the bins of nq_transfer_binned into the band's rows.  u, v and q_psi come from the last inversion's rows, as in the tick.
+static int s2s_model_mask(const nq_ctx* c) { return !c->kernel_family ? S2S_Q : c->ybj ? (S2S_ADV | S2S_REF) : (S2S_Q | S2S_ADV | S2S_REF); }
+static int s2s_reserve(nq_ctx* c, int nb) {
+  nq_ctx::S2s& k = c->ss;
+  if (k.ready) return 0;
+  const size_t N = (size_t)c->N, half = N * c->Ph * sizeof(cd), full = N * N * sizeof(cd);
+  std::vector<std::pair<void**, size_t>> want;
+  if (!c->ybj) {
+    want.push_back({(void**)&k.sq, half});
+    want.push_back({(void**)&k.mq, half});
+  }
+  for (int i = 0; i < (c->kernel_family ? 2 : 0); ++i) {
+    want.push_back({(void**)&k.sf[i], full});
+    want.push_back({(void**)&k.mf[i], full});
+  }
+  want.push_back({(void**)&k.g, sizeof(double) * NQ_S2S_MAX_BANDS * nb});
+  want.push_back({(void**)&k.out, sizeof(double) * NQ_S2S_MAX_BANDS * NQ_S2S_ROWS * nb});
+  SLABTRY(alloc_all_or_none(c, want, "nq_shell_transfer"));
+  k.ready = true;
+  return 0;
+}
+int nq_shell_transfer(nq_ctx* c, int what_mask, int nbands, const double* g, int nb, double* out) {
+  NQ_SINGLE_RANK(c, "nq_shell_transfer");
+  const int N = c->N, have = s2s_model_mask(c);
+  if (what_mask <= 0 || (what_mask & ~have))
+    NQ_FAIL(c, -1, "nq_shell_transfer: row mask %d; this model has mask %d (NQ_S2S_Q 1, NQ_S2S_ADV 2, NQ_S2S_REF 4)", what_mask, have);
+  if (nbands < 1 || nbands > NQ_S2S_MAX_BANDS) NQ_FAIL(c, -1, "nq_shell_transfer: %d bands; 1 to %d per call", nbands, NQ_S2S_MAX_BANDS);
+  if (!g || !out) NQ_FAIL(c, -1, "nq_shell_transfer: null table or null output");
+  if (nb != nq_shell_count(N)) NQ_FAIL(c, -1, "nq_shell_transfer: nb = %d, the grid has %d shells", nb, nq_shell_count(N));
+  for (int s = 0; s < nbands; ++s)
+    for (int b = 0; b < nb; ++b) {
+      const double x = g[(size_t)s * nb + b];
+      if (!std::isfinite(x)) NQ_FAIL(c, -1, "nq_shell_transfer: table %d is not finite on shell %d", s, b);
+      if (b >= N / 2 && x != 0.0) NQ_FAIL(c, -1, "nq_shell_transfer: table %d is %g on shell %d; every table is zero from shell nx/2 = %d on", s, x, b, N / 2);
+    }
+  if (N >= 8192)
+    NQ_FAIL(c, -1, "nq_shell_transfer: no shell-to-shell transfers at nx = %d: a thread of that row plan has 128 registers and spills even with one row per launch (DESIGN.md section 7)", N);
+  HIPCHK(c, hipSetDevice(c->device));
+  std::vector<nq_ctx*> grp(1, c);
+  SLABTRY(tick_need_phi(grp, "nq_shell_transfer"));
+  SLABTRY(slab_settle(grp));
+  SLABTRY(s2s_reserve(c, nb));
+  nq_ctx::S2s& k = c->ss;
+  const bool waves = c->kernel_family;
+  const bool need_q = (what_mask & S2S_Q) != 0, need_w = (what_mask & (S2S_ADV | S2S_REF)) != 0;
+  const cd* qh = c->q.y[c->q.cur];
+  if (need_q) SLABTRY(mean_qh(c, &qh));                                           // the q-hat the tick bins
+  const size_t rows = (size_t)NQ_S2S_ROWS * nb;
+  HIPCHK(c, hipMemcpyAsync(k.g, g, sizeof(double) * (size_t)nbands * nb, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(k.out, 0, sizeof(double) * (size_t)nbands * rows, c->stream));
+  for (int s = 0; s < nbands; ++s) {
+    BandSpec sp;
+    sp.Q = qh; sp.W = waves ? c->w.y[c->w.cur] : nullptr;
+    sp.gq = k.sq; sp.gw = k.sf[0]; sp.wy = k.sf[1];
+    sp.g = k.g + (size_t)s * nb; sp.ll = c->ll; sp.N = N; sp.ph = c->Ph; sp.what = what_mask;
+    const int cols = need_w ? N : N / 2 + 1;
+    hipLaunchKernelGGL(k_s_band, dim3((cols + 255) / 256, N), dim3(256), 0, c->stream, sp);
+    if (need_q) coarse_columns_inverse(c, &k.sq, &k.mq, 1, true);
+    if (need_w) coarse_columns_inverse(c, k.sf, k.mf, (what_mask & S2S_ADV) ? 2 : 1, false);
+    BandRows r;
+    r.mU = c->mU; r.mP = c->mP; r.mQ = c->mQ; r.mQw = c->mQw;
+    r.gq = coarse_rows_of(k.mq, c->Ph);
+    r.gw = k.mf[0]; r.wy = k.mf[1];
+    r.oUq = c->mUq; r.oVq = c->mVq; r.oW = c->mW;
+    r.v_zero_nyq = waves ? 1 : 0;
+    double* d = k.out + (size_t)s * rows;
+    for (int which = 0; which < 2; ++which) {          // 0: Jq^Q and J^Q, 1: R^Q -- Mw holds one of the two wave planes at a time
+      r.what = what_mask & (which == 0 ? (S2S_Q | S2S_ADV) : S2S_REF);
+      if (!r.what) continue;
+      if (c->p.model == NQ_MODEL_COUPLED) launch_x_band<MODE_COUPLED>(c, r);
+      else if (c->p.model == NQ_MODEL_UNCOUPLED) launch_x_band<MODE_UNCOUPLED>(c, r);
+      else launch_x_band<MODE_QG>(c, r);
+      const bool bq = (r.what & S2S_Q) != 0, bw = (r.what & (S2S_ADV | S2S_REF)) != 0;
+      if (bq && bw) launch_A_m(c, false, {&c->mUq, &c->mVq, &c->mW});
+      else if (bq) launch_A_m(c, false, {&c->mUq, &c->mVq});
+      else launch_A_m(c, false, {&c->mW});
+      if (bq) {
+        launch_B_p(c, false, c->mUq.ys, c->mUq.pitch, c->scr_h0, c->Ph, c->Wh, 1.0);
+        launch_B_p(c, false, c->mVq.ys, c->mVq.pitch, c->scr_h1, c->Ph, c->Wh, 1.0);
+        const BinTrQ t{HalfJac{c->scr_h0, c->scr_h1, N, c->Ph, c->kk, c->ll}, (const cd*)c->ph, qh};
+        hipLaunchKernelGGL(k_bin_shells<BinTrQ>, dim3(nb), dim3(256), 0, c->stream, t, N, nb, 0, c->kh0, c->Wh, d);
+      }
+      if (bw) {
+        launch_B_p(c, false, c->mW.ys, c->mW.pitch, c->scr_f0, c->Wf, c->Wf, 1.0);
+        const BinTrW t{(const cd*)c->w.y[c->w.cur], c->scr_f0, c->Wf};
+        hipLaunchKernelGGL(k_bin_shells<BinTrW>, dim3(nb), dim3(256), 0, c->stream, t, N, nb, 1, c->kf0, c->Wf, d + (size_t)(2 + which) * nb);
+      }
+    }
+    HIPCHK(c, hipGetLastError());
+  }
+  HIPCHK(c, hipMemcpyAsync(out, k.out, sizeof(double) * (size_t)nbands * rows, hipMemcpyDeviceToHost, c->stream));
   return nq_sync(c);
 }
 
