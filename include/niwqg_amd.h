@@ -439,6 +439,34 @@ enum { NQ_S2S_Q = 1, NQ_S2S_ADV = 2, NQ_S2S_REF = 4 };
 int nq_shell_transfer(nq_ctx* ctx, int what_mask, int nbands, const double* g /* nbands x nb */, int nb,
                       double* out /* nbands x NQ_S2S_ROWS x nb */);
 
+/* Isotropic co-spectra of the physical fields, formed on the device, single-rank fused contexts only (slab
+ * contexts: -4).  fields: 1 to NQ_COSPEC_MAX_FIELDS different ids out of those nq_field_hist takes for the model (Kernel family:
+ * NQ_PDF_Q, NQ_PDF_QPSI, NQ_PDF_PHI2 and the NQ_FLOW_* fields; QGModel: NQ_PDF_Q and, with its passive scalar, NQ_PDF_C), with
+ * the values nq_field_hist bins: the rows of the last inversion (dual_q contexts: the mean of the two q-hat copies), the CURRENT
+ * phi-hat for NQ_FLOW_GRADPHI2.  With F the unnormalised full-plane transform and A_i = F[field i], row i < 3 is
+ * sum |A_i|^2 and rows 3, 4, 5 are sum Re(conj A_i A_j) of the pairs (0,1), (0,2), (1,2), each over the wavenumbers of shell b
+ * (shell rule of nq_diagnostics_binned; every shell is kept): raw sums, no 1 / M^2; rows of fields the list does not have are
+ * zero.  The quadrature part Im(conj A_i A_j) sums to zero over +-k for real fields and is not formed.  Summed over the shells,
+ * row (i,j) / M^2 is the plane mean of field i times field j; shell 0 holds the product of the two means.
+ * accumulate = 0 zeroes the running sums before this call's rows are added to them, accumulate = 1 adds (the same list as the
+ * call that zeroed them, else -1); out: NULL (nothing is downloaded and the host does not wait) or NQ_COSPEC_ROWS x nb doubles,
+ * the rows of THIS call.  nq_cospectra_read: the calls in the running sums and the sums (NQ_COSPEC_ROWS x nb; -1 before the first
+ * call).  No floating-point atomics and a fixed summation order: two calls are bit-identical.  A null or bad list, a field twice
+ * or one the model lacks, a wrong nb, and a list with an NQ_FLOW_* field at nx = 8192 (a thread of that row plan holds one value,
+ * a packed pair needs two) are -1 before any launch.  The Kernel family runs the range pass of nq_field_minmax first and scales
+ * every field by a power of two before the transforms (exact, taken out again in the bins; nothing of it reaches the host), so
+ * fields of very different magnitudes do not share one transform's rounding.  The first call allocates the two tables
+ * (2 x NQ_COSPEC_ROWS x nb doubles) and, in the Kernel family, the range pass's partials (6 x 8192 doubles) and six scales,
+ * counted by nq_device_bytes, freed with the context; an allocation that fails is -5 and leaves the context as it was.  Reads the
+ * state; writes only these tables, the products' mixed-space planes (free between steps) and the scratch planes
+ * nq_transfer_binned writes.                                                                                                  */
+#define NQ_COSPEC_MAX_FIELDS 3
+#define NQ_COSPEC_ROWS 6           /* autos of the list in order, then pairs (0,1), (0,2), (1,2) */
+int nq_cospectra(nq_ctx* ctx, int nfields, const int* fields /* NQ_PDF_*, NQ_FLOW_* */, int nb,
+                 int accumulate /* 0: zero the device tables first, 1: add; needs the same list */,
+                 double* out /* NULL, or rows x nb RAW sums of this call (no 1/M^2) */);
+int nq_cospectra_read(nq_ctx* ctx, long long* samples, double* out /* rows x nb running sums */);
+
 /* copy of one ETDRK4 coefficient plane (0:E 1:Eh 2:Q 3:f0 4:fab 5:fc) of equation eq (0: q, (nx, nx/2+1) complex;
  * 1: phi, (nx, nx) complex; 2: QGModel's passive scalar, (nx, nx/2+1)), without the filter folded in; values as the
  * reference's expch, expch_h, Qh, f0, fab, fc (Kernel.py:417-454, QGModel.py:426-461).                           */

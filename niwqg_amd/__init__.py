@@ -19,3 +19,4 @@ from . import QGModel   # noqa: F401
 from . import YBJModel   # noqa: F401
 from . import coarse   # noqa: F401
 from . import shelltoshell   # noqa: F401
+from . import cospectra   # noqa: F401

@@ -327,6 +327,22 @@ class Context:
                   "nq_shell_transfer")
         return out
 
+    def cospectra(self, codes, accumulate=False, download=True):
+        """raw co-spectrum shell sums (COSPEC_ROWS, nb) of the listed fields (PDF_*, FLOW_*), added to the running sums on the
+        device; download=False: nothing comes back and the host does not wait (include/niwqg_amd.h: nq_cospectra)"""
+        nb = int(self.L.nq_spectrum_shells(self.h))
+        c = (ctypes.c_int * max(1, len(codes)))(*codes)
+        out = np.zeros((COSPEC_ROWS, nb)) if download else None                   # noqa: F821
+        self._chk(self.L.nq_cospectra(self.h, len(codes), c, nb, int(bool(accumulate)), _dptr(out) if download else None), "nq_cospectra")
+        return out
+
+    def cospectra_read(self):
+        """(calls in the running sums, the sums (COSPEC_ROWS, nb)) (include/niwqg_amd.h: nq_cospectra_read)"""
+        n = ctypes.c_longlong()
+        out = np.zeros((COSPEC_ROWS, int(self.L.nq_spectrum_shells(self.h))))     # noqa: F821
+        self._chk(self.L.nq_cospectra_read(self.h, ctypes.byref(n), _dptr(out)), "nq_cospectra_read")
+        return int(n.value), out
+
     def coeff(self, eq, which):
         n = self.nx
         w = n if eq == 1 else n // 2 + 1

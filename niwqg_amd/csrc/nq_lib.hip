@@ -283,6 +283,14 @@ struct nq_ctx {
     double *g = nullptr, *out = nullptr;
     bool ready = false;
   } ss;
+  // co-spectra of the physical fields (nq_cospectra): this call's rows, the running sums, the list the sums
+  // were started with and the calls in them; allocated by the first call, context-owned
+  struct Cospec {
+    double *cur = nullptr, *sum = nullptr;
+    double *part = nullptr, *scl = nullptr;     // Kernel family: workgroup partials of the range pass, the scales of the call
+    int nf = 0, fields[3] = {0, 0, 0};
+    long long samples = 0;
+  } cs;
 };
 
 // Device arrays start at staggered offsets inside their allocations.  hipMalloc hands out large blocks at addresses that
@@ -2423,6 +2431,21 @@ static void launch_x_band(nq_ctx* c, const BandRows& r) {
     if constexpr (NN < 8192) {                         // refused by nq_shell_transfer: that row plan spills
       typedef XPlan<NN> X;
       hipLaunchKernelGGL((k_x_band<NN, MODE>), dim3(nblocks), dim3(X::THREADS), X::LDS_BYTES, c->stream, r, c->twx, c->kk);
+    }
+  });
+}
+
+#include "nq_cospec.hpp"                   // the kernels of nq_cospectra (section 5q)
+static_assert(COSPEC_FIELDS == NQ_COSPEC_MAX_FIELDS && COSPEC_ROWS == NQ_COSPEC_ROWS, "rows of nq_cospectra");
+template <int MODE, bool FLOW>
+static void launch_x_cross(nq_ctx* c, const FlowSel& sel, const double* scl, const MArr& oAB, const MArr& oC) {
+  const int nblocks = xdiag_blocks(c);
+  with_row_size(c->N, [&](auto n) {
+    constexpr int NN = decltype(n)::value;
+    if constexpr (!FLOW || flow_nv<NN>() == COSPEC_FIELDS) {      // refused by nq_cospectra: one value per thread
+      typedef XPlan<NN> X;
+      hipLaunchKernelGGL((k_x_cross<NN, MODE, false, FLOW>), dim3(nblocks), dim3(X::THREADS), X::LDS_BYTES, c->stream, c->mQ, c->mQw, c->mU,
+                         c->mP, c->mPhi, c->mPhiy, c->twx, c->kk, sel, scl, oAB, oC);
     }
   });
 }
@@ -5315,6 +5338,97 @@ int nq_shell_transfer(nq_ctx* c, int what_mask, int nbands, const double* g, int
     HIPCHK(c, hipGetLastError());
   }
   HIPCHK(c, hipMemcpyAsync(out, k.out, sizeof(double) * (size_t)nbands * rows, hipMemcpyDeviceToHost, c->stream));
+  return nq_sync(c);
+}
+
+// ---- isotropic co-spectra of the physical fields -----------------------------------------------------------
+// Kernel family: k_x_cross packs the row values of the list (what nq_field_hist bins) as a + i b and c + i 0 and transforms them
+// forward into Mw and scr_f1; the column passes finish the first plane in scr_f0 and the third field's in Mw, BinCross bins them.
+// QGModel: q-hat and c-hat are the state and BinQC bins them as they are.
+static int cospec_reserve(nq_ctx* c, int nb) {
+  if (c->cs.cur) return 0;
+  std::vector<std::pair<void**, size_t>> want;
+  want.push_back({(void**)&c->cs.cur, sizeof(double) * NQ_COSPEC_ROWS * nb});
+  want.push_back({(void**)&c->cs.sum, sizeof(double) * NQ_COSPEC_ROWS * nb});
+  if (c->kernel_family) {                               // the range pass's workgroup partials and the scales formed from them
+    want.push_back({(void**)&c->cs.part, sizeof(double) * 6 * HIST_PART_BLOCKS});
+    want.push_back({(void**)&c->cs.scl, sizeof(double) * 2 * NQ_COSPEC_MAX_FIELDS});
+  }
+  return alloc_all_or_none(c, want, "nq_cospectra");
+}
+int nq_cospectra(nq_ctx* c, int nfields, const int* fields, int nb, int accumulate, double* out) {
+  NQ_SINGLE_RANK(c, "nq_cospectra");
+  {
+    const int rc = hist_check_fields(c, "nq_cospectra", nfields, fields);
+    if (rc) return rc;
+  }
+  const int N = c->N;
+  if (nb != nq_shell_count(N)) NQ_FAIL(c, -1, "nq_cospectra: nb = %d, the grid has %d shells", nb, nq_shell_count(N));
+  const bool flow = any_flow(nfields, fields);
+  if (flow && flow_nv_of(c) < NQ_COSPEC_MAX_FIELDS)
+    NQ_FAIL(c, -1, "nq_cospectra: flow fields (NQ_FLOW_*) at nx = %d: a thread of that row plan holds one value, a packed pair needs two (DESIGN.md section 7)", N);
+  nq_ctx::Cospec& k = c->cs;
+  if (accumulate) {
+    bool same = k.cur && k.samples > 0 && k.nf == nfields;
+    for (int i = 0; same && i < nfields; ++i) same = k.fields[i] == fields[i];
+    if (!same) NQ_FAIL(c, -1, "nq_cospectra: accumulate = 1 needs the field list of the call that zeroed the tables");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  SLABTRY(cospec_reserve(c, nb));
+  const size_t count = (size_t)NQ_COSPEC_ROWS * nb;
+  if (c->kernel_family) {
+    FlowSel sel = flow_sel_none(c);
+    for (int i = 0; i < nfields; ++i) sel.code[i] = fields[i];
+    // the third field's rows go to scr_f1 (Muq and Mvq are no home for a full row: k_x_products keeps the Jacobian's passenger sums
+    // in their padding column Muq.W, zero on the rows it does not write, and k_s_phi adds all of them up)
+    const MArr oC = coarse_rows_of(c->scr_f1, N);
+    const bool third = nfields == NQ_COSPEC_MAX_FIELDS, coupled = c->p.model == NQ_MODEL_COUPLED;
+    // the PDFs' range pass (the old names' kernel has fixed slots q, q_psi, phi2; the flow kernel's slot i is field i), then the
+    // scales: all on the device
+    CrossSlots sl = {{-1, -1, -1}};
+    for (int i = 0; i < nfields; ++i) sl.slot[i] = flow ? i : hist_slot(c, fields[i]);
+    const HistArgs none = {};
+    if (flow) flow_hist(c, true, nfields, fields, none, k.part);
+    else launch_xhist<true>(c, none, k.part);
+    hipLaunchKernelGGL(k_cospec_scale, dim3(1), dim3(256), 0, c->stream, (const double*)k.part, xdiag_blocks(c), 6, sl, k.scl);
+    if (flow) {
+      if (coupled) launch_x_cross<MODE_COUPLED, true>(c, sel, k.scl, c->mW, oC);
+      else launch_x_cross<MODE_UNCOUPLED, true>(c, sel, k.scl, c->mW, oC);
+    } else {
+      if (coupled) launch_x_cross<MODE_COUPLED, false>(c, sel, k.scl, c->mW, oC);
+      else launch_x_cross<MODE_UNCOUPLED, false>(c, sel, k.scl, c->mW, oC);
+    }
+    launch_A_m(c, false, {&c->mW});
+    if (third) launch_A(c, false, {c->scr_f1}, false);
+    launch_B_p(c, false, c->mW.ys, c->mW.pitch, c->scr_f0, N, N, 1.0);
+    if (third) launch_B_p(c, false, c->scr_f1, N, c->mW.ys, c->mW.pitch, N, 1.0);       // Mw is free again: the third plane ends there
+    const BinCross t{(const cd*)c->scr_f0, (const cd*)(third ? c->mW.ys : nullptr), (const double*)k.scl, N, c->mW.pitch, nfields == 1};
+    hipLaunchKernelGGL(k_bin_shells<BinCross>, dim3(nb), dim3(256), 0, c->stream, t, N, nb, 1, 0, N, k.cur);
+  } else {
+    BinQC t{{nullptr, nullptr, nullptr}, N, c->Ph};
+    for (int i = 0; i < nfields; ++i) t.f[i] = fields[i] == NQ_PDF_Q ? c->q.y[c->q.cur] : c->cq.y[c->cq.cur];
+    hipLaunchKernelGGL(k_bin_shells<BinQC>, dim3(nb), dim3(256), 0, c->stream, t, N, nb, 0, 0, c->Wh, k.cur);
+  }
+  if (!accumulate) HIPCHK(c, hipMemsetAsync(k.sum, 0, sizeof(double) * count, c->stream));
+  hipLaunchKernelGGL(k_cospec_add, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, c->stream, (const double*)k.cur, k.sum, (int)count);
+  HIPCHK(c, hipGetLastError());
+  if (!accumulate) {
+    k.nf = nfields;
+    for (int i = 0; i < nfields; ++i) k.fields[i] = fields[i];
+    k.samples = 0;
+  }
+  ++k.samples;
+  if (!out) return 0;
+  HIPCHK(c, hipMemcpyAsync(out, k.cur, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
+  return nq_sync(c);
+}
+int nq_cospectra_read(nq_ctx* c, long long* samples, double* out) {
+  NQ_SINGLE_RANK(c, "nq_cospectra_read");
+  if (!samples || !out) NQ_FAIL(c, -1, "nq_cospectra_read: null output");
+  if (!c->cs.cur || c->cs.samples == 0) NQ_FAIL(c, -1, "nq_cospectra_read: no nq_cospectra call yet");
+  HIPCHK(c, hipSetDevice(c->device));
+  *samples = c->cs.samples;
+  HIPCHK(c, hipMemcpyAsync(out, c->cs.sum, sizeof(double) * NQ_COSPEC_ROWS * nq_shell_count(c->N), hipMemcpyDeviceToHost, c->stream));
   return nq_sync(c);
 }
 

@@ -1,0 +1,208 @@
+"""CPU-only checks of the co-spectra module (niwqg_amd/cospectra.py): the numpy restatement against a direct double loop, the
+validation of names and pairs, the arithmetic of coherence / covariance / correlation with the NaN rule, the packed route
+(A, B from F[a + i b]) against the separate transforms, and the binding of the two entry points."""
+import ctypes
+
+import numpy as np
+import pytest
+
+
+def fields(nx, seed=0):
+    """the kind of state the GPU tests use (tests/test_gpu_flow.py: make): broadband plus a white part, so the Nyquist row and
+    column and the outer partial shells carry energy -> a q-like field, |phi|^2 and a second real field"""
+    rng = np.random.default_rng(seed + nx)
+    n = np.append(np.arange(0, nx // 2), np.arange(-(nx // 2), 0))
+    kap = np.sqrt(n[None, :] ** 2.0 + n[:, None] ** 2.0)
+    w = np.exp(-(kap / 8.0) ** 2) + 0.05
+
+    def noise(cplx):
+        z = rng.standard_normal((nx, nx)) + (1j * rng.standard_normal((nx, nx)) if cplx else 0)
+        z = np.fft.ifft2(np.fft.fft2(z) * w)
+        z = z if cplx else z.real
+        return z - z.mean()
+    q = noise(False)
+    q = 1e-5 * q / q.std()
+    p = noise(True)
+    phi = 0.2 * (1 + 0.5j) / np.sqrt(2) + 0.05 * p / np.abs(p).std()
+    r = noise(False)
+    return q, np.abs(phi) ** 2, 3.0 + r / r.std()
+
+
+def double_loop(planes, nx):
+    """sum over every wavenumber, one at a time, into the shell of the nearest integer radius"""
+    from niwqg_amd.spectra import shell_count
+    T = [np.fft.fft2(p) for p in planes]
+    out = np.zeros((6, shell_count(nx)))
+    for l in range(nx):
+        j = l if l < nx // 2 else l - nx
+        for k in range(nx):
+            i = k if k < nx // 2 else k - nx
+            r = np.hypot(i, j)
+            s = int(np.floor(r + 0.5))
+            assert abs(r - np.floor(r) - 0.5) > 1e-9
+            for a in range(len(T)):
+                out[a, s] += abs(T[a][l, k]) ** 2
+            for row, (a, b) in enumerate(((0, 1), (0, 2), (1, 2))):
+                if b < len(T):
+                    out[3 + row, s] += (np.conj(T[a][l, k]) * T[b][l, k]).real
+    return out
+
+
+@pytest.mark.parametrize("nx", [8, 16])
+def test_reference_equals_a_direct_double_loop(nx):
+    from niwqg_amd import cospectra
+    a, b, c = fields(nx)
+    for planes in ({"a": a, "b": b, "c": c}, {"a": a, "b": b}, {"c": c}):
+        R = cospectra.reference(planes, nx)
+        want = double_loop(list(planes.values()), nx)
+        scale = np.abs(want).max()
+        assert R.raw.shape == want.shape and np.abs(R.raw - want).max() <= 1e-13 * scale
+        names = list(planes)
+        M2 = float(nx) ** 4
+        for i, n in enumerate(names):
+            assert np.array_equal(R.auto[n], R.raw[i] / M2)
+        assert set(R.co) == {(x, y) for x in names for y in names if x != y}
+        if len(names) == 3:
+            assert np.array_equal(R.co[("a", "c")], R.raw[4] / M2) and np.array_equal(R.co[("c", "b")], R.raw[5] / M2)
+        # Parseval: the shells sum to the plane mean of the product, shell 0 is the product of the means
+        for x in names:
+            for y in names:
+                co = R.auto[x] if x == y else R.co[(x, y)]
+                px, py = planes[x], planes[y]
+                assert abs(co.sum() - (px * py).mean()) <= 1e-13 * np.sqrt((px * px).mean() * (py * py).mean())
+                assert abs(co[0] - px.mean() * py.mean()) <= 1e-13 * np.sqrt((px * px).mean() * (py * py).mean())
+    assert np.array_equal(R.shell, np.arange(len(R.shell))) and R.modes.sum() == nx * nx and R.k_iso_max == 0.5 * nx
+
+
+def test_names_and_pairs_are_validated():
+    from niwqg_amd import cospectra, flow
+    valid = ["q", "q_psi", "phi2"] + list(flow.NAMES)
+    assert cospectra.check(valid, "q") == ("q",)
+    assert cospectra.check(valid, ("q_psi", "ow", "gradphi2")) == ("q_psi", "ow", "gradphi2")
+    with pytest.raises(ValueError, match="valid names: q, q_psi, phi2, u"):
+        cospectra.check(valid, ("q", "zeta"))
+    with pytest.raises(ValueError, match="valid names"):
+        cospectra.check(valid, ())
+    with pytest.raises(ValueError, match="every name once"):
+        cospectra.check(valid, ("q", "ow", "q"))
+    with pytest.raises(ValueError, match="4 names"):
+        cospectra.check(valid, ("q", "q_psi", "phi2", "ow"))
+    with pytest.raises(ValueError, match="valid names: q, c"):
+        cospectra.check(["q", "c"], ("q", "u"))
+
+    import niwqg_amd.QGModel as Q
+    fake = Q.Model.__new__(Q.Model)
+    fake.passive_scalar = False
+    assert cospectra.available(fake) == ["q"]
+    fake.passive_scalar = True
+    assert cospectra.available(fake) == ["q", "c"]
+    with pytest.raises(ValueError, match="valid names: q, c"):
+        cospectra.cross_spectra(fake, ("q", "ow"))
+
+    class Kernel(object):
+        pass
+    assert cospectra.available(Kernel()) == valid
+
+    nx = 8
+    a, b, c = fields(nx)
+    R = cospectra.reference({"a": a, "b": b}, nx)
+    assert np.array_equal(R.co[("a", "b")], R.co[("b", "a")]) and np.array_equal(R.coherence("a", "b"), R.coherence("b", "a"))
+    with pytest.raises(KeyError):
+        R.coherence("a", "c")
+    with pytest.raises(ValueError, match="every name once|valid"):
+        cospectra.reference({}, nx)
+
+
+def test_coherence_covariance_correlation_arithmetic():
+    from niwqg_amd import cospectra
+    from niwqg_amd.spectra import shell_count
+    nx = 4
+    nb = shell_count(nx)
+    assert nb == 4
+    M2 = float(nx) ** 4
+    raw = np.zeros((6, nb))
+    raw[0] = [4.0, 9.0, 0.0, 16.0]                # auto a
+    raw[1] = [1.0, 4.0, 25.0, 0.0]                # auto b
+    raw[3] = [-2.0, 3.0, 0.0, 0.0]                # co (a, b)
+    R = cospectra.CrossSpectra(("a", "b"), raw * M2, 2.0, nx)
+    assert np.array_equal(R.auto["a"], raw[0]) and np.array_equal(R.co[("b", "a")], raw[3]) and np.array_equal(R.k, 2.0 * np.arange(nb))
+    coh = R.coherence("a", "b")
+    assert coh[0] == -1.0 and coh[1] == 0.5 and np.isnan(coh[2]) and np.isnan(coh[3])       # NaN where a denominator is 0
+    one = R.coherence("a", "a")
+    assert one[0] == 1.0 and one[1] == 1.0 and np.isnan(one[2]) and one[3] == 1.0
+    assert R.covariance("a", "b") == 3.0 and R.covariance("a", "a") == 25.0 and R.covariance("b", "b") == 29.0
+    assert R.correlation("a", "b") == 3.0 / np.sqrt(25.0 * 29.0)
+    # the mean over n states: the raw sums divided by n M^2
+    R3 = cospectra.CrossSpectra(("a", "b"), 3.0 * raw * M2, 2.0, nx, n=3)
+    assert R3.n == 3 and np.allclose(R3.auto["a"], raw[0], rtol=1e-15) and np.array_equal(R3.raw, 3.0 * raw * M2)
+    flat = cospectra.CrossSpectra(("a", "b"), np.zeros((6, nb)), 1.0, nx)
+    assert np.isnan(flat.correlation("a", "b")) and np.isnan(flat.coherence("a", "b")).all()
+    with pytest.raises(ValueError, match="shape"):
+        cospectra.CrossSpectra(("a",), np.zeros((6, nb + 1)), 1.0, nx)
+
+
+@pytest.mark.parametrize("nx", [64, 128, 512, 1024])
+def test_packed_route_equals_the_separate_transforms(nx):
+    """A, B from ONE transform of the scaled a + i b (the device's route) against F[a], F[b]: per shell within
+    1e-12 sum_shell |A||B| (the bar of the GPU tests), for fields five orders of magnitude apart"""
+    from niwqg_amd import cospectra
+    q, phi2, r = fields(nx)
+    assert cospectra.pack_scale(q) * np.abs(q).max() >= 1.0 and cospectra.pack_scale(q) * np.abs(q).max() < 2.0
+    assert np.frexp(cospectra.pack_scale(q))[0] == 0.5 and cospectra.pack_scale(0 * q) == 1.0 and cospectra.pack_scale(q + np.inf) == 1.0
+    assert cospectra.pack_scale(np.full((4, 4), 1e-310)) == 1.0 and np.isfinite(cospectra.pack_scale(np.full((4, 4), 2.3e-308)))      # subnormal: unscaled
+    for a, b in ((q, phi2), (phi2, r), (q, r)):
+        A, B = np.fft.fft2(a), np.fft.fft2(b)
+        Ap, Bp = cospectra.packed_transforms(a, b)
+        want, got = cospectra.table([A, B], nx), cospectra.table([Ap, Bp], nx)
+        absA, absB = np.abs(A), np.abs(B)
+        bars = {0: cospectra.bin_shells(absA * absA, nx), 1: cospectra.bin_shells(absB * absB, nx), 3: cospectra.bin_shells(absA * absB, nx)}
+        worst = 0.0
+        for row, bar in bars.items():
+            assert (bar > 0).all()
+            ratio = np.abs(got[row] - want[row]) / bar
+            worst = max(worst, float(ratio.max()))
+            assert (ratio <= 1e-12).all(), (nx, row, float(ratio.max()))
+        print("%d: packed against separate, worst shell %.3g of the scale" % (nx, worst))
+    # for the record, not asserted: the same pair (five orders of magnitude apart) packed WITHOUT the scales
+    raw = cospectra.table(list(cospectra.split_packed(np.fft.fft2(q + 1j * r))), nx)
+    print("%d: unscaled, auto row of the smaller field: worst shell %.3g of the scale"
+          % (nx, float((np.abs(raw[0] - cospectra.table([np.fft.fft2(q)], nx)[0]) / cospectra.bin_shells(np.abs(np.fft.fft2(q)) ** 2, nx)).max())))
+
+
+def test_entry_points_are_exported_and_typed():
+    import niwqg_amd
+    niwqg_amd.build()
+    from niwqg_amd import _lib
+    L = _lib.lib()
+    assert _lib.COSPEC_MAX_FIELDS == 3 and _lib.COSPEC_ROWS == 6
+    for name in ("nq_cospectra", "nq_cospectra_read"):
+        assert name in _lib.EXPORTS and getattr(L, name).argtypes is not None, name
+    assert L.nq_cospectra.argtypes[0] is ctypes.c_void_p and len(L.nq_cospectra.argtypes) == 6
+    assert L.nq_cospectra(None, 1, (ctypes.c_int * 1)(0), 46, 0, None) == -1
+    n = ctypes.c_longlong()
+    assert L.nq_cospectra_read(None, ctypes.byref(n), None) == -1
+
+
+@pytest.mark.parametrize("nx", [64, 256])
+def test_transform_rounding_bounds_numpys_own_two_orders(nx):
+    """The GPU tests hold the issue's bar, 1e-12 of a shell's content, on every resolved shell and add ``transform_rounding`` on the
+    others.  Here: (1) on broadband-plus-white fields that bound is a few per cent of the issue's bar on every shell but shell 0 of
+    the mean-free field, so all of them count as resolved; (2) on a field with a steep spectrum two orders of numpy's OWN
+    transform (fft2 of the plane, of its transpose) leave the issue's bar on the weak shells and stay inside the bound."""
+    from niwqg_amd import cospectra
+    q, phi2, r = fields(nx)
+    M2 = float(nx) ** 4
+    for a, b, mean_free in ((q, q, True), (q, phi2, True), (phi2, phi2, False), (phi2, r, False)):
+        A, B = np.fft.fft2(a), np.fft.fft2(b)
+        ratio = cospectra.transform_rounding(A, B, a, b, nx) / (1e-12 * cospectra.bin_shells(np.abs(A) * np.abs(B), nx) / M2)
+        assert (ratio[1:] <= 0.05).all(), float(ratio[1:].max())
+        assert (ratio[0] > 1.0) == mean_free
+    n = np.append(np.arange(0, nx // 2), np.arange(-(nx // 2), 0))
+    steep = np.fft.ifft2(np.fft.fft2(q) * np.exp(-(np.hypot(n[None, :], n[:, None]) / 6.0) ** 2)).real
+    A1, A2 = np.fft.fft2(steep), np.fft.fft2(steep.T).T
+    s1, s2 = cospectra.bin_shells(np.abs(A1) ** 2, nx) / M2, cospectra.bin_shells(np.abs(A2) ** 2, nx) / M2
+    bound = cospectra.transform_rounding(A1, A1, steep, steep, nx)
+    beyond = np.abs(s1 - s2) > 1e-12 * s1
+    print("%d: numpy against numpy, %d of %d shells beyond 1e-12 of their content, worst %.3g of the bound"
+          % (nx, beyond.sum(), len(s1), float((np.abs(s1 - s2) / bound).max())))
+    assert beyond.sum() > len(s1) // 4 and (np.abs(s1 - s2) <= bound).all()
