@@ -35,7 +35,9 @@ row a + i b (and c + i 0 for a third field), transforms forward, and the column 
 Z = F[a + i b] into A = (Z + Z*) / 2, B = (Z - Z*) / (2i), Z* = conj Z(-l, -k) (``split_packed`` restates it).  Before packing,
 every field is multiplied by the power of two that brings its largest |value| into [1, 2) (from the PDFs' range pass, on the
 device), and the bins take the powers out again, both exactly: q_psi (1e-5 1/s) and |phi|^2 or ow (1e-11 1/s^2) would otherwise
-share one transform's rounding and the smaller would lose digits (``packed_transforms`` restates the route).  No physical plane
+share one transform's rounding and the smaller would lose digits (``packed_transforms`` restates the route).  A field that is zero
+everywhere is taken out with the factor 0 instead (``unpack_scale``): its ``auto`` and every ``co`` row it is in are exactly 0.0 and
+its coherence is NaN, not the round-off of its partner's transform.  No physical plane
 is written or downloaded; one (6, nb) table leaves the GPU.  QGModel on the fused grids bins its state q-hat, c-hat directly.  Two
 calls are bit-identical (no atomics, fixed summation order).
 
@@ -46,6 +48,8 @@ Accumulator's ``add``) on the same model in between takes them over and the next
 Slab-decomposed models raise ``NotImplementedError``, and so does a list with a flow name at nx = 8192 (a device thread of that row
 plan holds one value).  ``q``, ``q_psi``, ``phi2`` work there.
 """
+import functools
+
 import numpy as np
 
 from . import _lib, flow, pdfs
@@ -75,10 +79,14 @@ def check(valid, names):
     return tuple(names)
 
 
+@functools.lru_cache(maxsize=2)
 def shell_map(nx):
-    """(nx, nx) int64: the shell of every wavenumber of the full plane in numpy.fft's layout"""
+    """(nx, nx) int64, read-only: the shell of every wavenumber of the full plane in numpy.fft's layout (kept for the last two
+    sizes: a reference table bins a dozen planes of one size)"""
     n = np.append(np.arange(0, nx // 2), np.arange(-(nx // 2), 0))
-    return shell_of(n[None, :], n[:, None])
+    out = shell_of(n[None, :], n[:, None])
+    out.setflags(write=False)
+    return out
 
 
 def bin_shells(term, nx):
@@ -127,10 +135,17 @@ def transform_rounding(A, B, a, b, nx, growth=None, packed=False):
     packed: the bound for the device's packed route instead, where a field shares its transform with a partner and the plane the
     transform sees has the size of the PEAKS (rms(x) is replaced by 2 sqrt 2 max |x|)."""
     M = float(A.size)
-    eps = (np.log2(M) if growth is None else float(growth)) * 2.0 ** -53 / np.sqrt(M)
-    n = shell_modes(nx).astype(np.float64)
     Sa = bin_shells(A.real * A.real + A.imag * A.imag, nx) / M ** 2
     Sb = bin_shells(B.real * B.real + B.imag * B.imag, nx) / M ** 2
+    return shell_sum_rounding(Sa, Sb, a, b, nx, growth, packed)
+
+
+def shell_sum_rounding(Sa, Sb, a, b, nx, growth=None, packed=False):
+    """``transform_rounding`` from the shell sums S_x = sum_shell |X|^2 / M^2 themselves (a square grid): for a caller that has
+    them from a route without a transform of its own, such as 2 x the enstrophy spectrum for q"""
+    M = float(nx) ** 2
+    eps = (np.log2(M) if growth is None else float(growth)) * 2.0 ** -53 / np.sqrt(M)
+    n = shell_modes(nx).astype(np.float64)
     ra, rb = float(np.sqrt(np.mean(np.asarray(a, np.float64) ** 2))), float(np.sqrt(np.mean(np.asarray(b, np.float64) ** 2)))
     if packed:      # the device's packed route: a transform of s_a a + i s_b b, both peaks in [1, 2): |Z| <= 2 sqrt 2, so a / s_a sees 2 sqrt 2 max |a|
         ra, rb = 2.0 * np.sqrt(2.0) * float(np.abs(a).max()), 2.0 * np.sqrt(2.0) * float(np.abs(b).max())
@@ -146,13 +161,27 @@ def pack_scale(x):
     return float(np.ldexp(1.0, 1 - np.frexp(top)[1]))
 
 
+def unpack_scale(x):
+    """the factor the bins take a field's split part out with: 1 / pack_scale(x), exactly, and 0 for a field that is zero
+    everywhere: packed with a partner, the split part of a vanishing field is the round-off of the PARTNER's transform (1e-16 of
+    its coefficients), which would otherwise give it a spectrum and a coherence of order one with its partner"""
+    if float(np.abs(x).max()) == 0.0:
+        return 0.0
+    return 1.0 / pack_scale(x)
+
+
 def packed_transforms(a, b):
     """F[a], F[b] of two real planes by the device's route: ONE transform of s_a a + i s_b b with the powers of two of
     ``pack_scale`` (two fields that share a transform share its rounding, a few ulp of the LARGER one's coefficients: unscaled,
     q_psi packed with |phi|^2 would lose digits in proportion to their ratio), split by ``split_packed``, the scales taken out"""
+    if unpack_scale(a) == 0.0 and unpack_scale(b) != 0.0:
+        # a first field that vanishes changes places with its partner: b's transform is then the one b alone gets, F[b + i 0],
+        # wherever in the list the zero field stands (F[0 + i b] equals i F[b] only up to the last bit)
+        B, A = packed_transforms(b, a)
+        return A, B
     sa, sb = pack_scale(a), pack_scale(b)
     A, B = split_packed(np.fft.fft2(sa * np.asarray(a, np.float64) + 1j * (sb * np.asarray(b, np.float64))))
-    return A / sa, B / sb
+    return A * unpack_scale(a), B * unpack_scale(b)
 
 
 class CrossSpectra(object):

@@ -45,7 +45,8 @@ __device__ __forceinline__ void cross_store(const cd (&w)[XPlan<N>::P], const MA
 }
 
 // The scales of a call: scl[i] = 2^-e_i with e_i the binary exponent of max |field i| over the plane (1 for a field that is zero,
-// subnormal throughout, not finite or not in the list), scl[3 + i] = 2^e_i.  part: the workgroup partials of the PDFs' range pass (k_x_hist /
+// subnormal throughout, not finite or not in the list), scl[3 + i] = 2^e_i, and 0 for a field whose maximum |value| is exactly 0:
+// BinCross multiplies the field's split part by it, so the rows of a vanishing field are exact zeros.  part: the workgroup partials of the PDFs' range pass (k_x_hist /
 // k_x_flow_hist with MINMAX), `per` doubles per workgroup, minimum and maximum of field i at [2 slot[i]], [2 slot[i] + 1].
 // One workgroup of 256 threads; a maximum does not depend on the order it is taken in.
 struct CrossSlots { int slot[COSPEC_FIELDS]; };
@@ -76,8 +77,18 @@ __global__ void __launch_bounds__(256) k_cospec_scale(const double* __restrict__
     // zero, NaN, infinity: unscaled; so is a field below the smallest normal number, whose 2^-e would overflow
     const int e = (x >= 2.2250738585072014e-308 && x <= 1.7976931348623157e308) ? ilogb(x) : 0;
     scl[i] = ldexp(1.0, -e);
-    scl[COSPEC_FIELDS + i] = ldexp(1.0, e);
+    // A field that vanishes everywhere (or is not in the list) comes back out with the factor 0: packed with a partner, its
+    // split part (Z - Z*) / (2i) is the round-off of the PARTNER's transform, not zero, and would give it a spectrum of ~1e-32
+    // of the partner's and a coherence of order one.  0 times that round-off is an exact zero in every row the field is in.
+    scl[COSPEC_FIELDS + i] = x == 0.0 ? 0.0 : ldexp(1.0, e);
   }
+}
+
+// A first field that vanishes everywhere beside a second one that does not: the two change places in the packed row, so that the
+// second field's transform is the one a call of that field alone runs, F[b + i 0], and its rows do not depend on where in the list
+// the zero field stands (F[0 + i b] is i F[b] only up to the last bit).  k_x_cross and BinCross read it off the scales alike.
+__device__ __forceinline__ bool cross_swapped(const double* __restrict__ scl) {
+  return scl[COSPEC_FIELDS] == 0.0 && scl[COSPEC_FIELDS + 1] != 0.0;
 }
 
 // sel.code[i]: the i-th field of the list (FLOW_NONE past its end); scl: k_cospec_scale's; oAB, oC: full-width rows
@@ -96,13 +107,15 @@ k_x_cross(MArr Mq, MArr Mqw, MArr Mu, MArr Mp, MArr Mphi, MArr Mphiy, const cd* 
   twr.base = lds + F::LDS_ELEMS;                       // the twiddles x_row_values / x_flow_values staged: nothing overwrote them
   cd w[P];
   double cv[P];
+  const bool swap = cross_swapped(scl);                // workgroup-uniform
   if constexpr (FLOW) {
     double val[COSPEC_FIELDS][P];
     x_flow_values<N, MODE, SLAB>(Mq, Mqw, Mu, Mp, Mphi, Mphiy, tw, kk, sel, val, w);
     const double s0 = scl[0], s1 = scl[1], s2 = scl[2];
 #pragma unroll
     for (int t = 0; t < P; ++t) {                      // slots nothing was selected for are zero
-      w[t] = cmake(s0 * val[0][t], s1 * val[1][t]);
+      const double a = s0 * val[0][t], b = s1 * val[1][t];
+      w[t] = swap ? cmake(b, a) : cmake(a, b);
       cv[t] = s2 * val[2][t];
     }
   } else {
@@ -112,7 +125,8 @@ k_x_cross(MArr Mq, MArr Mqw, MArr Mu, MArr Mp, MArr Mphi, MArr Mphiy, const cd* 
 #pragma unroll
     for (int t = 0; t < P; ++t) {
       const double a2 = w[t].x * w[t].x + w[t].y * w[t].y;
-      w[t] = cmake(s0 * cross_pick(sel.code[0], q[t], qpsi[t], a2), s1 * cross_pick(sel.code[1], q[t], qpsi[t], a2));
+      const double a = s0 * cross_pick(sel.code[0], q[t], qpsi[t], a2), b = s1 * cross_pick(sel.code[1], q[t], qpsi[t], a2);
+      w[t] = swap ? cmake(b, a) : cmake(a, b);
       cv[t] = s2 * cross_pick(sel.code[2], q[t], qpsi[t], a2);
     }
   }
@@ -141,16 +155,20 @@ struct BinCross {
     (void)kl;
     const size_t idx = (size_t)l * N + k, im = (size_t)((N - l) % N) * N + (N - k) % N;
     const cd x = z[idx], xm = z[im];
-    const double ha = 0.5 * scl[COSPEC_FIELDS], hb = single ? 0.0 : 0.5 * scl[COSPEC_FIELDS + 1];       // the scales taken out again: exact
+    const bool swap = cross_swapped(scl);               // the real part of the packed plane is then field 1, the imaginary part field 0
+    const double s0 = scl[COSPEC_FIELDS], s1 = scl[COSPEC_FIELDS + 1];
+    const double ha = 0.5 * (swap ? s1 : s0), hb = single ? 0.0 : 0.5 * (swap ? s0 : s1);       // the scales taken out again: exact
     const cd a = cmake(ha * (x.x + xm.x), ha * (x.y - xm.y)), b = cmake(hb * (x.y + xm.y), hb * (xm.x - x.x));
-    v[0] += a.x * a.x + a.y * a.y;
-    v[1] += b.x * b.x + b.y * b.y;
+    const double aa = a.x * a.x + a.y * a.y, bb = b.x * b.x + b.y * b.y;
+    v[0] += swap ? bb : aa;
+    v[1] += swap ? aa : bb;
     v[3] += a.x * b.x + a.y * b.y;
     if (zc != nullptr) {
       const cd c = cscale(zc[(size_t)l * pc + k], scl[COSPEC_FIELDS + 2]);
+      const double ac = a.x * c.x + a.y * c.y, bc = b.x * c.x + b.y * c.y;
       v[2] += c.x * c.x + c.y * c.y;
-      v[4] += a.x * c.x + a.y * c.y;
-      v[5] += b.x * c.x + b.y * c.y;
+      v[4] += swap ? bc : ac;
+      v[5] += swap ? ac : bc;
     }
   }
 };

@@ -169,6 +169,38 @@ def test_packed_route_equals_the_separate_transforms(nx):
           % (nx, float((np.abs(raw[0] - cospectra.table([np.fft.fft2(q)], nx)[0]) / cospectra.bin_shells(np.abs(np.fft.fft2(q)) ** 2, nx)).max())))
 
 
+@pytest.mark.parametrize("nx", [64, 128])
+def test_packed_route_with_a_zero_field(nx):
+    """A field that vanishes everywhere, packed with a partner: the plain split leaves it the round-off of the partner's transform
+    (a spectrum of 1e-32 of the partner's and a coherence of order one); taken out with ``unpack_scale`` = 0 its rows are exact
+    zeros and its coherence NaN, in either position, and the partner's rows are those of the partner packed with nothing."""
+    from niwqg_amd import cospectra
+    q, phi2, r = fields(nx)
+    zero = np.zeros_like(q)
+    assert cospectra.unpack_scale(zero) == 0.0 and cospectra.unpack_scale(q) * cospectra.pack_scale(q) == 1.0
+    assert cospectra.unpack_scale(np.full((4, 4), 1e-310)) == 1.0
+    M2 = float(nx) ** 4
+    # the defect this rule removes, for the record: the unscaled split of fft2(a + 0j)
+    plain = cospectra.CrossSpectra(("a", "b"), cospectra.table(list(cospectra.split_packed(np.fft.fft2(q + 0j))), nx), 1.0, nx)
+    print("%d: plain split, zero partner: max auto[b] = %.3g, max |coherence| = %.3g"
+          % (nx, plain.auto["b"].max(), np.nanmax(np.abs(plain.coherence("a", "b")))))
+    alone = cospectra.table([cospectra.split_packed(np.fft.fft2(cospectra.pack_scale(q) * q + 0j))[0] * cospectra.unpack_scale(q)], nx)
+    for a, b, za in ((q, zero, False), (zero, q, True)):
+        A, B = cospectra.packed_transforms(a, b)
+        R = cospectra.CrossSpectra(("a", "b"), cospectra.table([A, B], nx), 1.0, nx)
+        z, x = ("a", "b") if za else ("b", "a")
+        assert np.array_equal(R.auto[z], np.zeros_like(R.auto[z])) and np.array_equal(R.co[("a", "b")], np.zeros_like(R.auto[z]))
+        assert np.isnan(R.coherence("a", "b")).all() and np.isnan(R.correlation("a", "b"))
+        assert (R.auto[x][1:] > 0).all()
+        # the partner's transform does not see the zero field at all, wherever the zero field stands (a zero first field changes
+        # places with its partner)
+        assert np.array_equal(R.raw[1 if za else 0], alone[0])
+        want = cospectra.bin_shells(np.abs(np.fft.fft2(q)) ** 2, nx)
+        assert (np.abs(R.auto[x] * M2 - want) <= 1e-12 * want + cospectra.transform_rounding(np.fft.fft2(q), np.fft.fft2(q), q, q, nx, packed=True) * M2).all()
+    A, B = cospectra.packed_transforms(zero, zero)
+    assert not A.any() and not B.any()
+
+
 def test_entry_points_are_exported_and_typed():
     import niwqg_amd
     niwqg_amd.build()

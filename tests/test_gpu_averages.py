@@ -50,6 +50,9 @@ def own(m, name):
         return p.real * p.real + p.imag * p.imag
     if name == "q_psi" and any_size(m):
         return m._pdf_planes(["q_psi"])["q_psi"][0].get()
+    from niwqg_amd import flow
+    if name in flow.NAMES:                                 # no attribute of the model: the numpy restatement from m.ph, m.phih, m.q_psi
+        return flow.reference(m, [name])[name]
     return np.array(getattr(m, name))
 
 

@@ -4,7 +4,9 @@ maps equal the numpy restatement ``coarse.reference``, the moments agree with th
 bit-reproducible, nothing disturbs the run, and the models and grids without the maps refuse.
 
 Grids: 64 (eight rows per workgroup), 128 (four), 512 (one row, one wave), 1024 (two waves per row): the smallest shapes at which
-the row plan changes; 2048 and 4096 once, identity only.  States: those of test_gpu_flow.make, white part included (the Nyquist
+the row plan changes; 2048 and 4096 once, identity only here; values at 256 and 2048, moments at 4096,
+the two-pass tiles at 64 ... 512 and another column split at 1024 in tests/test_gpu_plan_ladder_analysis.py and the children of
+tests/test_gpu_plan_ladder.py, through ``check_maps``, ``check_mean_closes`` and ``check_moments`` of this module.  States: those of test_gpu_flow.make, white part included (the Nyquist
 lines carry energy), set and then advanced 3 steps, so quirks Q1 (UnCoupledModel's and YBJModel's stale gradients) and Q2 are live.
 
 Bounds.  Identity: |mean - flux[B]| <= 1e-12 (mean |map| + sum_b |T_b|), the project's standing 1e-12 of two device routes to
@@ -65,18 +67,24 @@ def cases():
 # ---- 1. the plane mean closes on the spectral flux -----------------------------------------------------------------------------
 @pytest.mark.parametrize("kind, nx, mask", CASES)
 def test_mean_closes_on_the_spectral_flux(cases, kind, nx, mask):
+    c = cases(kind, nx, mask)
+    check_mean_closes(c["m"], c["R"], c["shells"], "%s %d %s" % (kind, nx, mask))
+
+
+def check_mean_closes(m, R, shells, tag, cut_list=None):
+    """R: flux_maps on the tables [sharp(B) for B in shells] + ...; the plane mean of every sharp map on the cuts of the name
+    (cut_list: on these shells instead) against the spectral flux"""
     from niwqg_amd import coarse
     from niwqg_amd.transfer import spectral_transfer
-    c = cases(kind, nx, mask)
-    m, R = c["m"], c["R"]
+    nx = m.nx
     assert list(R.names) == coarse.available(m)
     st = spectral_transfer(m)
     for name in R.names:
         T = st.transfer[name]
-        for B in cuts(nx, name):
-            i = c["shells"].index(B)
+        for B in (cuts(nx, name) if cut_list is None else cut_list):
+            i = shells.index(B)
             err, scale = abs(R.mean[name][i] - st.flux[name][B]), np.abs(R.maps[name][i]).mean() + np.abs(T).sum()
-            print("%s %d %s %s B = %d: %.3g" % (kind, nx, mask, name, B, err / scale))
+            print("%s %s B = %d: %.3g" % (tag, name, B, err / scale))
             assert scale > 0 and err <= 1e-12 * scale, (name, B, err, scale)
 
 
@@ -112,11 +120,15 @@ def test_maps_equal_the_reference(cases, kind, nx, mask):
     c = cases(kind, nx, mask)
     m, R = c["m"], c["R"]
     assert bool(m._ctx.dual_q) == (mask == "dealias")
-    for i, g in enumerate(c["tab"]):
+    check_maps(m, R, c["tab"], c["ref"], "%s %d %s" % (kind, nx, mask))
+
+
+def check_maps(m, R, tab, ref, tag):
+    for i, g in enumerate(tab):
         f = factor_maxima(m, g)
         for name in R.names:
-            err, scale = np.abs(R.maps[name][i] - c["ref"][name][i]).max(), value_scale(name, f)
-            print("%s %d %s %s table %d: max |device - reference| / scale = %.3g" % (kind, nx, mask, name, i, err / scale))
+            err, scale = np.abs(R.maps[name][i] - ref[name][i]).max(), value_scale(name, f)
+            print("%s %s table %d: max |device - reference| / scale = %.3g" % (tag, name, i, err / scale))
             assert scale > 0 and err <= 1e-12 * scale, (name, i, err, scale)
 
 
@@ -126,18 +138,23 @@ def test_moments_agree_with_the_maps(cases, kind, nx, mask):
     from niwqg_amd import coarse
     c = cases(kind, nx, mask)
     m, R = c["m"], c["R"]
+    check_moments(R, nx, len(c["tab"]))
+    S = coarse.flux_maps(m, table=c["tab"], maps=False)
+    assert S.maps is None
+    for name in R.names:
+        assert S.sums[name].tobytes() == R.sums[name].tobytes() and S.sumsq[name].tobytes() == R.sumsq[name].tobytes(), name
+
+
+def check_moments(R, nx, ntab):
+    """mean and variance of every map against numpy's on the downloaded map"""
     M = float(nx) * nx
     for name in R.names:
-        for i in range(len(c["tab"])):
+        for i in range(ntab):
             x = R.maps[name][i]
             a1, a2 = np.abs(x).sum() / M, (x * x).sum() / M
             assert abs(R.mean[name][i] - x.mean()) <= 1e-12 * a1, (name, i)
             assert abs(R.variance[name][i] - x.var()) <= 1e-12 * a2, (name, i)
             assert R.variance[name][i] > 0
-    S = coarse.flux_maps(m, table=c["tab"], maps=False)
-    assert S.maps is None
-    for name in R.names:
-        assert S.sums[name].tobytes() == R.sums[name].tobytes() and S.sumsq[name].tobytes() == R.sumsq[name].tobytes(), name
 
 
 # ---- 4. scales and calls -------------------------------------------------------------------------------------------------------

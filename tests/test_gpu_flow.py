@@ -5,7 +5,9 @@ old names' tables alone, the averages in the step are the sequential sums of the
 any-size path agrees, and the models without flow fields refuse.
 
 Grids: 64 (eight rows per workgroup), 128 (four), 512 (one row, one wave), 1024 (two waves per row: the plan's LDS outgrows the
-default tables).  States: broadband q and phi with a white part, so the Nyquist row and column carry energy."""
+default tables); 256, 2048, 4096 and 8192, the two-pass tiles at 64 ... 512 and another column split at 1024 are in
+tests/test_gpu_plan_ladder_analysis.py and the children of tests/test_gpu_plan_ladder.py, through ``check_values`` and
+``check_pdf_calls`` of this module.  States: broadband q and phi with a white part, so the Nyquist row and column carry energy."""
 import ctypes
 import types
 
@@ -157,11 +159,17 @@ PDF_CALLS = [(("q_psi", "ow", "gradphi2"), ("ow", "gradphi2")), (("ss", "phi2"),
 @pytest.mark.parametrize("kind, nx, mask", [("coupled", 64, "none"), ("uncoupled", 128, "none"), ("ybj", 512, "none"),
                                             ("coupled", 1024, "none"), ("coupled", 128, "filter")])
 def test_pdfs_close_and_equal_the_restatement(kind, nx, mask):
-    from niwqg_amd import pdfs
     m = make(kind, nx, mask)
     advance(m, 2, batched=True)
+    check_pdf_calls(m, kind, nx)
+
+
+def check_pdf_calls(m, kind, nx, calls=None):
+    """every call of ``calls`` (PDF_CALLS): the counts close, equal the restatement up to the points near an edge, the joint table's
+    marginals are the 1-D counts, the default edges are the exact extremes"""
+    from niwqg_amd import pdfs
     bins, jb = 96, 24
-    for names, joint in PDF_CALLS:
+    for names, joint in (PDF_CALLS if calls is None else calls):
         ref = reference_with_old(m, names)
         ranges = {n: wide(ref[n]) for n in names}
         h = pdfs.field_pdfs(m, names=names, bins=bins, ranges=ranges, joint=joint, joint_bins=bins)

@@ -10,6 +10,10 @@ Every check is one the feature's own test makes at another size, through the sam
 1e-12 relative L2 between two states, 1e-12 of the field's maximum between two device routes to one plane, 1e-10 per shell over
 sum |ref| for spectra against numpy, 1e-11 sum |S| for closure, equality for counts, ring records and first-moment sums.
 
+The analysis features that came after this module (flow names, time-mean spectra, coarse-grained maps, shell-to-shell transfers,
+co-spectra) have their row plans, large plans and zero fields in the sibling tests/test_gpu_plan_ladder_analysis.py; the children of
+this module under NIWQG_AMD_SINGLE_PASS=0 and NIWQG_AMD_Y_SPLIT run them too (``check_analysis``).
+
 4096^2 and 8192^2 states are seeded white noise in physical space (the scaling of test_gpu_at_size's rough-field step, filter
 on): no host transform is needed to build them.  One model per size lives in a module-scoped fixture; its checks read it or step
 it forward, none depends on the step count another left behind."""
@@ -28,6 +32,11 @@ from test_gpu_pdfs import check_against_fields, check_closure, check_marginals, 
 from test_gpu_averages import own, attach_all, one_sample, advance
 from test_gpu_frequency import state_blocks, model as recorder_model
 from test_gpu_forcing import pair, amplitudes, full_hermitian, restated as restated_increment
+import test_gpu_flow as flow_t
+import test_gpu_coarse as coarse_t
+import test_gpu_shelltoshell as s2s_t
+import test_gpu_cospectra as cospec_t
+import test_gpu_timespectra as tspec_t
 
 pytestmark = pytest.mark.gpu
 
@@ -298,6 +307,50 @@ def check_forced_twin(A, B, kind, seed=21):
         assert e <= 1e-12, (j, a[:, j], b[:, j])
 
 
+def check_coarse(m, shells, tag, gaussian=False, names=None):
+    """test_gpu_coarse's three value checks on the sharp cuts `shells` (and one Gaussian): the maps equal coarse.reference, the
+    plane means close on the spectral flux, the moments agree with the downloaded maps"""
+    from niwqg_amd import coarse
+    tab = np.array([coarse.sharp(m, B) for B in shells] + ([coarse.gaussian(m, coarse_t.length(m))] if gaussian else []))
+    R = coarse.flux_maps(m, table=tab, names=names)
+    coarse_t.check_maps(m, R, tab, coarse.reference(m, tab, list(R.names)), tag)
+    if names is None:
+        coarse_t.check_mean_closes(m, R, list(shells), tag, cut_list=list(shells))
+    coarse_t.check_moments(R, m.nx, len(tab))
+    return R
+
+
+def check_s2s_rows(m, edges, tag, names=None):
+    """test_gpu_shelltoshell.test_rows_equal_the_reference on the bands between `edges`"""
+    from niwqg_amd import shelltoshell
+    R = shelltoshell.shell_to_shell(m, edges, names=names)
+    assert R.raw.shape[0] == len(edges) - 1
+    s2s_t.check_rows(m, R, tag, m.nx, "")
+    return R
+
+
+def check_qgc_cospectra(m, tag):
+    """test_gpu_cospectra.test_qgmodel's value check: QGModel bins q-hat and c-hat as they are"""
+    from niwqg_amd import cospectra
+    planes = {n: np.array(getattr(m, n), np.float64) for n in ("q", "c")}
+    T = cospec_t.transforms(planes)
+    for lst in (("q", "c"), ("c", "q")):
+        cospec_t.check_rows(cospectra.cross_spectra(m, lst), T, planes, m.nx, tag, packed=False)
+
+
+def check_analysis(m, kind, tag, cuts, edges, lists):
+    """the analysis features of sections 5m to 5q on one state of a coupled or a qgc model, against numpy: what a child under
+    a column-plan switch adds to its battery"""
+    from niwqg_amd import flow
+    if kind == "coupled":
+        flow_t.check_values(m, flow.NAMES, tag)
+        cospec_t.check_lists(m, m.nx, tag, lists=lists)
+    else:
+        check_qgc_cospectra(m, tag)
+    check_coarse(m, cuts, tag)
+    check_s2s_rows(m, edges, tag)
+
+
 # ---- 1. averages on every row plan ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind, nx, mask", [("coupled", 128, "filter"), ("coupled", 256, "filter"), ("coupled", 2048, "filter"),
                                             ("uncoupled", 256, "filter"), ("uncoupled", 2048, "filter"), ("ybj", 1024, "filter"),
@@ -419,7 +472,12 @@ def battery(nx):
         check_transfer_numpy(m, kind)
         check_pdfs(m, kind)
         check_averages(m, kind)
-        check_forced_twin(make(kind, nx), make(kind, nx), kind)
+        twins = [make(kind, nx) for _ in range(4)]
+        check_forced_twin(twins[0], twins[1], kind)
+        check_analysis(m, kind, "%s %d two-pass" % (kind, nx), sorted({2, nx // 8}), [0, 4, nx // 8, nx // 2], cospec_t.LISTS[:2])
+        tspec_t.check_bit_identity(twins[2], twins[3], kind, 4)
+        for t in twins:
+            t._ctx.close()
         out[kind + ":a_subpasses"] = np.array(a_subpasses_of_one_step(m))
     return out
 
@@ -461,6 +519,7 @@ def split_run():
     steps(m, 10)
     check_spectra_numpy(m, "coupled 16,64")
     check_transfer_numpy(m, "coupled 16,64")
+    check_analysis(m, "coupled", "coupled 1024 split 16,64", [1024 // 8], [0, 16, 1024 // 16, 1024 // 2], cospec_t.LISTS[1:2])
     return state_of(m)
 
 

@@ -4,7 +4,10 @@ restatement ``shelltoshell.reference``, their sum over the donor bands closes on
 bit-reproducible, nothing disturbs the run, and the models and grids without the transfers refuse.
 
 Grids: 64 (eight rows per workgroup), 128 (four), 512 (one row, one wave), 1024 (two waves per row): the smallest shapes at which
-the row plan changes; 2048 and 4096 once, closure only, 3 bands.  States: those of test_gpu_flow.make, white part included (the
+the row plan changes; 2048 and 4096 once, closure only, 3 bands, on a band-limited state; the rows against
+the reference at 256, 1024 and 2048, the closure on a broadband state at 4096, the two-pass tiles at 64 ... 512 and another column
+split at 1024 are in tests/test_gpu_plan_ladder_analysis.py and the children of tests/test_gpu_plan_ladder.py, through ``check_rows``,
+``check_closure`` and ``check_antisymmetry`` of this module.  States: those of test_gpu_flow.make, white part included (the
 Nyquist lines carry energy), set and then advanced 3 steps, so quirks Q1 and Q2 are live ("broadband"); and a state band-limited
 to shell nx/8, just set ("fresh"): nothing on the shells >= nx/2 and alias-free triple products (on CoupledModel psi carries up
 to 2 nx/8 through q_w: the factors' top shells sum to 4 nx/8 < nx).
@@ -83,11 +86,16 @@ def cases():
 # ---- 1. the device rows equal the reference --------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind, nx, mask", [c for c in CASES if c[1] <= 512])
 def test_rows_equal_the_reference(cases, kind, nx, mask):
-    from niwqg_amd import shelltoshell
     c = cases(kind, nx, mask)
     m, R = c["m"], c["R"]
     assert bool(m._ctx.dual_q) == (mask == "dealias")
-    ref = shelltoshell.reference(m, c["tab"], R.names)
+    check_rows(m, R, kind, nx, mask)
+
+
+def check_rows(m, R, kind, nx, mask):
+    """the rows of R against shelltoshell.reference on R's own table, 1e-10 of sum |T| per name"""
+    from niwqg_amd import shelltoshell
+    ref = shelltoshell.reference(m, R.table, R.names)
     for name in R.names:
         err, scale = np.abs(R.rows[name] - ref[name]).max(), np.abs(ref[name]).sum()
         print("%s %d %s %s: max |device - reference| / sum |T| = %.3g" % (kind, nx, mask, name, err / scale))

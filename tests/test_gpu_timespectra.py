@@ -8,7 +8,9 @@ fused multiply-add saves.
 
 Shapes: 64 is the smallest fused plan (single-pass columns), every family once; 64 with dealias=True is a dual-copy context (the
 mean of the two q-hat copies goes through the scratch plane the two bodies share); 1024 has two-pass columns; 4096 (two steps,
-the only large case) runs the q update on a second stream, which the sample must come after."""
+the only large case here) runs the q update on a second stream, which the sample must come after; 128, 256, 512, 2048, 8192 and
+the two-pass tiles at 64 ... 512 are in tests/test_gpu_plan_ladder_analysis.py and the children of tests/test_gpu_plan_ladder.py,
+through ``check_bit_identity`` of this module."""
 import ctypes
 
 import numpy as np
@@ -118,8 +120,13 @@ CASES5 = [("coupled", 64, "filter", NSTEPS), ("uncoupled", 64, "filter", NSTEPS)
 
 @pytest.mark.parametrize("kind, nx, mask, n", CASES5)
 def test_bit_identity_batched(kind, nx, mask, n):
-    from niwqg_amd import timespectra
     A, B = twin(kind, nx, mask)
+    check_bit_identity(A, B, kind, n, mask)
+
+
+def check_bit_identity(A, B, kind, n, mask="filter"):
+    """A with both bodies attached and two batched nq_step calls, B driven by single steps and the two host calls"""
+    from niwqg_amd import timespectra
     if mask == "mask":
         assert A._ctx.dual_q
     T = timespectra.attach(A, spectra=True, transfer=True, every=1)

@@ -6,7 +6,7 @@
 --cost: CoupledModel at nx with a broadband state; four calls alternate --reps times in one run, each timed with device events
 after a warm-up call, and the medians are reported: cross_spectra on (q_psi, phi2) and on (q_psi, ow, gradphi2), both without
 download, spectral_transfer(m)'s device call, and the flow-names field_pdfs call of tools/flow_cost.py.
---check: the instantiations the tests do not reach.  Every row of every list against numpy's fft2 of the planes one averages
+--check: the instantiations the feature's own test does not reach (tests/test_gpu_plan_ladder_analysis.py does since).  Every row of every list against numpy's fft2 of the planes one averages
 sample returns for the same names, per shell, in units of the tests' bar (tests/test_gpu_cospectra.py: the issue's 1e-12 of the
 shell's content on every resolved shell): ok means <= 1.  At 8192 a
 list with a flow name must be refused and the three old names are checked."""

@@ -4,7 +4,7 @@
     python tools/flow_cost.py --check 2048       # one sample of every flow name against flow.reference; one JSON line
 
 --cost: CoupledModel at nx with a broadband state; the three calls alternate --reps times in one run, each timed with device
-events after a warm-up call, and the medians are reported.  --check: the instantiations the tests do not reach (2048, 4096, and
+events after a warm-up call, and the medians are reported.  --check: the instantiations the feature's own test does not reach, which tests/test_gpu_plan_ladder_analysis.py covers since (2048, 4096, and
 8192, where every name runs in a launch of its own)."""
 import argparse
 import json
