@@ -495,6 +495,15 @@ int nq_overlap_grid(int nb, int cus);
 int nq_overlap_default_cus(int nx);
 int nq_overlap_info(const nq_ctx* ctx, int* out3);
 
+/* ---- grids of the persistent row kernels ------------------------------------------------------------------
+ * The products and the wave-PV row kernels of 4096- and 8192-point rows are persistent: g workgroups walk nb row blocks in
+ * ceil(nb / g) rounds, g from the CU count of the device.  NIWQG_AMD_NUM_CU=n (read by nq_create, 1 <= n <= the device's count,
+ * anything else is refused) sizes those grids as if the device had n CUs; it masks no CU and exists so that tests can run
+ * grids that do not divide their rows.  nq_row_grid_info: out6 = {CU count in use, CUs reserved on a slab link
+ * (NIWQG_AMD_SLAB_RESERVE_CUS), products grid, products row blocks, wave-PV grid, wave-PV row blocks} of a launch over all
+ * rows of this context, from the same arithmetic the launches use.                                                         */
+int nq_row_grid_info(const nq_ctx* ctx, int* out6);
+
 /* ---- 1-D slab decomposition over nranks GPUs (one process per GPU) -----------------
  * Rows of the mixed-space planes are split over ranks on the "x side" (row kernels), columns on the "y side"
  * (spectral kernels).  Arrays that cross together form an exchange group g = 0..3; each group has an x-side

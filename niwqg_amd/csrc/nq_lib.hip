@@ -1333,26 +1333,63 @@ static MArr rw(const nq_ctx* c, const MArr& m) {
   if (r.xs) r.xs += (size_t)c->row0 * m.pitch;
   return r;
 }
+// Grid and row blocks of a row kernel over `nrows` rows of an N-point grid: the one place that sizes them, for the launches
+// below and for nq_row_grid_info.  A persistent grid never exceeds its row blocks (grid <= nb): every workgroup owns the block
+// blockIdx.x, which the 4096-point kernels request before their loop without a guard.
+enum { RG_PRODUCTS = 0, RG_WAVEPV = 1 };
+struct RowGrid { int grid, nb; };
+template <int N>
+static RowGrid row_grid(const nq_ctx* c, int which, int nrows) {
+  RowGrid g;
+  if (which == RG_WAVEPV) {
+    if constexpr (N == 8192) {
+      const int ncu = (c->stream2 ? c->overlap_grid : c->num_cu) - c->reserve_cus, nb = nrows, grid = nb < ncu ? nb : ncu;
+      g.grid = grid;
+      g.nb = nb;
+    } else if constexpr (N == 4096) {
+      typedef XPlan<4096> X;
+      int grid = (c->stream2 ? c->overlap_grid : c->num_cu) - c->reserve_cus;      // one persistent workgroup per CU
+      const int nb = nrows / X::C;
+      if (grid > nb) grid = nb;
+      g.grid = grid;
+      g.nb = nb;
+    } else {                                          // not persistent: one workgroup per row block
+      g.grid = g.nb = nrows / XPlan1<N>::C;
+    }
+    return g;
+  }
+  const int ncu = c->num_cu - c->reserve_cus;
+  if constexpr (N == 8192) {
+    const int nb = nrows, grid = nb < ncu ? nb : ncu;
+    g.grid = grid;
+    g.nb = nb;
+  } else {
+    typedef XPlan<N> X;
+    const int nb = nrows / X::C;
+    // one workgroup fits per CU (LDS) and does not spill: persistent; 8192-point rows spill and do better with dynamic dispatch
+    const int grid = (X::LDS_BYTES > 80 * 1024 && X::THREADS <= 512 && nb > ncu) ? ncu : nb;
+    g.grid = grid;
+    g.nb = nb;
+  }
+  return g;
+}
 template <bool SLAB>
 static void launch_wavepv_t(nq_ctx* c) {
   const MArr mPhi = rw(c, c->mPhi), mPhiy = rw(c, c->mPhiy), mA = rw(c, c->mA), mB = rw(c, c->mB);
   with_row_size(c->N, [&](auto n) {
     constexpr int N = decltype(n)::value;
+    const RowGrid g = row_grid<N>(c, RG_WAVEPV, c->nrows);
     if constexpr (N == 8192) {                        // even / odd samples as two 4096-point problems (no spills)
       typedef XPlan<4096> X;
-      const int ncu = (c->stream2 ? c->overlap_grid : c->num_cu) - c->reserve_cus, nb = c->nrows, grid = nb < ncu ? nb : ncu;
       const size_t ldsb = X::LDS_BYTES + (size_t)4096 * sizeof(cd);           // + the 64 KB of thread-private park slots
-      hipLaunchKernelGGL((k_x_wavepv_eo<8192, SLAB>), dim3(grid), dim3(X::THREADS), ldsb, c->stream, mPhi, mPhiy, mA, mB, c->twx_half, c->tw, c->kk, nb);
+      hipLaunchKernelGGL((k_x_wavepv_eo<8192, SLAB>), dim3(g.grid), dim3(X::THREADS), ldsb, c->stream, mPhi, mPhiy, mA, mB, c->twx_half, c->tw, c->kk, g.nb);
     } else if constexpr (N == 4096) {                 // long rows: two transforms in flight, no spills
       typedef XPlan<4096> X;
       const size_t ldsb = X::LDS_BYTES + X::F::LDS_ELEMS * sizeof(cd);
-      int grid = (c->stream2 ? c->overlap_grid : c->num_cu) - c->reserve_cus;      // one persistent workgroup per CU
-      const int nb = c->nrows / X::C;
-      if (grid > nb) grid = nb;
-      hipLaunchKernelGGL((k_x_wavepv2<4096, SLAB>), dim3(grid), dim3(X::THREADS), ldsb, c->stream, mPhi, mPhiy, mA, mB, c->twx, c->kk, nb);
+      hipLaunchKernelGGL((k_x_wavepv2<4096, SLAB>), dim3(g.grid), dim3(X::THREADS), ldsb, c->stream, mPhi, mPhiy, mA, mB, c->twx, c->kk, g.nb);
     } else {
       typedef XPlan1<N> X;
-      hipLaunchKernelGGL((k_x_wavepv<N, SLAB>), dim3(c->nrows / X::C), dim3(X::THREADS), X::LDS_BYTES, c->stream, mPhi, mPhiy, mA, mB, c->twx1, c->kk);
+      hipLaunchKernelGGL((k_x_wavepv<N, SLAB>), dim3(g.grid), dim3(X::THREADS), X::LDS_BYTES, c->stream, mPhi, mPhiy, mA, mB, c->twx1, c->kk);
     }
   });
 }
@@ -1370,22 +1407,18 @@ static void launch_products_t(nq_ctx* c, double cj, double cr, bool fresh_grad) 
   const MArr mGx = rw(c, c->mGx), mGy = rw(c, c->mGy), mUc = rw(c, c->mUc), mVc = rw(c, c->mVc);
   const MArr& gx = (MODE == MODE_QGC) ? mUc : ((MODE == MODE_UNCOUPLED && !fresh_grad) ? mGx : mPhi);
   const MArr& gy = (MODE == MODE_QGC) ? mVc : ((MODE == MODE_UNCOUPLED && !fresh_grad) ? mGy : mPhiy);
-  const int ncu = c->num_cu - c->reserve_cus;
   with_row_size(c->N, [&](auto n) {
     constexpr int N = decltype(n)::value;
+    const RowGrid g = row_grid<N>(c, RG_PRODUCTS, c->nrows);
     if constexpr (N == 8192) {
       // rows too long for the register budget as one transform: even / odd samples as two 4096-point problems
       // (their stage table, c->twx_half, exists on every 8192 context)
       typedef XPlan<4096> X;
-      const int nb = c->nrows, grid = nb < ncu ? nb : ncu;
       const size_t ldsb = X::LDS_BYTES + (size_t)4096 * sizeof(cd);             // + the 64 KB of thread-private park slots
-      hipLaunchKernelGGL((k_x_products_eo<8192, MODE, SLAB>), dim3(grid), dim3(X::THREADS), ldsb, c->stream, mU, mP, mQ, mQw, mPhi, gx, gy, mUq, mVq, mW, c->twx_half, c->tw, c->kk, vz, cj, cr, nb);
+      hipLaunchKernelGGL((k_x_products_eo<8192, MODE, SLAB>), dim3(g.grid), dim3(X::THREADS), ldsb, c->stream, mU, mP, mQ, mQw, mPhi, gx, gy, mUq, mVq, mW, c->twx_half, c->tw, c->kk, vz, cj, cr, g.nb);
     } else {
       typedef XPlan<N> X;
-      const int nb = c->nrows / X::C;
-      // one workgroup fits per CU (LDS) and does not spill: persistent; 8192-point rows spill and do better with dynamic dispatch
-      const int grid = (X::LDS_BYTES > 80 * 1024 && X::THREADS <= 512 && nb > ncu) ? ncu : nb;
-      hipLaunchKernelGGL((k_x_products<N, MODE, SLAB>), dim3(grid), dim3(X::THREADS), X::LDS_BYTES, c->stream, mU, mP, mQ, mQw, mPhi, gx, gy, mUq, mVq, mW, c->twx, c->kk, vz, cj, cr, nb);
+      hipLaunchKernelGGL((k_x_products<N, MODE, SLAB>), dim3(g.grid), dim3(X::THREADS), X::LDS_BYTES, c->stream, mU, mP, mQ, mQw, mPhi, gx, gy, mUq, mVq, mW, c->twx, c->kk, vz, cj, cr, g.nb);
     }
   });
 }
@@ -1723,6 +1756,20 @@ int nq_overlap_grid(int nb, int cus) {
 }
 
 int nq_overlap_default_cus(int nx) { return nx == 4096 ? NQ_OVERLAP_CUS_DEFAULT : 0; }
+int nq_row_grid_info(const nq_ctx* c, int* out6) {
+  if (!c || !out6) return -1;
+  out6[0] = c->num_cu;
+  out6[1] = c->reserve_cus;
+  with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    const RowGrid p = row_grid<N>(c, RG_PRODUCTS, c->Nloc), w = row_grid<N>(c, RG_WAVEPV, c->Nloc);
+    out6[2] = p.grid;
+    out6[3] = p.nb;
+    out6[4] = w.grid;
+    out6[5] = w.nb;
+  });
+  return 0;
+}
 int nq_overlap_info(const nq_ctx* c, int* out3) {
   if (!c || !out3) return -1;
   out3[0] = c->stream2 ? c->overlap_cus : 0;
@@ -2625,6 +2672,13 @@ static int create_impl(const nq_params* p_in, const double* kk, const double* ll
     {
       int ncu = 0;
       if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) c->num_cu = ncu;
+    }
+    if (const char* e = getenv("NIWQG_AMD_NUM_CU")) {      // the CU count the row grids are sized by (tests: grids that do not divide their rows)
+      char* end = nullptr;
+      const long v = strtol(e, &end, 10);
+      if (end == e || *end || v < 1 || v > c->num_cu)
+        NQ_FAIL(c, -2, "NIWQG_AMD_NUM_CU=%s: an integer in 1..%d (the CUs of the device); it sizes grids, it masks nothing", e, c->num_cu);
+      c->num_cu = (int)v;
     }
     if (ext_stream) {
       c->stream = reinterpret_cast<hipStream_t>(ext_stream);

@@ -201,7 +201,7 @@ def test_every_export_survives_a_null_context():
              lambda: lib.nq_timer_start(None), lambda: lib.nq_timer_stop(None, ctypes.byref(f)),
              lambda: lib.nq_profile_enable(None, 0), lambda: lib.nq_profile_read(None, ctypes.byref(n), ctypes.byref(f)),
              lambda: lib.nq_profile_read_all(None, (ctypes.c_int * 6)(), (ctypes.c_float * 6)()),
-             lambda: lib.nq_slab_info(None, (ctypes.c_int * 8)()),
+             lambda: lib.nq_slab_info(None, (ctypes.c_int * 8)()), lambda: lib.nq_row_grid_info(None, (ctypes.c_int * 6)()),
              lambda: lib.nq_group_buffers(None, 0, ctypes.byref(vp), ctypes.byref(vp), ctypes.byref(ll_)),
              lambda: lib.nq_upload_spectral(None, 0, d), lambda: lib.nq_download_spectral(None, 0, d),
              lambda: lib.nq_phase(None, 0, 0), lambda: lib.nq_reduce_buffer(None, 0, ctypes.byref(vp), ctypes.byref(n)),
