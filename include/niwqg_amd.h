@@ -289,6 +289,29 @@ int nq_particles_get(nq_ctx* ctx, double* x, double* y);
 int nq_particles_sample(nq_ctx* ctx, int nnames, const int* names, double* out);
 int nq_particles_records(nq_ctx* ctx, long long* info4, long long* steps, double* out);
 
+/* Lagrangian spectra and dispersion of the particle records, formed on the device, single-rank contexts
+ * only (-4 on slab contexts, -4 with no particles attached; -1 with record_every = 0 or fewer than 2 held records).  With the
+ * T held records (T must be their number), oldest first, and the particles taken in the order of a group-sorted index list --
+ * `order` (n indices in [0, n)) in G <= 256 runs, run g being order[offsets[g] .. offsets[g + 1] - 1], offsets[0] = 0,
+ * offsets[G] = n:
+ * spectrum: name 0 u, 1 v, 2 q (real series), 3 phi (complex), 4 u + i v (both recorded); a real finite window w_n (T values),
+ * demean: each particle's own time mean is subtracted first; X_p(i) = sum_n w_n x_n(i) e^{+2 pi i p n / nfft} (a series turning
+ * as e^{-i omega t} appears at +omega), T <= nfft <= 8192 or nfft = 16384;
+ *   out[p][g] = 1/2 sum_{i in run g} |X_p(i)|^2 / (nfft sum w^2),   (nfft, G), row p = FFT bin p.
+ * The particles go through a (nfft, C) work plane C at a time: chunk = 0 takes C from (n, nfft) alone (the plane within 256 MiB),
+ * chunk > 0 asks for that many (cut to the same bound); chunk partials are added in chunk order.
+ * dispersion: with d = r_n(i) - r_0(i) of the unwrapped positions, out[n][g][6] = the sums over run g of dx, dy, dx^2, dy^2,
+ * dx dy, (dx^2 + dy^2)^2; with npairs > 0 pairs (pi[q], pj[q]), indices in [0, n) and different, and s = r_n(pi) - r_n(pj),
+ * out_pairs[n][5] = the sums of sx^2, sy^2, sx sy, |s|^2, |s|^4.
+ * All sums are sums: the caller divides by the counts.  No floating-point atomics: two calls return the same bits.  The calls
+ * wait for the context's stream first and write nothing the step or the particles read.  Work memory (and, for the spectrum, an
+ * any-size engine for the transform along the record axis) is allocated by the first call, grows when a later call needs more,
+ * is counted by nq_device_bytes and freed by nq_particles_detach; an allocation that fails is -5 and leaves none of it.          */
+int nq_lagr_spectrum(nq_ctx* ctx, int name, int T, int nfft, const double* window, int demean, int G, const int* order, const int* offsets,
+                     int chunk, double* out);
+int nq_lagr_dispersion(nq_ctx* ctx, int T, int G, const int* order, const int* offsets, int npairs, const int* pi, const int* pj, double* out,
+                       double* out_pairs);
+
 /* Stochastic forcing of q and phi, single-rank contexts only (slab contexts refuse every call with -4).
  * After every step of nq_step (after the filtered ETDRK4 update, unfiltered) the library adds
  *   qh(l, k)   += sqrt(dt) Aq(l, k)   xi_q(l, k; s)      half spectrum (ny, nx/2+1), Hermitian: the forcing of q is a real field
@@ -725,6 +748,14 @@ int nq_any_freq_record(nq_any* eng, int nf, void* const* rings, const void* cons
                        int length, int slot);
 int nq_any_freq_spectrum(nq_any* eng, const void* ring, int rows, int kmax, int full, int kappa, int length, int first, int T,
                          const double* window, int demean, double dk, int nb, double* out);
+/* Lagrangian spectra and dispersion on engine planes (nq_lagr_spectrum above: the same kernels and tables).  The any-size path
+ * keeps one plane per record and name: re[r], im[r] are the device addresses of particle 0's real and imaginary part in record r,
+ * oldest first (im NULL: a real series; for the value of a complex plane: its address, and that plus 8 bytes), stride the doubles
+ * between particles (2 on a complex plane); pos[r]: the (1, n) plane x + i y of record r.  The work memory lives for the call.   */
+int nq_any_lagr_spectrum(nq_any* eng, int n, int T, const void* const* re, const void* const* im, int stride, int nfft, const double* window,
+                         int demean, int G, const int* order, const int* offsets, int chunk, double* out);
+int nq_any_lagr_dispersion(nq_any* eng, int n, int T, const void* const* pos, int G, const int* order, const int* offsets, int npairs,
+                           const int* pi, const int* pj, double* out, double* out_pairs);
 /* One sample of the averages on engine planes (nq_avg_attach above: the same rule, QGModel's kernel).  src[i]: complex planes of
  * `elems` values read as what[i] (0: Re, 1: |a|^2, 2: the complex value, at most once and in no product) and added to sums[i]
  * (elems doubles; what 2: elems complex); pairs: 2 x nproducts indices into src, psums[p] += the product.  Not synchronous.  */

@@ -485,6 +485,36 @@ class Context:
         self._chk(self.L.nq_particles_records(self.h, info, steps, _dptr(out)), "nq_particles_records")
         return np.array(steps[:m], np.int64), out
 
+    def particles_held(self, steps=False):
+        """records the ring holds; steps=True: their steps since attach (m,), oldest first (nothing is downloaded)"""
+        info = (ctypes.c_longlong * 4)()
+        self._chk(self.L.nq_particles_records(self.h, info, None, None), "nq_particles_records")
+        m = int(info[1])
+        if not steps:
+            return m
+        out = (ctypes.c_longlong * max(1, m))()
+        self._chk(self.L.nq_particles_records(self.h, info, out, None), "nq_particles_records")
+        return np.array(out[:m], np.int64)
+
+    # ---- Lagrangian spectra and dispersion (include/niwqg_amd.h: nq_lagr_*; niwqg_amd/lagrangian.py) ---------------------------
+    def lagr_spectrum(self, code, T, F, window, demean, G, order, offsets, chunk):
+        """(F, G) sums over each group, row p = FFT bin p"""
+        w = np.ascontiguousarray(window, np.float64)
+        out = np.empty((F, G))
+        self._chk(self.L.nq_lagr_spectrum(self.h, int(code), int(T), int(F), _dptr(w), int(bool(demean)), int(G), _iptr(order), _iptr(offsets),
+                                          int(chunk), _dptr(out)), "nq_lagr_spectrum")
+        return out
+
+    def lagr_dispersion(self, T, G, order, offsets, pairs):
+        """((T, G, 6) sums over each group, (T, 5) sums over the pairs or None)"""
+        out = np.empty((T, G, 6))
+        npairs = 0 if pairs is None else len(pairs[0])
+        outp = np.empty((T, 5)) if npairs else None
+        self._chk(self.L.nq_lagr_dispersion(self.h, int(T), int(G), _iptr(order), _iptr(offsets), npairs, _iptr(pairs[0]) if npairs else None,
+                                            _iptr(pairs[1]) if npairs else None, _dptr(out), _dptr(outp) if npairs else None),
+                  "nq_lagr_dispersion")
+        return out, outp
+
     # ---- PDFs of the physical fields (include/niwqg_amd.h: nq_field_hist; niwqg_amd/pdfs.py) --------------------------------
     def field_minmax(self, codes):
         """[(min, max)] of the listed fields (PDF_*), exact, from one device pass"""

@@ -64,6 +64,17 @@ struct DevOwned {
     bytes = to.bytes;
     return freed;
   }
+  // frees one allocation of `nbytes` out of order (no mark may be outstanding); returns the bytes no longer counted
+  long long release(void* p, long long nbytes) {
+    for (size_t i = 0; i < mem.size(); ++i)
+      if (mem[i] == p) {
+        (void)hipFree(p);
+        mem.erase(mem.begin() + i);
+        bytes -= nbytes;
+        return nbytes;
+      }
+    return 0;
+  }
 };
 // Host bookkeeping of a ring of `cap` records, one after every `every`-th step (every == 0: never).
 struct RecordRing {
@@ -90,6 +101,13 @@ struct NqParticles : DevOwned {            // Lagrangian particles (section 5g)
   double* qplane = nullptr;                // physical q (PT_Q), allocated when first needed
   cd* phiplane = nullptr;                  // physical phi (PT_PHI), idem
   double* samp = nullptr;                  // nq_particles_sample's output columns (4 x n), idem
+  // Lagrangian spectra and dispersion (section 5r): work plane, window, series table, index lists and tables, allocated by the
+  // first call and grown when a later call needs more; the transform of the record axis runs on an engine of its own
+  enum { LG_WORK = 0, LG_WIN, LG_SER, LG_ORDER, LG_OFFS, LG_TAB, LG_PAIRS, LG_NBUF };
+  void* lg[LG_NBUF] = {};
+  size_t lg_have[LG_NBUF] = {};            // bytes
+  nq_any* eng = nullptr;
+  ~NqParticles() { if (eng) (void)nq_any_destroy(eng); }
 };
 struct NqForcing : DevOwned {              // stochastic forcing (section 5i)
   double *Aq = nullptr, *Aphi = nullptr;   // amplitude planes: (N, N/2+1) and (N, N), contiguous
@@ -6748,6 +6766,315 @@ int nq_any_freq_spectrum(nq_any* e, const void* ring, int rows, int K, int full,
   ANYCHK(e, tmp.get(&dtab, (size_t)T * nb));
   return fq_spectrum_run(e, reinterpret_cast<const cd*>(ring), rows, K, ncols, full ? 1 : 0, kappa ? 1 : 0, length, first, T, window, demean, dk, nb, work,
                          dwin, dtab, out);
+}
+
+}  // extern "C"
+
+// ==================================================================================================================
+// Lagrangian spectra and dispersion of the particle records (kernels: csrc/nq_lagr.hpp)
+// ==================================================================================================================
+#include "nq_lagr.hpp"
+
+enum { LG_UV = 4 };                        // the composite u + i v, after PT_U .. PT_PHI
+
+// the group-sorted index list: G runs of `order`, run g is offsets[g] .. offsets[g + 1] - 1; null: fine, else what is wrong
+static const char* lg_check_groups(int n, int G, const int* order, const int* offsets) {
+  if (G < 1 || G > 256) return "the number of groups must be 1 to 256";
+  if (!order || !offsets) return "no index list";
+  if (offsets[0] != 0 || offsets[G] != n) return "the offsets must run from 0 to n";
+  for (int g = 0; g < G; ++g)
+    if (offsets[g + 1] < offsets[g]) return "the offsets decrease";
+  for (int i = 0; i < n; ++i)
+    if (order[i] < 0 || order[i] >= n) return "an index of the list is outside [0, n)";
+  return nullptr;
+}
+static const char* lg_check_pairs(int n, int npairs, const int* pi, const int* pj) {
+  if (npairs < 0 || (npairs > 0 && (!pi || !pj))) return "no pair lists";
+  for (int q = 0; q < npairs; ++q)
+    if (pi[q] < 0 || pi[q] >= n || pj[q] < 0 || pj[q] >= n || pi[q] == pj[q]) return "a pair index is outside [0, n), or i = j";
+  return nullptr;
+}
+// columns of the work plane per chunk: a rule of (n, F) alone -- the plane stays within 256 MiB -- or the caller's `chunk`, cut to it
+static int lg_chunk(int n, int F, int chunk) {
+  long long cmax = ((256LL << 20) / ((long long)sizeof(cd) * F)) / 256 * 256;
+  if (cmax < 256) cmax = 256;
+  long long C = chunk > 0 ? chunk : cmax;
+  if (C > cmax) C = cmax;
+  if (C > n) C = n;
+  return (int)C;
+}
+struct LgDev {
+  cd* work;
+  double* win;
+  LgSeries* ser;
+  int *order, *offs, *pairs;
+  double* tab;
+};
+// The spectrum pass on the engine's stream, chunk by chunk: window -> transform along the record axis -> power per group, the
+// chunks' partials added in chunk order.  out: (F, G) host, row p = FFT bin p, the sums over each group times 1 / (2 F sum w^2).
+static int lg_spectrum_run(nq_any* e, const LgDev& d, const LgSeries* ser, int n, int T, int F, const double* window, int demean, int G,
+                           const int* order, const int* offsets, int C, double* out) {
+  double sw2 = 0.0;
+  for (int k = 0; k < T; ++k) sw2 += window[k] * window[k];
+  if (!(sw2 > 0.0)) ANYFAIL(e, -1, "Lagrangian spectrum: the window is zero everywhere");
+  const double scale = 0.5 / ((double)F * sw2);
+  ANYCHK(e, hipMemcpyAsync(d.win, window, sizeof(double) * T, hipMemcpyHostToDevice, e->stream));
+  ANYCHK(e, hipMemcpyAsync(d.ser, ser, sizeof(LgSeries) * T, hipMemcpyHostToDevice, e->stream));
+  ANYCHK(e, hipMemcpyAsync(d.order, order, sizeof(int) * n, hipMemcpyHostToDevice, e->stream));
+  ANYCHK(e, hipMemcpyAsync(d.offs, offsets, sizeof(int) * (G + 1), hipMemcpyHostToDevice, e->stream));
+  for (int c0 = 0; c0 < n; c0 += C) {
+    const int Cw = n - c0 < C ? n - c0 : C;
+    hipLaunchKernelGGL(k_lg_window, dim3((Cw + 255) / 256), dim3(256), 0, e->stream, (const LgSeries*)d.ser, (const int*)d.order, d.work,
+                       (const double*)d.win, c0, Cw, T, F, demean ? 1 : 0);
+    ANYCHK(e, hipGetLastError());
+    const int rc = nq_any_fft(e, d.work, d.work, F, Cw, 0, 0);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_lg_power, dim3(G, F), dim3(256), 0, e->stream, (const cd*)d.work, (const int*)d.offs, c0, Cw, F, G, scale, c0 == 0 ? 1 : 0, d.tab);
+    ANYCHK(e, hipGetLastError());
+  }
+  ANYCHK(e, hipMemcpyAsync(out, d.tab, sizeof(double) * (size_t)F * G, hipMemcpyDeviceToHost, e->stream));
+  return nq_any_sync(e);
+}
+// The dispersion pass on `st`: out (T, G, 6) host sums, outp (T, 5) host sums of the pairs (npairs > 0); returns after the copies
+static hipError_t lg_dispersion_run(hipStream_t st, const LgDev& d, const LgSeries* pos, int n, int T, int G, const int* order, const int* offsets,
+                                    int npairs, const int* pi, const int* pj, double* out, double* outp) {
+  hipError_t r = hipMemcpyAsync(d.ser, pos, sizeof(LgSeries) * T, hipMemcpyHostToDevice, st);
+  if (r == hipSuccess) r = hipMemcpyAsync(d.order, order, sizeof(int) * n, hipMemcpyHostToDevice, st);
+  if (r == hipSuccess) r = hipMemcpyAsync(d.offs, offsets, sizeof(int) * (G + 1), hipMemcpyHostToDevice, st);
+  if (r != hipSuccess) return r;
+  const size_t single = (size_t)T * G * LG_SINGLE_SUMS;
+  hipLaunchKernelGGL(k_lg_disp, dim3(G, T), dim3(256), 0, st, (const LgSeries*)d.ser, (const int*)d.order, (const int*)d.offs, G, d.tab);
+  if ((r = hipGetLastError()) != hipSuccess) return r;
+  if (npairs > 0) {
+    r = hipMemcpyAsync(d.pairs, pi, sizeof(int) * npairs, hipMemcpyHostToDevice, st);
+    if (r == hipSuccess) r = hipMemcpyAsync(d.pairs + npairs, pj, sizeof(int) * npairs, hipMemcpyHostToDevice, st);
+    if (r != hipSuccess) return r;
+    hipLaunchKernelGGL(k_lg_pairs, dim3(T), dim3(256), 0, st, (const LgSeries*)d.ser, (const int*)d.pairs, (const int*)(d.pairs + npairs), npairs, d.tab + single);
+    if ((r = hipGetLastError()) != hipSuccess) return r;
+    r = hipMemcpyAsync(outp, d.tab + single, sizeof(double) * (size_t)T * LG_PAIR_SUMS, hipMemcpyDeviceToHost, st);
+    if (r != hipSuccess) return r;
+  }
+  r = hipMemcpyAsync(out, d.tab, sizeof(double) * single, hipMemcpyDeviceToHost, st);
+  if (r != hipSuccess) return r;
+  return hipStreamSynchronize(st);
+}
+
+// ---- fused contexts: the records are the particles' ring; work memory hangs on NqParticles ----------------------------------
+static int lg_column(const NqParticles* P, int name) {
+  int col = 2;
+  for (int nm : P->names) {
+    if (nm == name) return col;
+    col += nm == PT_PHI ? 2 : 1;
+  }
+  return -1;
+}
+// every buffer holds at least need[b] bytes after this; when one is short they are all given back and allocated again under one
+// mark, so a failure leaves the particles as they were before their first call
+static int lg_reserve(nq_ctx* c, NqParticles* P, const size_t* need, const char* what) {
+  bool enough = true;
+  for (int b = 0; b < NqParticles::LG_NBUF; ++b) enough = enough && P->lg_have[b] >= need[b];
+  if (enough) return 0;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (P->eng) {
+    const int rc = nq_any_sync(P->eng);
+    if (rc) NQ_FAIL(c, rc, "%s: %s", what, nq_any_last_error(P->eng));
+  }
+  size_t want[NqParticles::LG_NBUF];
+  for (int b = 0; b < NqParticles::LG_NBUF; ++b) {
+    want[b] = need[b] > P->lg_have[b] ? need[b] : P->lg_have[b];
+    if (P->lg[b]) c->bytes -= P->release(P->lg[b], (long long)P->lg_have[b]);
+    P->lg[b] = nullptr;
+    P->lg_have[b] = 0;
+  }
+  const DevMark before = P->mark();
+  int rc = 0;
+  for (int b = 0; b < NqParticles::LG_NBUF && !rc; ++b) {
+    if (!want[b]) continue;
+    char* p = nullptr;
+    rc = att_alloc(c, P, &p, want[b], what);
+    if (!rc) {
+      P->lg[b] = p;
+      P->lg_have[b] = want[b];
+    }
+  }
+  if (rc) {
+    c->bytes -= P->rollback(before);
+    for (int b = 0; b < NqParticles::LG_NBUF; ++b) {
+      P->lg[b] = nullptr;
+      P->lg_have[b] = 0;
+    }
+  }
+  return rc;
+}
+static LgDev lg_dev(const NqParticles* P) {
+  LgDev d;
+  d.work = static_cast<cd*>(P->lg[NqParticles::LG_WORK]);
+  d.win = static_cast<double*>(P->lg[NqParticles::LG_WIN]);
+  d.ser = static_cast<LgSeries*>(P->lg[NqParticles::LG_SER]);
+  d.order = static_cast<int*>(P->lg[NqParticles::LG_ORDER]);
+  d.offs = static_cast<int*>(P->lg[NqParticles::LG_OFFS]);
+  d.pairs = static_cast<int*>(P->lg[NqParticles::LG_PAIRS]);
+  d.tab = static_cast<double*>(P->lg[NqParticles::LG_TAB]);
+  return d;
+}
+
+extern "C" {
+
+int nq_lagr_spectrum(nq_ctx* c, int kind, int T, int F, const double* window, int demean, int G, const int* order, const int* offsets, int chunk,
+                     double* out) {
+  NQ_SINGLE_RANK(c, "nq_lagr_spectrum");
+  NqParticles* P = c->pt;
+  if (!P) NQ_FAIL(c, -4, "nq_lagr_spectrum: no particles attached");
+  if (!window || !out) return -1;
+  if (P->rg.every <= 0) NQ_FAIL(c, -1, "nq_lagr_spectrum: the particles were attached with record_every = 0");
+  const int held = (int)P->rg.held();
+  if (held < 2) NQ_FAIL(c, -1, "nq_lagr_spectrum: %d record held (at least 2)", held);
+  if (T != held) NQ_FAIL(c, -1, "nq_lagr_spectrum: a window of %d values, %d records are held", T, held);
+  if (F < T || (F > 8192 && F != 16384)) NQ_FAIL(c, -1, "nq_lagr_spectrum: nfft = %d (from T = %d to 8192, or 16384)", F, T);
+  if (kind < PT_U || kind > LG_UV) NQ_FAIL(c, -1, "nq_lagr_spectrum: name %d (0 u, 1 v, 2 q, 3 phi, 4 u + i v)", kind);
+  const int cre = lg_column(P, kind == LG_UV ? PT_U : kind), cim = kind == LG_UV ? lg_column(P, PT_V) : (kind == PT_PHI ? cre + 1 : -1);
+  if (cre < 0 || (kind == LG_UV && cim < 0)) NQ_FAIL(c, -1, "nq_lagr_spectrum: name %d is not recorded", kind);
+  for (int k = 0; k < T; ++k)
+    if (!std::isfinite(window[k])) NQ_FAIL(c, -1, "nq_lagr_spectrum: the window is not finite at record %d", k);
+  const int n = P->n;
+  if (const char* bad = lg_check_groups(n, G, order, offsets)) NQ_FAIL(c, -1, "nq_lagr_spectrum: %s", bad);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!P->eng) {
+    const int rc = nq_any_create(c->device, &P->eng);
+    if (rc) {
+      P->eng = nullptr;
+      NQ_FAIL(c, rc, "nq_lagr_spectrum: %s", g_last_error.c_str());
+    }
+  }
+  const int C = lg_chunk(n, F, chunk);
+  size_t need[NqParticles::LG_NBUF] = {};
+  need[NqParticles::LG_WORK] = sizeof(cd) * (size_t)F * C;
+  need[NqParticles::LG_WIN] = sizeof(double) * T;
+  need[NqParticles::LG_SER] = sizeof(LgSeries) * T;
+  need[NqParticles::LG_ORDER] = sizeof(int) * (size_t)n;
+  need[NqParticles::LG_OFFS] = sizeof(int) * (G + 1);
+  need[NqParticles::LG_TAB] = sizeof(double) * (size_t)F * G;
+  int rc = lg_reserve(c, P, need, "nq_lagr_spectrum");
+  if (rc) return rc;
+  rc = nq_sync(c);                                  // every record queued on the context's stream is in the ring
+  if (rc) return rc;
+  const size_t rec = (size_t)(2 + P->ncol) * n;
+  std::vector<LgSeries> ser((size_t)T);
+  for (int r = 0; r < T; ++r) {
+    const double* base = P->ring + (size_t)P->rg.oldest(r) * rec;
+    ser[r].re = base + (size_t)cre * n;
+    ser[r].im = cim >= 0 ? base + (size_t)cim * n : nullptr;
+    ser[r].stride = 1;
+  }
+  const long long eng_before = nq_any_device_bytes(P->eng);
+  rc = lg_spectrum_run(P->eng, lg_dev(P), ser.data(), n, T, F, window, demean, G, order, offsets, C, out);
+  const long long grown = nq_any_device_bytes(P->eng) - eng_before;       // the engine's work rows count as the particles'
+  P->bytes += grown;
+  c->bytes += grown;
+  if (rc) NQ_FAIL(c, rc, "nq_lagr_spectrum: %s", nq_any_last_error(P->eng));
+  return 0;
+}
+
+int nq_lagr_dispersion(nq_ctx* c, int T, int G, const int* order, const int* offsets, int npairs, const int* pi, const int* pj, double* out,
+                       double* out_pairs) {
+  NQ_SINGLE_RANK(c, "nq_lagr_dispersion");
+  NqParticles* P = c->pt;
+  if (!P) NQ_FAIL(c, -4, "nq_lagr_dispersion: no particles attached");
+  if (!out || (npairs > 0 && !out_pairs)) return -1;
+  if (P->rg.every <= 0) NQ_FAIL(c, -1, "nq_lagr_dispersion: the particles were attached with record_every = 0");
+  const int held = (int)P->rg.held();
+  if (held < 2) NQ_FAIL(c, -1, "nq_lagr_dispersion: %d record held (at least 2)", held);
+  if (T != held) NQ_FAIL(c, -1, "nq_lagr_dispersion: tables of %d records, %d are held", T, held);
+  const int n = P->n;
+  if (const char* bad = lg_check_groups(n, G, order, offsets)) NQ_FAIL(c, -1, "nq_lagr_dispersion: %s", bad);
+  if (const char* bad = lg_check_pairs(n, npairs, pi, pj)) NQ_FAIL(c, -1, "nq_lagr_dispersion: %s", bad);
+  HIPCHK(c, hipSetDevice(c->device));
+  size_t need[NqParticles::LG_NBUF] = {};
+  need[NqParticles::LG_SER] = sizeof(LgSeries) * T;
+  need[NqParticles::LG_ORDER] = sizeof(int) * (size_t)n;
+  need[NqParticles::LG_OFFS] = sizeof(int) * (G + 1);
+  need[NqParticles::LG_TAB] = sizeof(double) * (size_t)T * ((size_t)G * LG_SINGLE_SUMS + LG_PAIR_SUMS);
+  need[NqParticles::LG_PAIRS] = sizeof(int) * 2 * (size_t)npairs;
+  int rc = lg_reserve(c, P, need, "nq_lagr_dispersion");
+  if (rc) return rc;
+  rc = nq_sync(c);
+  if (rc) return rc;
+  const size_t rec = (size_t)(2 + P->ncol) * n;
+  std::vector<LgSeries> pos((size_t)T);
+  for (int r = 0; r < T; ++r) {
+    const double* base = P->ring + (size_t)P->rg.oldest(r) * rec;
+    pos[r].re = base;
+    pos[r].im = base + n;
+    pos[r].stride = 1;
+  }
+  HIPCHK(c, lg_dispersion_run(c->stream, lg_dev(P), pos.data(), n, T, G, order, offsets, npairs, pi, pj, out, out_pairs));
+  return 0;
+}
+
+// The same passes on engine planes (the any-size path keeps one plane per record and name).  re[r], im[r]: the device address of
+// particle 0's real and imaginary part in record r, oldest first (im NULL: a real series; an entry of a complex plane: the plane's
+// address and that plus 8 bytes); stride: doubles between particles (2 on a complex plane).  The work memory lives for the call.
+int nq_any_lagr_spectrum(nq_any* e, int n, int T, const void* const* re, const void* const* im, int stride, int F, const double* window, int demean,
+                         int G, const int* order, const int* offsets, int chunk, double* out) {
+  if (!e || !re || !window || !out) return -1;
+  if (n < 1 || T < 2 || stride < 1) ANYFAIL(e, -1, "nq_any_lagr_spectrum: n = %d, %d records (at least 2), stride %d", n, T, stride);
+  if (F < T || (F > 8192 && F != 16384)) ANYFAIL(e, -1, "nq_any_lagr_spectrum: nfft = %d (from T = %d to 8192, or 16384)", F, T);
+  for (int k = 0; k < T; ++k) {
+    if (!re[k] || (im && !im[k])) ANYFAIL(e, -1, "nq_any_lagr_spectrum: record %d has no plane", k);
+    if (!std::isfinite(window[k])) ANYFAIL(e, -1, "nq_any_lagr_spectrum: the window is not finite at record %d", k);
+  }
+  if (const char* bad = lg_check_groups(n, G, order, offsets)) ANYFAIL(e, -1, "nq_any_lagr_spectrum: %s", bad);
+  ANYCHK(e, hipSetDevice(e->device));
+  const int C = lg_chunk(n, F, chunk);
+  LgDev d = {};
+  AnyScratch tmp;
+  if (tmp.get(&d.work, (size_t)F * C) != hipSuccess) {
+    (void)hipGetLastError();
+    ANYFAIL(e, -5, "nq_any_lagr_spectrum: cannot allocate %zu bytes of device memory", (size_t)F * C * sizeof(cd));
+  }
+  ANYCHK(e, tmp.get(&d.win, (size_t)T));
+  ANYCHK(e, tmp.get(&d.ser, (size_t)T));
+  ANYCHK(e, tmp.get(&d.order, (size_t)n));
+  ANYCHK(e, tmp.get(&d.offs, (size_t)G + 1));
+  ANYCHK(e, tmp.get(&d.tab, (size_t)F * G));
+  std::vector<LgSeries> ser((size_t)T);
+  for (int r = 0; r < T; ++r) {
+    ser[r].re = static_cast<const double*>(re[r]);
+    ser[r].im = im ? static_cast<const double*>(im[r]) : nullptr;
+    ser[r].stride = stride;
+  }
+  const int rc = lg_spectrum_run(e, d, ser.data(), n, T, F, window, demean, G, order, offsets, C, out);
+  if (rc) (void)hipStreamSynchronize(e->stream);   // the temporaries go back with nothing queued on them
+  return rc;
+}
+
+// pos[r]: the (1, n) complex plane x + i y of record r, oldest first
+int nq_any_lagr_dispersion(nq_any* e, int n, int T, const void* const* pos, int G, const int* order, const int* offsets, int npairs, const int* pi,
+                           const int* pj, double* out, double* out_pairs) {
+  if (!e || !pos || !out || (npairs > 0 && !out_pairs)) return -1;
+  if (n < 1 || T < 2) ANYFAIL(e, -1, "nq_any_lagr_dispersion: n = %d, %d records (at least 2)", n, T);
+  for (int k = 0; k < T; ++k)
+    if (!pos[k]) ANYFAIL(e, -1, "nq_any_lagr_dispersion: record %d has no plane", k);
+  if (const char* bad = lg_check_groups(n, G, order, offsets)) ANYFAIL(e, -1, "nq_any_lagr_dispersion: %s", bad);
+  if (const char* bad = lg_check_pairs(n, npairs, pi, pj)) ANYFAIL(e, -1, "nq_any_lagr_dispersion: %s", bad);
+  ANYCHK(e, hipSetDevice(e->device));
+  LgDev d = {};
+  AnyScratch tmp;
+  ANYCHK(e, tmp.get(&d.ser, (size_t)T));
+  ANYCHK(e, tmp.get(&d.order, (size_t)n));
+  ANYCHK(e, tmp.get(&d.offs, (size_t)G + 1));
+  ANYCHK(e, tmp.get(&d.tab, (size_t)T * ((size_t)G * LG_SINGLE_SUMS + LG_PAIR_SUMS)));
+  if (npairs > 0) ANYCHK(e, tmp.get(&d.pairs, 2 * (size_t)npairs));
+  std::vector<LgSeries> ser((size_t)T);
+  for (int r = 0; r < T; ++r) {
+    ser[r].re = static_cast<const double*>(pos[r]);
+    ser[r].im = ser[r].re + 1;
+    ser[r].stride = 2;
+  }
+  const hipError_t r = lg_dispersion_run(e->stream, d, ser.data(), n, T, G, order, offsets, npairs, pi, pj, out, out_pairs);
+  if (r != hipSuccess) (void)hipStreamSynchronize(e->stream);
+  ANYCHK(e, r);
+  return 0;
 }
 
 }  // extern "C"

@@ -79,26 +79,27 @@ def check(nx, class_id, kmax, every=1, length=256, fields=None):
     return int(kmax), int(every), int(length), tuple(fields)
 
 
-def check_window(window, T):
-    """the window of ``spectrum`` as T float64 values: "boxcar", "hann" (periodic: 0.5 - 0.5 cos(2 pi n / T)) or T finite reals"""
+def check_window(window, T, what="frequency.spectrum"):
+    """the window of ``spectrum`` as T float64 values: "boxcar", "hann" (periodic: 0.5 - 0.5 cos(2 pi n / T)) or T finite reals;
+    ``what``: the prefix of the messages (lagrangian.py checks its windows here too)"""
     if not _integer(T) or T < 2:
-        raise ValueError("frequency.spectrum: %r records held (at least 2)" % (T,))
+        raise ValueError("%s: %r records held (at least 2)" % (what, T))
     if isinstance(window, str):
         if window == "boxcar":
             return np.ones(T)
         if window == "hann":
             return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(T) / T)
-        raise ValueError("frequency.spectrum: window = %r ('boxcar', 'hann' or an array of %d reals)" % (window, T))
+        raise ValueError("%s: window = %r ('boxcar', 'hann' or an array of %d reals)" % (what, window, T))
     try:
         w = np.array(window, np.float64)
     except (TypeError, ValueError):
-        raise ValueError("frequency.spectrum: the window must be 'boxcar', 'hann' or an array of %d reals" % T)
+        raise ValueError("%s: the window must be 'boxcar', 'hann' or an array of %d reals" % (what, T))
     if w.shape != (T,):
-        raise ValueError("frequency.spectrum: the window has shape %s, %d records are held" % (w.shape, T))
+        raise ValueError("%s: the window has shape %s, %d records are held" % (what, w.shape, T))
     if not np.all(np.isfinite(w)):
-        raise ValueError("frequency.spectrum: the window must be finite")
+        raise ValueError("%s: the window must be finite" % what)
     if not np.any(w != 0.0):
-        raise ValueError("frequency.spectrum: the window is zero everywhere")
+        raise ValueError("%s: the window is zero everywhere" % what)
     return np.ascontiguousarray(w)
 
 

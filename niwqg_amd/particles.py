@@ -19,12 +19,15 @@ Values at a particle come from the periodic tensor-product cubic convolution (Ke
 value [j, i] sitting at ((i + 1/2) dx, (j + 1/2) dy).  ``interpolate`` below is the same rule in numpy.  The particles write
 only buffers of their own: every model output is bit-identical to a run without them.
 """
+import ctypes
+
 import numpy as np
 
-from . import _attach
+from . import _attach, _lib
 
 NAMES = ("u", "v", "q", "phi")
 _CODES = dict(u=0, v=1, q=2, phi=3)
+_LAGR_CODES = dict(_CODES, uv=4)                  # nq_lagr_spectrum's names: the columns, and the composite u + i v
 
 
 def _is_qg(m):
@@ -191,6 +194,19 @@ class _Fused(Particles):
         vals = self._split(self.record, [out[:, 2 + c, :] for c in range(out.shape[1] - 2)])
         return steps, out[:, 0, :].copy(), out[:, 1, :].copy(), vals
 
+    # the device passes of lagrangian.py: the library reads its own ring
+    def _held(self):
+        return self.ctx.particles_held()
+
+    def _record_steps(self):
+        return self.ctx.particles_held(steps=True)
+
+    def _lagr_spectrum(self, name, T, F, w, demean, G, order, offsets, chunk):
+        return self.ctx.lagr_spectrum(_LAGR_CODES[name], T, F, w, demean, G, order, offsets, chunk)
+
+    def _lagr_dispersion(self, T, G, order, offsets, pairs):
+        return self.ctx.lagr_dispersion(T, G, order, offsets, pairs)
+
     def _detach(self):
         self.ctx.particles_detach()
 
@@ -281,6 +297,40 @@ class _AnySize(Particles):
             a = np.array([r[1][nm].get().reshape(-1) for r in recs]).reshape(m, self.n)
             vals[nm] = a if nm == "phi" else a.real.copy()
         return steps, pos.real.copy(), pos.imag.copy(), vals
+
+    # the device passes of lagrangian.py on the planes of the held records, oldest first
+    def _held(self):
+        return self.rg.held() if self.ring else 0
+
+    def _held_records(self):
+        return [self.ring[self.rg.oldest(r)] for r in range(self.rg.held())]
+
+    def _record_steps(self):
+        return np.array([self.rg.ring_step[self.rg.oldest(r)] for r in range(self.rg.held())], np.int64)
+
+    def _lagr_spectrum(self, name, T, F, w, demean, G, order, offsets, chunk):
+        e, recs = self.eng, self._held_records()
+        if name == "uv":                          # the real parts of the u and the v plane
+            re, im = [r[1]["u"].ptr for r in recs], [r[1]["v"].ptr for r in recs]
+        else:                                     # a complex plane: phi's imaginary part sits 8 bytes on; the others are real
+            re = [r[1][name].ptr for r in recs]
+            im = [p + 8 for p in re] if name == "phi" else None
+        out = np.empty((F, G))
+        ptrs = ctypes.c_void_p * T
+        e.chk(e.L.nq_any_lagr_spectrum(e.h, self.n, T, ptrs(*re), None if im is None else ptrs(*im), 2, F, _lib._dptr(w), int(demean), G,
+                                       _lib._iptr(order), _lib._iptr(offsets), chunk, _lib._dptr(out)), "nq_any_lagr_spectrum")
+        return out
+
+    def _lagr_dispersion(self, T, G, order, offsets, pairs):
+        e, recs = self.eng, self._held_records()
+        out = np.empty((T, G, 6))
+        npairs = 0 if pairs is None else len(pairs[0])
+        outp = np.empty((T, 5)) if npairs else None
+        e.chk(e.L.nq_any_lagr_dispersion(e.h, self.n, T, (ctypes.c_void_p * T)(*[r[0].ptr for r in recs]), G, _lib._iptr(order),
+                                         _lib._iptr(offsets), npairs, _lib._iptr(pairs[0]) if npairs else None,
+                                         _lib._iptr(pairs[1]) if npairs else None, _lib._dptr(out), _lib._dptr(outp) if npairs else None),
+              "nq_any_lagr_dispersion")
+        return out, outp
 
     def _detach(self):
         self.pos = self.U = self.src = self.U0 = None
