@@ -289,6 +289,29 @@ int nq_particles_get(nq_ctx* ctx, double* x, double* y);
 int nq_particles_sample(nq_ctx* ctx, int nnames, const int* names, double* out);
 int nq_particles_records(nq_ctx* ctx, long long* info4, long long* steps, double* out);
 
+/* Drifter mode, Kernel family only: the particles move through the whole velocity,
+ *   (U + u, v) + a (Re, Im)[phi(x, y, t) e^{-i f0 t}],
+ * a > 0 the amplitude of the vertical mode at the drifters' depth, phi the back-rotated wave field.  The time of step s after
+ * attach is t_s = t0 + s dt, s counted by the particles (not the accumulated float clock: they differ by rounding).  One step
+ * from t = t_s, with Phi0 / Phi1 the physical phi of the state the step starts from and of the state after it (after the
+ * forcing's re-emission), beside U0 / U1:
+ *   k1 = U0(x) + a Phi0(x) e^{-i f0 t},   k2 = (U0 + U1)/2 (x + dt/2 k1) + a (Phi0 + Phi1)/2 (x + dt/2 k1) e^{-i f0 (t + dt/2)},
+ *   k3 likewise at x + dt/2 k2,            k4 = U1(x + dt k3) + a Phi1(x + dt k3) e^{-i f0 (t + dt)},
+ * k complex (x += Re, y += Im; U added to the real part), x += dt/6 (k1 + 2 k2 + 2 k3 + k4): the slow envelope linear in time,
+ * the fast phase exact at the stage times (the three factors are formed on the host in double precision).  One stencil per stage
+ * position serves the U and the phi gathers.  Phi0 is formed again after every call that forms U0 again (nq_set_phi included,
+ * also where it leaves U0's source as it was).  YBJModel: U1 = U0, Phi0 / Phi1 are two planes.
+ * wave: right after nq_particles_attach, before any step; -4 with no particles, on QGModel, after the first step or when the mode
+ * is on already; -1 for a <= 0 or non-finite arguments; two (nx, nx) complex planes more, counted by nq_device_bytes and freed by
+ * detach (-5: none of them stays).
+ * Names NQ_PT_UW, NQ_PT_VW of attach and sample: a Re / Im [phi(x_p) e^{-i f0 t_s}] at the particle, one column each; without
+ * drifter mode a = 1.  Their clock is f0 = nq_params.f, t0 = 0 until nq_particles_wave or nq_particles_clock (same refusals but
+ * the amplitude's; no allocation) sets it; both write the "uw" / "vw" columns of the record taken at attach again.
+ * NQ_LAGR_UVW, NQ_LAGR_UVT: nq_lagr_spectrum's composites uw + i vw and (u + uw) + i (v + vw) (all their columns recorded).    */
+enum { NQ_PT_UW = 5, NQ_PT_VW = 6, NQ_LAGR_UVW = 7, NQ_LAGR_UVT = 8 };
+int nq_particles_wave(nq_ctx* ctx, double amplitude, double f0, double t0);
+int nq_particles_clock(nq_ctx* ctx, double f0, double t0);
+
 /* Lagrangian spectra and dispersion of the particle records, formed on the device, single-rank contexts
  * only (-4 on slab contexts, -4 with no particles attached; -1 with record_every = 0 or fewer than 2 held records).  With the
  * T held records (T must be their number), oldest first, and the particles taken in the order of a group-sorted index list --
@@ -733,6 +756,12 @@ int nq_any_minmax(nq_any* eng, const void* plane, long long elems, int what, dou
 int nq_any_particles_rk4(nq_any* eng, void* pos, int n, const void* U0, const void* U1, int nx, double Lx, double Ly, double U,
                          double dt);
 int nq_any_interp(nq_any* eng, void* out, const void* plane, const void* pos, int n, int nx, double Lx, double Ly);
+/* Drifter mode on engine planes (nq_particles_wave above): the step from time t with P0, P1 the (nx, nx) physical phi planes beside
+ * U0, U1 (amplitude finite and > 0); out[i] = amplitude phi(pos[i]) e^{-i f0 t} */
+int nq_any_particles_rk4_wave(nq_any* eng, void* pos, int n, const void* U0, const void* U1, const void* P0, const void* P1, int nx,
+                              double Lx, double Ly, double U, double dt, double amplitude, double f0, double t);
+int nq_any_interp_wave(nq_any* eng, void* out, const void* phi, const void* pos, int n, int nx, double Lx, double Ly, double amplitude,
+                       double f0, double t);
 /* Stochastic forcing on engine planes (nq_forcing_attach above: the same generator, counters and Hermitian rule):
  * plane += sqrt_dt Re(amp_plane) xi(.; s).  layout 0: (rows, rows/2+1) half spectrum under the q rule; 1: full (rows, rows) plane,
  * independent values of `stream`; 2: full plane, the Hermitian extension of the q rule (columns k > rows/2 take the conjugate of

@@ -461,6 +461,14 @@ class Context:
         self._chk(self.L.nq_particles_attach(self.h, len(x), _dptr(x), _dptr(y), float(Lx), float(Ly), int(record_every),
                                              int(capacity), len(codes), c), "nq_particles_attach")
 
+    def particles_wave(self, amplitude, f0, t0):
+        """drifter mode: right after particles_attach"""
+        self._chk(self.L.nq_particles_wave(self.h, float(amplitude), float(f0), float(t0)), "nq_particles_wave")
+
+    def particles_clock(self, f0, t0):
+        """the clock of the "uw" / "vw" values without drifter mode"""
+        self._chk(self.L.nq_particles_clock(self.h, float(f0), float(t0)), "nq_particles_clock")
+
     def particles_detach(self):
         self._chk(self.L.nq_particles_detach(self.h), "nq_particles_detach")
 

@@ -19,6 +19,8 @@ namespace nq {
 struct LgSeries {
   const double* re;
   const double* im;      // null: a real series
+  const double* re2;     // null, or a second series added to the first (re + re2) + i (im + im2): the sum of two velocities
+  const double* im2;
   long long stride;      // doubles between consecutive particles
 };
 
@@ -35,6 +37,17 @@ __device__ inline double lg_block_sum(double v, double* sh) {
   return ((sh[0] + sh[1]) + sh[2]) + sh[3];
 }
 
+// the value of particle i in one record of a series
+__device__ __forceinline__ double lg_re(const LgSeries& s, size_t i) {
+  const double x = s.re[i * s.stride];
+  return s.re2 ? x + s.re2[i * s.stride] : x;
+}
+__device__ __forceinline__ double lg_im(const LgSeries& s, size_t i) {
+  if (!s.im) return 0.0;
+  const double y = s.im[i * s.stride];
+  return s.im2 ? y + s.im2[i * s.stride] : y;
+}
+
 // work(n, s - c0) = w_n (x_n(i) - mean(i)), i = order[s], s = c0 .. c0 + C - 1, n = 0 .. T-1; rows T .. F-1 are zero.  One
 // thread per entry of the sorted order (consecutive threads, consecutive columns: the writes coalesce); the mean is the sum in
 // record order over T.
@@ -47,8 +60,8 @@ __global__ void __launch_bounds__(256) k_lg_window(const LgSeries* __restrict__ 
   if (demean) {
     for (int n = 0; n < T; ++n) {
       const LgSeries s = ser[n];
-      mx += s.re[i * s.stride];
-      if (s.im) my += s.im[i * s.stride];
+      mx += lg_re(s, i);
+      my += lg_im(s, i);
     }
     mx /= (double)T;
     my /= (double)T;
@@ -56,7 +69,7 @@ __global__ void __launch_bounds__(256) k_lg_window(const LgSeries* __restrict__ 
   for (int n = 0; n < T; ++n) {
     const LgSeries s = ser[n];
     const double w = win[n];
-    const double x = s.re[i * s.stride], y = s.im ? s.im[i * s.stride] : 0.0;
+    const double x = lg_re(s, i), y = lg_im(s, i);
     work[(size_t)n * C + j] = make_double2(w * (x - mx), w * (y - my));
   }
   for (int n = T; n < F; ++n) work[(size_t)n * C + j] = make_double2(0.0, 0.0);

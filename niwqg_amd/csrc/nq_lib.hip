@@ -101,6 +101,12 @@ struct NqParticles : DevOwned {            // Lagrangian particles (section 5g)
   double* qplane = nullptr;                // physical q (PT_Q), allocated when first needed
   cd* phiplane = nullptr;                  // physical phi (PT_PHI), idem
   double* samp = nullptr;                  // nq_particles_sample's output columns (4 x n), idem
+  // drifter mode (section 5s): the particles also move through a phi e^{-i f0 t}
+  bool wave = false;
+  double wa = 1.0, wf0 = 0.0, wt0 = 0.0;   // amplitude; the clock of "uw" / "vw" and of the mode: t_s = wt0 + s dt
+  cd* wphi[2] = {nullptr, nullptr};        // physical phi planes, ping-pong (YBJModel too: phi is not steady): wphi[wcur] is the current state's
+  int wcur = 0;
+  bool w0 = false;                         // wphi[wcur] is phi of the state the next step starts from
   // Lagrangian spectra and dispersion (section 5r): work plane, window, series table, index lists and tables, allocated by the
   // first call and grown when a later call needs more; the transform of the record axis runs on an engine of its own
   enum { LG_WORK = 0, LG_WIN, LG_SER, LG_ORDER, LG_OFFS, LG_TAB, LG_PAIRS, LG_NBUF };
@@ -380,8 +386,11 @@ static int att_fail(nq_ctx* c, A*& slot, int rc) {
 static void attachments_before_step(nq_ctx* c);
 static int attachments_after_step(nq_ctx* c);
 // particles: U0 is formed again from the state the next step starts from
+// -- and, in drifter mode (section 5s), Phi0 from its phi.  Phi0 has a flag of its own: sampling "u" forms U0 alone, and
+// nq_set_phi on CoupledModel changes phi's x-side array while quirk Q2 leaves U0's source as it was.  Every call that may change
+// either between two steps clears both.
 static void pt_mark_stale(nq_ctx* c) {
-  if (c && c->pt) c->pt->u0 = false;
+  if (c && c->pt) c->pt->u0 = c->pt->w0 = false;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3240,7 +3249,9 @@ int nq_get_stage4_max(nq_ctx* c, double* out2) {
 // ends with the inversion of its final state (store_aux), set_q / set_c / nq_invert run do_invert_now, the QGModel scalar tick
 // re-runs do_invert_now after its stale inversion, YBJModel's step writes neither, and a dual-q context inverts the mean of its
 // two copies exactly where ph takes it.  So a velocity plane is ONE row kernel (k_x_get_uv) away at any point between steps.
-enum { PT_U = 0, PT_V = 1, PT_Q = 2, PT_PHI = 3 };
+enum { PT_U = 0, PT_V = 1, PT_Q = 2, PT_PHI = 3, PT_UW = NQ_PT_UW, PT_VW = NQ_PT_VW };
+static bool pt_name_ok(int name) { return (name >= PT_U && name <= PT_PHI) || name == PT_UW || name == PT_VW; }
+static bool pt_name_needs_phi(int name) { return name == PT_PHI || name == PT_UW || name == PT_VW; }
 static PtGrid pt_grid(const nq_ctx* c) {
   PtGrid g;
   g.n = c->N;
@@ -3262,13 +3273,26 @@ static void pt_form_uv(nq_ctx* c, cd* out) {
       hipLaunchKernelGGL((k_x_get_uv<N, false, one>), rows_grid<X>(c->N), dim3(X::THREADS), X::LDS_BYTES, c->stream, c->mU, c->mP, out, c->N, c->tw, c->kk, c->kernel_family ? 1 : 0, comp);
   });
 }
+// the physical phi of the current phi-hat from Mphi on the x side (one row pass), as nq_get_field(NQ_F_PHI) forms it
+static void pt_form_phi(nq_ctx* c, cd* out) { launch_x_c2c(c, true, c->mPhi.xs, out, c->mPhi.pitch, c->N, 1.0); }
 static void pt_before_step(nq_ctx* c) {
   NqParticles* P = c->pt;
   if (!P->u0) {
     pt_form_uv(c, P->uv[P->cur]);
     P->u0 = true;
   }
+  if (P->wave && !P->w0) {
+    pt_form_phi(c, P->wphi[P->wcur]);
+    P->w0 = true;
+  }
 }
+// e^{-i f0 t} = (c, s), formed on the host in double precision
+static void pt_phase(double f0, double t, double* co, double* si) {
+  *co = std::cos(f0 * t);
+  *si = -std::sin(f0 * t);
+}
+// the time of step s after attach, counted by the particles: t_s = t0 + s dt (not the accumulated float clock)
+static double pt_time(const nq_ctx* c) { return c->pt->wt0 + (double)c->pt->rg.steps * c->p.dt; }
 // sample column `name` into o0 (and o1: phi's imaginary part) from the current state; planes allocated on first use
 static int pt_sample_into(nq_ctx* c, int name, double* o0, double* o1) {
   NqParticles* P = c->pt;
@@ -3287,6 +3311,20 @@ static int pt_sample_into(nq_ctx* c, int name, double* o0, double* o1) {
     if (!P->phiplane) { int rc = att_alloc(c, P, &P->phiplane, (size_t)c->N * c->N, "particles"); if (rc) return rc; }
     launch_x_c2c(c, true, c->mPhi.xs, P->phiplane, c->mPhi.pitch, c->N, 1.0);         // as nq_get_field(NQ_F_PHI)
     hipLaunchKernelGGL(k_pt_sample<cd>, dim3(nb), dim3(256), 0, c->stream, (const cd*)P->phiplane, (const double*)P->x, (const double*)P->y, P->n, g, o0, o1);
+  } else if (name == PT_UW || name == PT_VW) {
+    if (!c->kernel_family) NQ_FAIL(c, -4, "particles: QGModel has no wave field (phi)");
+    const cd* phi;
+    if (P->wave) {                            // drifter mode holds the current phi already
+      pt_before_step(c);
+      phi = P->wphi[P->wcur];
+    } else {
+      if (!P->phiplane) { int rc = att_alloc(c, P, &P->phiplane, (size_t)c->N * c->N, "particles"); if (rc) return rc; }
+      pt_form_phi(c, P->phiplane);
+      phi = P->phiplane;
+    }
+    double co, si;
+    pt_phase(P->wf0, pt_time(c), &co, &si);
+    hipLaunchKernelGGL(k_pt_sample_w, dim3(nb), dim3(256), 0, c->stream, phi, (const double*)P->x, (const double*)P->y, P->n, g, P->wa, co, si, name == PT_UW ? o0 : nullptr, name == PT_VW ? o0 : nullptr);
   } else {
     NQ_FAIL(c, -1, "particles: unknown sample name %d", name);
   }
@@ -3317,7 +3355,20 @@ static int pt_after_step(nq_ctx* c) {
     pt_form_uv(c, P->uv[P->cur ^ 1]);
     U1 = P->uv[P->cur ^ 1];
   }
-  hipLaunchKernelGGL(k_pt_rk4, dim3(pt_blocks(P->n)), dim3(256), 0, c->stream, P->x, P->y, P->n, U0, U1, g, c->p.U, c->p.dt);
+  if (P->wave) {                           // Phi1 beside U1; the phases at t_s, t_s + dt/2, t_s + dt
+    pt_form_phi(c, P->wphi[P->wcur ^ 1]);
+    const double t = pt_time(c), dt = c->p.dt;
+    PtWave wv;
+    wv.a = P->wa;
+    pt_phase(P->wf0, t, &wv.c[0], &wv.s[0]);
+    pt_phase(P->wf0, t + 0.5 * dt, &wv.c[1], &wv.s[1]);
+    pt_phase(P->wf0, t + dt, &wv.c[2], &wv.s[2]);
+    hipLaunchKernelGGL(k_pt_rk4_w, dim3(pt_blocks(P->n)), dim3(256), 0, c->stream, P->x, P->y, P->n, U0, U1, (const cd*)P->wphi[P->wcur],
+                       (const cd*)P->wphi[P->wcur ^ 1], g, c->p.U, dt, wv);
+    P->wcur ^= 1;
+  } else {
+    hipLaunchKernelGGL(k_pt_rk4, dim3(pt_blocks(P->n)), dim3(256), 0, c->stream, P->x, P->y, P->n, U0, U1, g, c->p.U, c->p.dt);
+  }
   HIPCHK(c, hipGetLastError());
   if (!c->ybj) P->cur ^= 1;
   return P->rg.tick() ? pt_record(c) : 0;
@@ -3330,11 +3381,11 @@ int nq_particles_attach(nq_ctx* c, int n, const double* x, const double* y, doub
   if (n < 1 || !x || !y) NQ_FAIL(c, -1, "nq_particles_attach: n = %d (>= 1) and both coordinate arrays", n);
   if (!(Lx > 0.0) || !(Ly > 0.0) || !std::isfinite(Lx) || !std::isfinite(Ly)) NQ_FAIL(c, -1, "nq_particles_attach: domain %g x %g", Lx, Ly);
   if (record_every < 0 || (record_every > 0 && capacity < 1)) NQ_FAIL(c, -1, "nq_particles_attach: record_every = %d, capacity = %d", record_every, capacity);
-  if (nnames < 0 || nnames > 4 || (nnames > 0 && !names)) NQ_FAIL(c, -1, "nq_particles_attach: %d record names", nnames);
+  if (nnames < 0 || nnames > 6 || (nnames > 0 && !names)) NQ_FAIL(c, -1, "nq_particles_attach: %d record names", nnames);
   int ncol = 0;
   for (int i = 0; i < nnames; ++i) {
-    if (names[i] < PT_U || names[i] > PT_PHI) NQ_FAIL(c, -1, "nq_particles_attach: record name %d", names[i]);
-    if (names[i] == PT_PHI && !c->kernel_family) NQ_FAIL(c, -1, "nq_particles_attach: QGModel has no wave field (phi)");
+    if (!pt_name_ok(names[i])) NQ_FAIL(c, -1, "nq_particles_attach: record name %d", names[i]);
+    if (pt_name_needs_phi(names[i]) && !c->kernel_family) NQ_FAIL(c, -1, "nq_particles_attach: QGModel has no wave field (phi)");
     ncol += names[i] == PT_PHI ? 2 : 1;
   }
   for (int i = 0; i < n; ++i)
@@ -3348,6 +3399,7 @@ int nq_particles_attach(nq_ctx* c, int n, const double* x, const double* y, doub
   P->rg.init(record_every > 0 ? capacity : 0, record_every);
   P->ncol = ncol;
   P->names.assign(names, names + nnames);
+  P->wf0 = c->p.f;                         // the clock of "uw" / "vw" until nq_particles_clock / nq_particles_wave set it
   const size_t plane = (size_t)c->N * c->N;
   const char* what = "nq_particles_attach";
   int rc = att_alloc(c, P, &P->x, (size_t)n, what);
@@ -3364,6 +3416,66 @@ int nq_particles_attach(nq_ctx* c, int n, const double* x, const double* y, doub
     rc = pt_record(c);
     if (rc) return att_fail(c, c->pt, rc);
   }
+  return nq_sync(c);
+}
+// the "uw" / "vw" columns of the record written at attach, again with the clock (and amplitude) just set
+static int pt_rewrite_wave_columns(nq_ctx* c) {
+  NqParticles* P = c->pt;
+  if (P->rg.every <= 0 || P->rg.count != 1) return 0;
+  const size_t n = (size_t)P->n;
+  double* r = P->ring + (size_t)P->rg.oldest(0) * (2 + P->ncol) * n;
+  int col = 2;
+  for (int name : P->names) {
+    if (name == PT_UW || name == PT_VW) {
+      const int rc = pt_sample_into(c, name, r + col * n, nullptr);
+      if (rc) return rc;
+    }
+    col += name == PT_PHI ? 2 : 1;
+  }
+  return 0;
+}
+static int pt_set_clock(nq_ctx* c, const char* what, double f0, double t0) {
+  if (!c->pt) NQ_FAIL(c, -4, "%s: no particles attached", what);
+  if (!c->kernel_family) NQ_FAIL(c, -4, "%s: QGModel has no wave field (phi)", what);
+  if (!std::isfinite(f0) || !std::isfinite(t0)) NQ_FAIL(c, -1, "%s: f0 = %g, t0 = %g", what, f0, t0);
+  if (c->pt->rg.steps > 0) NQ_FAIL(c, -4, "%s: the particles have moved already (call it right after nq_particles_attach)", what);
+  c->pt->wf0 = f0;
+  c->pt->wt0 = t0;
+  return 0;
+}
+int nq_particles_clock(nq_ctx* c, double f0, double t0) {
+  NQ_SINGLE_RANK(c, "nq_particles_clock");
+  int rc = pt_set_clock(c, "nq_particles_clock", f0, t0);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  rc = pt_rewrite_wave_columns(c);
+  if (rc) return rc;
+  return nq_sync(c);
+}
+int nq_particles_wave(nq_ctx* c, double amplitude, double f0, double t0) {
+  NQ_SINGLE_RANK(c, "nq_particles_wave");
+  NqParticles* P = c->pt;
+  if (!P) NQ_FAIL(c, -4, "nq_particles_wave: no particles attached");
+  if (!c->kernel_family) NQ_FAIL(c, -4, "nq_particles_wave: QGModel has no wave field (phi)");
+  if (!(amplitude > 0.0) || !std::isfinite(amplitude)) NQ_FAIL(c, -1, "nq_particles_wave: amplitude = %g (finite, > 0)", amplitude);
+  if (P->wave) NQ_FAIL(c, -4, "nq_particles_wave: drifter mode is on already");
+  int rc = pt_set_clock(c, "nq_particles_wave", f0, t0);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t plane = (size_t)c->N * c->N;
+  const DevMark before = P->mark();
+  rc = att_alloc(c, P, &P->wphi[0], plane, "nq_particles_wave");
+  if (!rc) rc = att_alloc(c, P, &P->wphi[1], plane, "nq_particles_wave");
+  if (rc) {                                // the particles stay as they were
+    c->bytes -= P->rollback(before);
+    P->wphi[0] = P->wphi[1] = nullptr;
+    return rc;
+  }
+  P->wa = amplitude;
+  P->wave = true;
+  P->w0 = false;
+  rc = pt_rewrite_wave_columns(c);
+  if (rc) return rc;
   return nq_sync(c);
 }
 int nq_particles_detach(nq_ctx* c) {
@@ -3387,8 +3499,8 @@ int nq_particles_sample(nq_ctx* c, int nnames, const int* names, double* out) {
   if (!P) NQ_FAIL(c, -4, "nq_particles_sample: no particles attached");
   if (nnames < 0 || (nnames > 0 && (!names || !out))) return -1;
   for (int i = 0; i < nnames; ++i) {
-    if (names[i] < PT_U || names[i] > PT_PHI) NQ_FAIL(c, -1, "nq_particles_sample: name %d", names[i]);
-    if (names[i] == PT_PHI && !c->kernel_family) NQ_FAIL(c, -1, "nq_particles_sample: QGModel has no wave field (phi)");
+    if (!pt_name_ok(names[i])) NQ_FAIL(c, -1, "nq_particles_sample: name %d", names[i]);
+    if (pt_name_needs_phi(names[i]) && !c->kernel_family) NQ_FAIL(c, -1, "nq_particles_sample: QGModel has no wave field (phi)");
   }
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = (size_t)P->n;
@@ -6124,6 +6236,42 @@ int nq_any_interp(nq_any* e, void* out, const void* plane, const void* pos, int 
   ANYCHK(e, hipGetLastError());
   return 0;
 }
+// Drifter mode on engine planes: the step of nq_particles_wave from time t, P0 / P1 the physical phi of
+// the state the step starts from and of the state after it; and a phi e^{-i f0 t} at the particles.  The phases are formed here,
+// on the host.
+int nq_any_particles_rk4_wave(nq_any* e, void* pos, int n, const void* U0, const void* U1, const void* P0, const void* P1, int nx, double Lx,
+                              double Ly, double Ub, double dt, double amplitude, double f0, double t) {
+  if (!e || !pos || !U0 || !U1 || !P0 || !P1 || n < 1 || nx < 1) return -1;
+  if (!(Lx > 0.0) || !(Ly > 0.0)) ANYFAIL(e, -1, "nq_any_particles_rk4_wave: domain %g x %g", Lx, Ly);
+  if (!(amplitude > 0.0) || !std::isfinite(amplitude) || !std::isfinite(f0) || !std::isfinite(t))
+    ANYFAIL(e, -1, "nq_any_particles_rk4_wave: amplitude = %g (finite, > 0), f0 = %g, t = %g", amplitude, f0, t);
+  ANYCHK(e, hipSetDevice(e->device));
+  const PtGrid g{nx, Lx, Ly, Lx / nx, Ly / nx};
+  PtWave wv;
+  wv.a = amplitude;
+  pt_phase(f0, t, &wv.c[0], &wv.s[0]);
+  pt_phase(f0, t + 0.5 * dt, &wv.c[1], &wv.s[1]);
+  pt_phase(f0, t + dt, &wv.c[2], &wv.s[2]);
+  hipLaunchKernelGGL(k_pt_rk4_wc, dim3(pt_blocks(n)), dim3(256), 0, e->stream, reinterpret_cast<cd*>(pos), n, reinterpret_cast<const cd*>(U0),
+                     reinterpret_cast<const cd*>(U1), reinterpret_cast<const cd*>(P0), reinterpret_cast<const cd*>(P1), g, Ub, dt, wv);
+  ANYCHK(e, hipGetLastError());
+  return 0;
+}
+int nq_any_interp_wave(nq_any* e, void* out, const void* phi, const void* pos, int n, int nx, double Lx, double Ly, double amplitude, double f0,
+                       double t) {
+  if (!e || !out || !phi || !pos || n < 1 || nx < 1) return -1;
+  if (!(Lx > 0.0) || !(Ly > 0.0)) ANYFAIL(e, -1, "nq_any_interp_wave: domain %g x %g", Lx, Ly);
+  if (!std::isfinite(amplitude) || !std::isfinite(f0) || !std::isfinite(t))
+    ANYFAIL(e, -1, "nq_any_interp_wave: amplitude = %g, f0 = %g, t = %g", amplitude, f0, t);
+  ANYCHK(e, hipSetDevice(e->device));
+  const PtGrid g{nx, Lx, Ly, Lx / nx, Ly / nx};
+  double co, si;
+  pt_phase(f0, t, &co, &si);
+  hipLaunchKernelGGL(k_pt_interp_wc, dim3(pt_blocks(n)), dim3(256), 0, e->stream, reinterpret_cast<cd*>(out), reinterpret_cast<const cd*>(phi),
+                     reinterpret_cast<const cd*>(pos), n, g, amplitude, co, si);
+  ANYCHK(e, hipGetLastError());
+  return 0;
+}
 // Stochastic forcing on engine planes: plane += sqrt_dt Re(amp) xi with the generator, counters and
 // Hermitian rule of the fused contexts.  layout 0: (rows, rows/2+1) half spectrum, the q rule; 1: full (rows, rows) plane,
 // independent values of `stream`; 2: full plane, the Hermitian extension of the q rule (the reference's full-plane qh).
@@ -6775,7 +6923,7 @@ int nq_any_freq_spectrum(nq_any* e, const void* ring, int rows, int K, int full,
 // ==================================================================================================================
 #include "nq_lagr.hpp"
 
-enum { LG_UV = 4 };                        // the composite u + i v, after PT_U .. PT_PHI
+enum { LG_UV = 4, LG_UVW = NQ_LAGR_UVW, LG_UVT = NQ_LAGR_UVT };   // the composites u + i v, uw + i vw and (u + uw) + i (v + vw)
 
 // the group-sorted index list: G runs of `order`, run g is offsets[g] .. offsets[g + 1] - 1; null: fine, else what is wrong
 static const char* lg_check_groups(int n, int G, const int* order, const int* offsets) {
@@ -6931,9 +7079,30 @@ int nq_lagr_spectrum(nq_ctx* c, int kind, int T, int F, const double* window, in
   if (held < 2) NQ_FAIL(c, -1, "nq_lagr_spectrum: %d record held (at least 2)", held);
   if (T != held) NQ_FAIL(c, -1, "nq_lagr_spectrum: a window of %d values, %d records are held", T, held);
   if (F < T || (F > 8192 && F != 16384)) NQ_FAIL(c, -1, "nq_lagr_spectrum: nfft = %d (from T = %d to 8192, or 16384)", F, T);
-  if (kind < PT_U || kind > LG_UV) NQ_FAIL(c, -1, "nq_lagr_spectrum: name %d (0 u, 1 v, 2 q, 3 phi, 4 u + i v)", kind);
-  const int cre = lg_column(P, kind == LG_UV ? PT_U : kind), cim = kind == LG_UV ? lg_column(P, PT_V) : (kind == PT_PHI ? cre + 1 : -1);
-  if (cre < 0 || (kind == LG_UV && cim < 0)) NQ_FAIL(c, -1, "nq_lagr_spectrum: name %d is not recorded", kind);
+  if (!(pt_name_ok(kind) || kind == LG_UV || kind == LG_UVW || kind == LG_UVT))
+    NQ_FAIL(c, -1, "nq_lagr_spectrum: name %d (0 u, 1 v, 2 q, 3 phi, 4 u + i v, 5 uw, 6 vw, 7 uw + i vw, 8 (u + uw) + i (v + vw))", kind);
+  // the columns of the series: re + i im, plus re2 + i im2 for the sum of two velocities
+  int cre, cim = -1, cre2 = -1, cim2 = -1;
+  bool have;
+  if (kind == LG_UV || kind == LG_UVT) {
+    cre = lg_column(P, PT_U);
+    cim = lg_column(P, PT_V);
+    have = cre >= 0 && cim >= 0;
+    if (kind == LG_UVT) {
+      cre2 = lg_column(P, PT_UW);
+      cim2 = lg_column(P, PT_VW);
+      have = have && cre2 >= 0 && cim2 >= 0;
+    }
+  } else if (kind == LG_UVW) {
+    cre = lg_column(P, PT_UW);
+    cim = lg_column(P, PT_VW);
+    have = cre >= 0 && cim >= 0;
+  } else {
+    cre = lg_column(P, kind);
+    have = cre >= 0;
+    if (kind == PT_PHI) cim = cre + 1;
+  }
+  if (!have) NQ_FAIL(c, -1, "nq_lagr_spectrum: name %d is not recorded", kind);
   for (int k = 0; k < T; ++k)
     if (!std::isfinite(window[k])) NQ_FAIL(c, -1, "nq_lagr_spectrum: the window is not finite at record %d", k);
   const int n = P->n;
@@ -6964,6 +7133,8 @@ int nq_lagr_spectrum(nq_ctx* c, int kind, int T, int F, const double* window, in
     const double* base = P->ring + (size_t)P->rg.oldest(r) * rec;
     ser[r].re = base + (size_t)cre * n;
     ser[r].im = cim >= 0 ? base + (size_t)cim * n : nullptr;
+    ser[r].re2 = cre2 >= 0 ? base + (size_t)cre2 * n : nullptr;
+    ser[r].im2 = cim2 >= 0 ? base + (size_t)cim2 * n : nullptr;
     ser[r].stride = 1;
   }
   const long long eng_before = nq_any_device_bytes(P->eng);

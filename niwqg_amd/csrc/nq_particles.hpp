@@ -1,5 +1,6 @@
 // Lagrangian particles advected inside the step: the velocity plane of a state, the periodic cubic
-// convolution that interpolates a physical plane at a particle, the RK4 step linear in time, and sampling.
+// convolution that interpolates a physical plane at a particle, the RK4 step linear in time, and sampling; the same step with
+// the near-inertial wave velocity a phi e^{-i f0 t} added (drifter mode, section 5s).
 //
 // Grid value [j, i] of an (n, n) physical plane sits at ((i + 1/2) dx, (j + 1/2) dy) (the reference's _initialize_grid).
 // Interpolation is the tensor product of Keys' cubic convolution kernel (a = -1/2) on the 4 x 4 nearest nodes: exact at the
@@ -140,6 +141,74 @@ __global__ void __launch_bounds__(256) k_pt_rk4_c(cd* __restrict__ pos, int n, c
   }
 }
 
+// ---- drifter mode: the wave velocity a phi e^{-i f0 t} added to (Ub + u, v) -------------------------
+// The amplitude and the phase factors e^{-i f0 t} = (c, s) at the three stage times t, t + dt/2, t + dt of one step; the host
+// forms them in double precision.
+struct PtWave {
+  double a;
+  double c[3], s[3];
+};
+// a (w.x + i w.y) (c + i s)
+__device__ __forceinline__ cd pt_wave_vel(const cd w, double a, double c, double s) {
+  return make_double2(a * (w.x * c - w.y * s), a * (w.x * s + w.y * c));
+}
+// pt_vel with the wave term: ONE stencil per stage position, shared by the U and the phi gathers (two 64-byte segments per
+// stencil row).  The slow envelope is linear in time (the mean of the two interpolated values at the half step), the fast phase
+// exact at the stage time `st` (0: t, 1: t + dt/2, 2: t + dt).
+__device__ __forceinline__ cd pt_vel_w(const cd* __restrict__ U0, const cd* __restrict__ U1, const cd* __restrict__ P0,
+                                       const cd* __restrict__ P1, const PtGrid& g, double x, double y, int st, double Ub,
+                                       const PtWave& wv) {
+  const PtStencil s = pt_stencil(g, x, y);
+  cd v, w;
+  if (st == 0) {
+    v = pt_gather(U0, g, s);
+    w = pt_gather(P0, g, s);
+  } else if (st == 2) {
+    v = pt_gather(U1, g, s);
+    w = pt_gather(P1, g, s);
+  } else {
+    v = pt_gather(U0, g, s);
+    if (U0 != U1) {
+      const cd b = pt_gather(U1, g, s);
+      v = make_double2(0.5 * (v.x + b.x), 0.5 * (v.y + b.y));
+    }
+    const cd p = pt_gather(P0, g, s), q = pt_gather(P1, g, s);
+    w = make_double2(0.5 * (p.x + q.x), 0.5 * (p.y + q.y));
+  }
+  const cd ww = pt_wave_vel(w, wv.a, wv.c[st], wv.s[st]);
+  return make_double2((v.x + Ub) + ww.x, v.y + ww.y);
+}
+__device__ __forceinline__ void pt_rk4_w(const cd* __restrict__ U0, const cd* __restrict__ U1, const cd* __restrict__ P0,
+                                         const cd* __restrict__ P1, const PtGrid& g, double Ub, double dt, const PtWave& wv,
+                                         double& x, double& y) {
+  const double x0 = x, y0 = y, h = 0.5 * dt;
+  const cd k1 = pt_vel_w(U0, U1, P0, P1, g, x0, y0, 0, Ub, wv);
+  const cd k2 = pt_vel_w(U0, U1, P0, P1, g, x0 + h * k1.x, y0 + h * k1.y, 1, Ub, wv);
+  const cd k3 = pt_vel_w(U0, U1, P0, P1, g, x0 + h * k2.x, y0 + h * k2.y, 1, Ub, wv);
+  const cd k4 = pt_vel_w(U0, U1, P0, P1, g, x0 + dt * k3.x, y0 + dt * k3.y, 2, Ub, wv);
+  x = x0 + dt / 6.0 * (k1.x + 2.0 * k2.x + 2.0 * k3.x + k4.x);
+  y = y0 + dt / 6.0 * (k1.y + 2.0 * k2.y + 2.0 * k3.y + k4.y);
+}
+// fused contexts
+__global__ void __launch_bounds__(256) k_pt_rk4_w(double* __restrict__ px, double* __restrict__ py, int n, const cd* U0, const cd* U1,
+                                                  const cd* P0, const cd* P1, PtGrid g, double Ub, double dt, PtWave wv) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    double x = px[i], y = py[i];
+    pt_rk4_w(U0, U1, P0, P1, g, Ub, dt, wv, x, y);
+    px[i] = x;
+    py[i] = y;
+  }
+}
+// any-size engine
+__global__ void __launch_bounds__(256) k_pt_rk4_wc(cd* __restrict__ pos, int n, const cd* U0, const cd* U1, const cd* P0, const cd* P1,
+                                                   PtGrid g, double Ub, double dt, PtWave wv) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    double x = pos[i].x, y = pos[i].y;
+    pt_rk4_w(U0, U1, P0, P1, g, Ub, dt, wv, x, y);
+    pos[i] = make_double2(x, y);
+  }
+}
+
 // values of a physical plane at the particles: T = double (out0), T = cd (out0 = real part, out1 = imaginary part; either may be
 // null)
 template <typename T>
@@ -162,6 +231,19 @@ __global__ void __launch_bounds__(256) k_pt_interp_c(cd* __restrict__ out, const
                                                      int n, PtGrid g) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
     out[i] = pt_gather(plane, g, pt_stencil(g, pos[i].x, pos[i].y));
+}
+// the wave velocity a phi e^{-i f0 t} at the particles ("uw": o0, "vw": o1; either may be null); (c, s) = e^{-i f0 t}
+__global__ void __launch_bounds__(256) k_pt_sample_w(const cd* __restrict__ phi, const double* __restrict__ px,
+                                                     const double* __restrict__ py, int n, PtGrid g, double a, double c, double s,
+                                                     double* o0, double* o1) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    pt_store<cd>(pt_wave_vel(pt_gather(phi, g, pt_stencil(g, px[i], py[i])), a, c, s), o0, o1, i);
+}
+// any-size engine: out[i] = a phi(pos[i]) e^{-i f0 t}
+__global__ void __launch_bounds__(256) k_pt_interp_wc(cd* __restrict__ out, const cd* __restrict__ phi, const cd* __restrict__ pos,
+                                                      int n, PtGrid g, double a, double c, double s) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    out[i] = pt_wave_vel(pt_gather(phi, g, pt_stencil(g, pos[i].x, pos[i].y)), a, c, s);
 }
 
 // the velocity plane (u, v) of the fields the last inversion emitted (Hu = column-transformed -il psi, Hp = psi on the x side):

@@ -17,7 +17,8 @@ With the T >= 2 held records of a series x_n(i) (particle i, record n, oldest fi
 
 F = ``nfft`` >= T (default T; the records are followed by zeros).  The convention is ``frequency.py``'s: a series turning as
 e^{-i omega t} appears at +omega.  By Parseval sum_p P(p, g) is the group mean of 1/2 sum_n w_n^2 |x'_n|^2 / sum_n w_n^2.  Series:
-"q", "u", "v" (real), "phi" (complex), "uv" (u + i v: the rotary spectrum) -- whatever was recorded.
+"q", "u", "v", "uw", "vw" (real), "phi" (complex), "uv" (u + i v: the rotary spectrum) -- whatever was recorded -- and, with the
+wave velocity columns of section 5s, "uvw" (uw + i vw) and "uvt" ((u + uw) + i (v + vw): what a drifter's rotary spectrum shows).
 
     R(k) = mean_i (T - k)^-1 sum_n conj(x'_n(i)) x'_{n+k}(i),  k = 0 .. max_lag        (the unbiased autocovariance)
 
@@ -34,7 +35,9 @@ import numpy as np
 
 from . import frequency
 
-SERIES = ("u", "v", "q", "phi", "uv")             # ids of the library (include/niwqg_amd.h: nq_lagr_spectrum)
+SERIES = ("u", "v", "q", "phi", "uv", "uw", "vw", "uvw", "uvt")       # ids of the library (include/niwqg_amd.h: nq_lagr_spectrum)
+COMPOSITES = {"uv": ("u", "v"), "uvw": ("uw", "vw"), "uvt": ("u", "v", "uw", "vw")}      # the columns a composite is made of
+REAL = ("u", "v", "q", "uw", "vw")
 MAX_GROUPS = 256
 
 
@@ -44,15 +47,17 @@ def _integer(v):
 
 
 def available(record):
-    """series names the recorded columns give: the columns themselves, "uv" first in place of u and v when both are there"""
+    """series names the recorded columns give: the columns themselves, "uv" first in place of u and v when both are there,
+    likewise "uvw" in place of uw and vw, and "uvt" when all four are"""
     record = list(record)
-    if "u" in record and "v" in record:
-        return ["uv"] + [n for n in record if n not in ("u", "v")]
-    return record
+    made = [c for c in ("uv", "uvw", "uvt") if all(n in record for n in COMPOSITES[c])]
+    used = set(n for c in made for n in COMPOSITES[c])
+    return made + [n for n in record if n not in used]
 
 
 def check_names(record, names, what="spectrum"):
-    """``names`` (None: ``available(record)``) as a list, each one a recorded column or "uv" with both u and v recorded"""
+    """``names`` (None: ``available(record)``) as a list, each one a recorded column or a composite ("uv", "uvw", "uvt") with all
+    its columns recorded"""
     if names is None:
         names = available(record)
     names = [names] if isinstance(names, str) else list(names)
@@ -62,6 +67,10 @@ def check_names(record, names, what="spectrum"):
         if n == "uv":
             if "u" not in record or "v" not in record:
                 raise ValueError("lagrangian.%s: 'uv' needs both 'u' and 'v' recorded; recorded: %s" % (what, ", ".join(record) or "nothing"))
+        elif isinstance(n, str) and n in COMPOSITES:
+            if any(c not in record for c in COMPOSITES[n]):
+                raise ValueError("lagrangian.%s: %r needs %s recorded; recorded: %s"
+                                 % (what, n, " and ".join(repr(c) for c in COMPOSITES[n]), ", ".join(record) or "nothing"))
         elif n not in SERIES:
             raise ValueError("lagrangian.%s: unknown name %r; valid names: %s" % (what, n, ", ".join(SERIES)))
         elif n not in record:
@@ -171,7 +180,7 @@ class LagrangianSpectra(object):
 
 
 class Autocovariance(object):
-    """lag (K + 1,) in time units, values (K + 1,) or (K + 1, G): float64 for a real series, complex128 for "phi" and "uv";
+    """lag (K + 1,) in time units, values (K + 1,) or (K + 1, G): float64 for a real series, complex128 for "phi", "uv", "uvw", "uvt";
     counts (G,)"""
 
     def __init__(self, name, lag, values, counts):
@@ -180,7 +189,7 @@ class Autocovariance(object):
     def diffusivity(self):
         """the cumulative trapezoid of Re R over the lag: int_0^tau R for a real series, 1/2 int_0^tau Re R for "uv" (and "phi"),
         so that a velocity's is the single-component diffusivity either way; [0] = 0"""
-        r = np.real(self.values) * (1.0 if self.name in ("u", "v", "q") else 0.5)
+        r = np.real(self.values) * (1.0 if self.name in REAL else 0.5)
         d = np.diff(self.lag)
         d = d.reshape((-1,) + (1,) * (r.ndim - 1))
         out = np.zeros_like(r)
@@ -249,7 +258,7 @@ def autocovariance(P, name, max_lag=None, demean=True, groups=None, chunk=0):
     check_nfft(2 * T, T)
     order, offsets, counts, G = check_groups(groups, P.n, "autocovariance")
     sums = P._lagr_spectrum(name, T, 2 * T, np.ones(T), bool(demean), G, order, offsets, int(chunk))
-    R = _autocov_from_table(sums, counts, T, K, name in ("u", "v", "q"), groups is not None)
+    R = _autocov_from_table(sums, counts, T, K, name in REAL, groups is not None)
     return Autocovariance(name, np.arange(K + 1) * (P.record_every * float(P.m.dt)), R, counts)
 
 
@@ -269,6 +278,11 @@ def _compose(tr, name):
         if "u" not in tr.values or "v" not in tr.values:
             raise ValueError("lagrangian: 'uv' needs both 'u' and 'v' in the trajectory")
         return tr.values["u"] + 1j * tr.values["v"]
+    if isinstance(name, str) and name in COMPOSITES:
+        if any(c not in tr.values for c in COMPOSITES[name]):
+            raise ValueError("lagrangian: %r needs %s in the trajectory" % (name, " and ".join(repr(c) for c in COMPOSITES[name])))
+        v = tr.values
+        return v["uw"] + 1j * v["vw"] if name == "uvw" else (v["u"] + v["uw"]) + 1j * (v["v"] + v["vw"])
     if name not in tr.values:
         raise ValueError("lagrangian: %r is not in the trajectory; it holds: %s" % (name, ", ".join(sorted(tr.values))))
     return np.asarray(tr.values[name])
