@@ -312,6 +312,32 @@ enum { NQ_PT_UW = 5, NQ_PT_VW = 6, NQ_LAGR_UVW = 7, NQ_LAGR_UVT = 8 };
 int nq_particles_wave(nq_ctx* ctx, double amplitude, double f0, double t0);
 int nq_particles_clock(nq_ctx* ctx, double f0, double t0);
 
+/* Ray mode, Kernel family only: each particle is a near-inertial wave packet and also carries a wavevector
+ * (k, l).  With eta = f / kappa^2 (hslash) and zeta = q_psi, the dispersion relation of the YBJ operator,
+ *   omega = (U + u) k + v l + zeta / 2 + (eta / 2) (k^2 + l^2),
+ * gives the rays as Hamilton's equations
+ *   dx/dt = U + u + eta k,   dy/dt = v + eta l,   dk/dt = -(k u_x + l v_x) - zeta_x / 2,   dl/dt = -(k u_y + l v_y) - zeta_y / 2.
+ * After every step of the model one classical RK4 step of the four, with the particles' time treatment: U0 / Z0 the (u, v) and zeta
+ * planes of the state the step starts from, U1 / Z1 of the state after it, the fields linear in time between them (stages at t,
+ * t + dt/2 twice, t + dt).  u, v, zeta come from the Keys interpolant and their gradients from ITS derivative (the same 16 nodes
+ * contracted with w'(t) / dx along one axis): the discrete rays are Hamilton's equations of the interpolated omega exactly.
+ * zeta is q_psi = q - q_w of the state the LAST INVERSION saw: on the host ifft2(-wv2 ph).real + mean(q).  nq_set_phi on
+ * CoupledModel runs no inversion (quirk Q2): until the next one zeta stays what it was, the q_psi that matches the held ph, not
+ * q minus the q_w of the new phi.  YBJModel: psi and q are steady, one zeta plane (formed again after nq_set_q).
+ * rays: right after nq_particles_attach, before any step; -4 with no particles, on QGModel, on a slab context, after the first
+ * step, or with ray or drifter mode on already (the two exclude each other: nq_particles_wave returns -4 once rays are on); -1
+ * for null arrays or a non-finite k, l or eta; two arrays of n doubles and two (nx, nx) planes of doubles more (YBJModel: one),
+ * counted by nq_device_bytes and freed by detach (-5: none of them stays, the particles are as they were).
+ * get_rays: the wavevectors now (-4 without ray mode).
+ * Names of attach and sample, one column each: NQ_PT_K, NQ_PT_L the wavevector; NQ_PT_ZETA zeta at the particle (any mode);
+ * NQ_PT_OMEGA the omega above from the current state at the ray, U included.  Sampling K, L or OMEGA without ray mode: -1.  Attach
+ * accepts them, for the mode is set after it: nq_particles_rays writes those columns of the record taken at attach again; records
+ * taken without the mode hold NaN there.  nq_particles_attach takes up to 10 record names.  nq_lagr_spectrum does not take the
+ * four (-1). */
+enum { NQ_PT_K = 9, NQ_PT_L = 10, NQ_PT_ZETA = 11, NQ_PT_OMEGA = 12 };
+int nq_particles_rays(nq_ctx* ctx, const double* k, const double* l, double eta);
+int nq_particles_get_rays(nq_ctx* ctx, double* k, double* l);
+
 /* Lagrangian spectra and dispersion of the particle records, formed on the device, single-rank contexts
  * only (-4 on slab contexts, -4 with no particles attached; -1 with record_every = 0 or fewer than 2 held records).  With the
  * T held records (T must be their number), oldest first, and the particles taken in the order of a group-sorted index list --
@@ -676,7 +702,8 @@ int nq_event_record(nq_ctx* ctx, int slot);
 int nq_event_elapsed(nq_ctx* ctx, int slot_a, int slot_b, float* elapsed_ms);
 /* Per-kernel timing with HIP events on the context's stream.  While enabled, every launch of the
  * selected kernel class inside nq_step is bracketed by an event pair (cost ~2 us per launch).
- * class: 0 x_products, 1 x_wavepv, 2 s_q, 3 s_phi, 4 s_invert, 5 y_A (all A sub-passes)              */
+ * class: 0 x_products, 1 x_wavepv, 2 s_q, 3 s_phi, 4 s_invert, 5 y_A (all A sub-passes);
+ * 6 the zeta row pass and 7 the ray step of ray mode (nq_particles_rays), read with nq_profile_read           */
 /* best of `reps` timed launches of a 1-read + 1-write stream copy of `bytes` bytes (16 B per lane, grid-stride), in GB/s
  * of bytes moved (read + written): the copy rate of THIS device, bench.py's second roofline denominator */
 int nq_stream_copy_gbs(nq_ctx* ctx, long long bytes, int reps, double* gbs_out);
@@ -762,6 +789,14 @@ int nq_any_particles_rk4_wave(nq_any* eng, void* pos, int n, const void* U0, con
                               double Lx, double Ly, double U, double dt, double amplitude, double f0, double t);
 int nq_any_interp_wave(nq_any* eng, void* out, const void* phi, const void* pos, int n, int nx, double Lx, double Ly, double amplitude,
                        double f0, double t);
+/* Ray mode on engine planes (nq_particles_rays above): one step of the rays pos[i] = x + i y, wv[i] = k + i l; U0, U1 the velocity
+ * planes u + i v and Z0, Z1 complex (nx, nx) planes with zeta in the real part (every engine plane is complex: a real layout
+ * would cost the engine a conversion pass per step), of the state the step starts from and of the state after it (U0 == U1 or
+ * Z0 == Z1: steady).  out[i] = omega at the rays from U, Z (imaginary part 0). */
+int nq_any_particles_rk4_rays(nq_any* eng, void* pos, void* wv, int n, const void* U0, const void* U1, const void* Z0, const void* Z1,
+                              int nx, double Lx, double Ly, double U, double eta, double dt);
+int nq_any_interp_omega(nq_any* eng, void* out, const void* U, const void* Z, const void* pos, const void* wv, int n, int nx, double Lx,
+                        double Ly, double Ub, double eta);
 /* Stochastic forcing on engine planes (nq_forcing_attach above: the same generator, counters and Hermitian rule):
  * plane += sqrt_dt Re(amp_plane) xi(.; s).  layout 0: (rows, rows/2+1) half spectrum under the q rule; 1: full (rows, rows) plane,
  * independent values of `stream`; 2: full plane, the Hermitian extension of the q rule (columns k > rows/2 take the conjugate of

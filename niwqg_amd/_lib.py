@@ -435,6 +435,7 @@ class Context:
         return ms.value
 
     KERNEL_CLASSES = {"x_products": 0, "x_wavepv": 1, "s_q": 2, "s_phi": 3, "s_invert": 4, "y_A": 5}
+    RAY_KERNEL_CLASSES = {"pt_zeta": 6, "pt_rays": 7}       # ray mode's row pass and step: one at a time, profile_read()
 
     def profile_enable(self, kernel_class):
         self._chk(self.L.nq_profile_enable(self.h, int(kernel_class)), "nq_profile_enable")
@@ -468,6 +469,17 @@ class Context:
     def particles_clock(self, f0, t0):
         """the clock of the "uw" / "vw" values without drifter mode"""
         self._chk(self.L.nq_particles_clock(self.h, float(f0), float(t0)), "nq_particles_clock")
+
+    def particles_rays(self, k, l, eta):
+        """ray mode: right after particles_attach"""
+        k = np.ascontiguousarray(k, np.float64)
+        l = np.ascontiguousarray(l, np.float64)
+        self._chk(self.L.nq_particles_rays(self.h, _dptr(k), _dptr(l), float(eta)), "nq_particles_rays")
+
+    def particles_get_rays(self, n):
+        k, l = np.empty(n), np.empty(n)
+        self._chk(self.L.nq_particles_get_rays(self.h, _dptr(k), _dptr(l)), "nq_particles_get_rays")
+        return k, l
 
     def particles_detach(self):
         self._chk(self.L.nq_particles_detach(self.h), "nq_particles_detach")

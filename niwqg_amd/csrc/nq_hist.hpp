@@ -118,8 +118,9 @@ template <int N> constexpr size_t hist_lds_bytes(int words) {
 // or the twiddles after it.
 // The part both k_x_hist and k_x_moments (nq_avg.hpp) run: the loads, the packing and the two transforms of one row block, up to
 // "values in registers": q[t], qpsi[t] and phi[t] of point j + t * T of the thread's row.  On return every wave is through its
-// last exchange: the LDS (the twiddles included) is free.
-template <int N, int MODE, bool SLAB>
+// last exchange: the LDS (the twiddles included) is free.  PHI = false (k_x_get_zeta, nq_particles.hpp): q and q_psi only, the phi row
+// is neither read nor transformed (w returns the transformed (q, q_w) pair).
+template <int N, int MODE, bool SLAB, bool PHI = true>
 __device__ __forceinline__ void x_row_values(const MArr& Mq, const MArr& Mqw, const MArr& Mphi, const cd* __restrict__ tw,
                                              const double* __restrict__ kk, double (&q)[XPlan<N>::P], double (&qpsi)[XPlan<N>::P],
                                              cd (&w)[XPlan<N>::P]) {
@@ -145,13 +146,13 @@ __device__ __forceinline__ void x_row_values(const MArr& Mq, const MArr& Mqw, co
     q[t] = w[t].x;
     qpsi[t] = (MODE == MODE_COUPLED) ? w[t].x - w[t].y : w[t].x;
   }
-  {
+  if constexpr (PHI) {
     const XRowT<SLAB> rp = xrow<SLAB>(Mphi, row);
 #pragma unroll
     for (int t = 0; t < P; ++t) w[t] = *rp.at(j + t * T);
+    NQ_PHASE_FENCE();
+    F::template run<true>(w, j, c, lds, twr);
   }
-  NQ_PHASE_FENCE();
-  F::template run<true>(w, j, c, lds, twr);
   NQ_PHASE_FENCE();
   wg_barrier_all();                                  // every wave is through its last exchange: the LDS is free
 }

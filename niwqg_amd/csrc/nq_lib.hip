@@ -107,6 +107,13 @@ struct NqParticles : DevOwned {            // Lagrangian particles (section 5g)
   cd* wphi[2] = {nullptr, nullptr};        // physical phi planes, ping-pong (YBJModel too: phi is not steady): wphi[wcur] is the current state's
   int wcur = 0;
   bool w0 = false;                         // wphi[wcur] is phi of the state the next step starts from
+  // ray mode (section 5t): each particle carries a wavevector (k, l) through (U + u, v) and zeta = q_psi
+  bool rays = false;
+  double eta = 0.0;                        // f / kappa^2 (hslash)
+  double *k = nullptr, *l = nullptr;
+  double* zeta[2] = {nullptr, nullptr};    // q_psi planes beside uv[0], uv[1] (YBJModel: one, as uv): zeta[cur] is the current state's
+  bool z0 = false;                         // zeta[cur] is q_psi of the state the next step starts from
+  double* zplane = nullptr;                // q_psi for PT_ZETA without ray mode, allocated when first needed
   // Lagrangian spectra and dispersion (section 5r): work plane, window, series table, index lists and tables, allocated by the
   // first call and grown when a later call needs more; the transform of the record axis runs on an engine of its own
   enum { LG_WORK = 0, LG_WIN, LG_SER, LG_ORDER, LG_OFFS, LG_TAB, LG_PAIRS, LG_NBUF };
@@ -388,9 +395,9 @@ static int attachments_after_step(nq_ctx* c);
 // particles: U0 is formed again from the state the next step starts from
 // -- and, in drifter mode (section 5s), Phi0 from its phi.  Phi0 has a flag of its own: sampling "u" forms U0 alone, and
 // nq_set_phi on CoupledModel changes phi's x-side array while quirk Q2 leaves U0's source as it was.  Every call that may change
-// either between two steps clears both.
+// either between two steps clears both -- and the flag of ray mode's zeta plane (section 5t), for the same reason as Phi0's.
 static void pt_mark_stale(nq_ctx* c) {
-  if (c && c->pt) c->pt->u0 = c->pt->w0 = false;
+  if (c && c->pt) c->pt->u0 = c->pt->w0 = c->pt->z0 = false;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1189,7 +1196,8 @@ template <class X>
 static dim3 rows_grid(int rows) { return dim3((rows + X::C - 1) / X::C); }
 
 // per-kernel event profiling ---------------------------------------------------------------------
-enum { PK_PRODUCTS = 0, PK_WAVEPV = 1, PK_SQ = 2, PK_SPHI = 3, PK_INVERT = 4, PK_A = 5 };
+enum { PK_PRODUCTS = 0, PK_WAVEPV = 1, PK_SQ = 2, PK_SPHI = 3, PK_INVERT = 4, PK_A = 5,
+       PK_PT_ZETA = 6, PK_PT_RAYS = 7 };   // ray mode's two kernels (section 5t): read one class at a time (nq_profile_read)
 struct ProfScope {
   nq_ctx* c;
   bool on;
@@ -3249,9 +3257,15 @@ int nq_get_stage4_max(nq_ctx* c, double* out2) {
 // ends with the inversion of its final state (store_aux), set_q / set_c / nq_invert run do_invert_now, the QGModel scalar tick
 // re-runs do_invert_now after its stale inversion, YBJModel's step writes neither, and a dual-q context inverts the mean of its
 // two copies exactly where ph takes it.  So a velocity plane is ONE row kernel (k_x_get_uv) away at any point between steps.
-enum { PT_U = 0, PT_V = 1, PT_Q = 2, PT_PHI = 3, PT_UW = NQ_PT_UW, PT_VW = NQ_PT_VW };
-static bool pt_name_ok(int name) { return (name >= PT_U && name <= PT_PHI) || name == PT_UW || name == PT_VW; }
+enum { PT_U = 0, PT_V = 1, PT_Q = 2, PT_PHI = 3, PT_UW = NQ_PT_UW, PT_VW = NQ_PT_VW, PT_K = NQ_PT_K, PT_L = NQ_PT_L, PT_ZETA = NQ_PT_ZETA,
+       PT_OMEGA = NQ_PT_OMEGA };
+static bool pt_name_of_rays(int name) { return name == PT_K || name == PT_L || name == PT_OMEGA; }   // values only ray mode has
+static bool pt_name_ok(int name) {
+  return (name >= PT_U && name <= PT_PHI) || name == PT_UW || name == PT_VW || name == PT_ZETA || pt_name_of_rays(name);
+}
 static bool pt_name_needs_phi(int name) { return name == PT_PHI || name == PT_UW || name == PT_VW; }
+// q_psi comes from the Kernel family's row pass, and ray mode is the Kernel family's
+static bool pt_name_needs_waves(int name) { return name == PT_ZETA || pt_name_of_rays(name); }
 static PtGrid pt_grid(const nq_ctx* c) {
   PtGrid g;
   g.n = c->N;
@@ -3275,11 +3289,27 @@ static void pt_form_uv(nq_ctx* c, cd* out) {
 }
 // the physical phi of the current phi-hat from Mphi on the x side (one row pass), as nq_get_field(NQ_F_PHI) forms it
 static void pt_form_phi(nq_ctx* c, cd* out) { launch_x_c2c(c, true, c->mPhi.xs, out, c->mPhi.pitch, c->N, 1.0); }
+// q_psi of the state the last inversion saw, from Mq (and Mqw on CoupledModel) on the x side: one row kernel (Kernel family)
+static void pt_form_zeta(nq_ctx* c, double* out) {
+  ProfScope ps(c, PK_PT_ZETA);
+  with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    typedef XPlan<N> X;
+    if (c->p.model == NQ_MODEL_COUPLED)
+      hipLaunchKernelGGL((k_x_get_zeta<N, MODE_COUPLED>), dim3(c->Nloc / X::C), dim3(X::THREADS), X::LDS_BYTES, c->stream, c->mQ, c->mQw, c->twx, c->kk, out);
+    else
+      hipLaunchKernelGGL((k_x_get_zeta<N, MODE_UNCOUPLED>), dim3(c->Nloc / X::C), dim3(X::THREADS), X::LDS_BYTES, c->stream, c->mQ, c->mQw, c->twx, c->kk, out);
+  });
+}
 static void pt_before_step(nq_ctx* c) {
   NqParticles* P = c->pt;
   if (!P->u0) {
     pt_form_uv(c, P->uv[P->cur]);
     P->u0 = true;
+  }
+  if (P->rays && !P->z0) {
+    pt_form_zeta(c, P->zeta[P->cur]);
+    P->z0 = true;
   }
   if (P->wave && !P->w0) {
     pt_form_phi(c, P->wphi[P->wcur]);
@@ -3325,6 +3355,28 @@ static int pt_sample_into(nq_ctx* c, int name, double* o0, double* o1) {
     double co, si;
     pt_phase(P->wf0, pt_time(c), &co, &si);
     hipLaunchKernelGGL(k_pt_sample_w, dim3(nb), dim3(256), 0, c->stream, phi, (const double*)P->x, (const double*)P->y, P->n, g, P->wa, co, si, name == PT_UW ? o0 : nullptr, name == PT_VW ? o0 : nullptr);
+  } else if (name == PT_ZETA) {
+    if (!c->kernel_family) NQ_FAIL(c, -4, "particles: zeta is formed by the row pass of the Kernel family");
+    const double* z;
+    if (P->rays) {                            // ray mode holds the current zeta already
+      pt_before_step(c);
+      z = P->zeta[P->cur];
+    } else {
+      if (!P->zplane) { int rc = att_alloc(c, P, &P->zplane, (size_t)c->N * c->N, "particles"); if (rc) return rc; }
+      pt_form_zeta(c, P->zplane);
+      z = P->zplane;
+    }
+    hipLaunchKernelGGL(k_pt_sample<double>, dim3(nb), dim3(256), 0, c->stream, z, (const double*)P->x, (const double*)P->y, P->n, g, o0, nullptr);
+  } else if (pt_name_of_rays(name)) {
+    if (!P->rays) {                           // a column recorded without the mode (nq_particles_sample refuses): NaN, every bit set
+      HIPCHK(c, hipMemsetAsync(o0, 0xff, sizeof(double) * (size_t)P->n, c->stream));
+    } else if (name == PT_OMEGA) {
+      pt_before_step(c);
+      hipLaunchKernelGGL(k_pt_omega, dim3(nb), dim3(256), 0, c->stream, (const cd*)P->uv[P->cur], (const double*)P->zeta[P->cur], (const double*)P->x,
+                         (const double*)P->y, (const double*)P->k, (const double*)P->l, P->n, g, c->p.U, P->eta, o0);
+    } else {
+      HIPCHK(c, hipMemcpyAsync(o0, name == PT_K ? P->k : P->l, sizeof(double) * (size_t)P->n, hipMemcpyDeviceToDevice, c->stream));
+    }
   } else {
     NQ_FAIL(c, -1, "particles: unknown sample name %d", name);
   }
@@ -3366,6 +3418,11 @@ static int pt_after_step(nq_ctx* c) {
     hipLaunchKernelGGL(k_pt_rk4_w, dim3(pt_blocks(P->n)), dim3(256), 0, c->stream, P->x, P->y, P->n, U0, U1, (const cd*)P->wphi[P->wcur],
                        (const cd*)P->wphi[P->wcur ^ 1], g, c->p.U, dt, wv);
     P->wcur ^= 1;
+  } else if (P->rays) {                    // zeta1 beside U1 (YBJModel: q is steady as psi is, one plane)
+    if (!c->ybj) pt_form_zeta(c, P->zeta[P->cur ^ 1]);
+    ProfScope ps(c, PK_PT_RAYS);
+    hipLaunchKernelGGL(k_pt_rk4_r, dim3(pt_blocks(P->n)), dim3(256), 0, c->stream, P->x, P->y, P->k, P->l, P->n, U0, U1, (const double*)P->zeta[P->cur],
+                       (const double*)P->zeta[c->ybj ? P->cur : P->cur ^ 1], g, c->p.U, P->eta, c->p.dt);
   } else {
     hipLaunchKernelGGL(k_pt_rk4, dim3(pt_blocks(P->n)), dim3(256), 0, c->stream, P->x, P->y, P->n, U0, U1, g, c->p.U, c->p.dt);
   }
@@ -3381,11 +3438,12 @@ int nq_particles_attach(nq_ctx* c, int n, const double* x, const double* y, doub
   if (n < 1 || !x || !y) NQ_FAIL(c, -1, "nq_particles_attach: n = %d (>= 1) and both coordinate arrays", n);
   if (!(Lx > 0.0) || !(Ly > 0.0) || !std::isfinite(Lx) || !std::isfinite(Ly)) NQ_FAIL(c, -1, "nq_particles_attach: domain %g x %g", Lx, Ly);
   if (record_every < 0 || (record_every > 0 && capacity < 1)) NQ_FAIL(c, -1, "nq_particles_attach: record_every = %d, capacity = %d", record_every, capacity);
-  if (nnames < 0 || nnames > 6 || (nnames > 0 && !names)) NQ_FAIL(c, -1, "nq_particles_attach: %d record names", nnames);
+  if (nnames < 0 || nnames > 10 || (nnames > 0 && !names)) NQ_FAIL(c, -1, "nq_particles_attach: %d record names", nnames);
   int ncol = 0;
   for (int i = 0; i < nnames; ++i) {
     if (!pt_name_ok(names[i])) NQ_FAIL(c, -1, "nq_particles_attach: record name %d", names[i]);
     if (pt_name_needs_phi(names[i]) && !c->kernel_family) NQ_FAIL(c, -1, "nq_particles_attach: QGModel has no wave field (phi)");
+    if (pt_name_needs_waves(names[i]) && !c->kernel_family) NQ_FAIL(c, -1, "nq_particles_attach: record name %d is the Kernel family's (zeta, rays)", names[i]);
     ncol += names[i] == PT_PHI ? 2 : 1;
   }
   for (int i = 0; i < n; ++i)
@@ -3418,15 +3476,16 @@ int nq_particles_attach(nq_ctx* c, int n, const double* x, const double* y, doub
   }
   return nq_sync(c);
 }
-// the "uw" / "vw" columns of the record written at attach, again with the clock (and amplitude) just set
-static int pt_rewrite_wave_columns(nq_ctx* c) {
+// the "uw" / "vw" columns of the record written at attach, again with the clock (and amplitude) just set; rays: the "k", "l"
+// and "omega" columns instead, with the mode just set
+static int pt_rewrite_wave_columns(nq_ctx* c, bool rays = false) {
   NqParticles* P = c->pt;
   if (P->rg.every <= 0 || P->rg.count != 1) return 0;
   const size_t n = (size_t)P->n;
   double* r = P->ring + (size_t)P->rg.oldest(0) * (2 + P->ncol) * n;
   int col = 2;
   for (int name : P->names) {
-    if (name == PT_UW || name == PT_VW) {
+    if (rays ? pt_name_of_rays(name) : (name == PT_UW || name == PT_VW)) {
       const int rc = pt_sample_into(c, name, r + col * n, nullptr);
       if (rc) return rc;
     }
@@ -3459,6 +3518,7 @@ int nq_particles_wave(nq_ctx* c, double amplitude, double f0, double t0) {
   if (!c->kernel_family) NQ_FAIL(c, -4, "nq_particles_wave: QGModel has no wave field (phi)");
   if (!(amplitude > 0.0) || !std::isfinite(amplitude)) NQ_FAIL(c, -1, "nq_particles_wave: amplitude = %g (finite, > 0)", amplitude);
   if (P->wave) NQ_FAIL(c, -4, "nq_particles_wave: drifter mode is on already");
+  if (P->rays) NQ_FAIL(c, -4, "nq_particles_wave: ray mode is on (the two modes exclude each other)");
   int rc = pt_set_clock(c, "nq_particles_wave", f0, t0);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
@@ -3476,6 +3536,52 @@ int nq_particles_wave(nq_ctx* c, double amplitude, double f0, double t0) {
   P->w0 = false;
   rc = pt_rewrite_wave_columns(c);
   if (rc) return rc;
+  return nq_sync(c);
+}
+// ray mode
+int nq_particles_rays(nq_ctx* c, const double* k, const double* l, double eta) {
+  NQ_SINGLE_RANK(c, "nq_particles_rays");
+  NqParticles* P = c->pt;
+  if (!P) NQ_FAIL(c, -4, "nq_particles_rays: no particles attached");
+  if (!c->kernel_family) NQ_FAIL(c, -4, "nq_particles_rays: QGModel has no near-inertial waves");
+  if (P->rays) NQ_FAIL(c, -4, "nq_particles_rays: ray mode is on already");
+  if (P->wave) NQ_FAIL(c, -4, "nq_particles_rays: drifter mode is on (the two modes exclude each other)");
+  if (P->rg.steps > 0) NQ_FAIL(c, -4, "nq_particles_rays: the particles have moved already (call it right after nq_particles_attach)");
+  if (!k || !l) NQ_FAIL(c, -1, "nq_particles_rays: both wavevector arrays");
+  if (!std::isfinite(eta)) NQ_FAIL(c, -1, "nq_particles_rays: eta = %g", eta);
+  for (int i = 0; i < P->n; ++i)
+    if (!std::isfinite(k[i]) || !std::isfinite(l[i])) NQ_FAIL(c, -1, "nq_particles_rays: ray %d has a non-finite wavevector", i);
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t plane = (size_t)c->N * c->N, n = (size_t)P->n;
+  const DevMark before = P->mark();
+  const char* what = "nq_particles_rays";
+  int rc = att_alloc(c, P, &P->k, n, what);
+  if (!rc) rc = att_alloc(c, P, &P->l, n, what);
+  if (!rc) rc = att_alloc(c, P, &P->zeta[0], plane, what);
+  if (!rc && !c->ybj) rc = att_alloc(c, P, &P->zeta[1], plane, what);
+  if (rc) {                                // the particles stay as they were
+    c->bytes -= P->rollback(before);
+    P->k = P->l = P->zeta[0] = P->zeta[1] = nullptr;
+    return rc;
+  }
+  if (c->ybj) P->zeta[1] = P->zeta[0];
+  HIPCHK(c, hipMemcpyAsync(P->k, k, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(P->l, l, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+  P->eta = eta;
+  P->rays = true;
+  P->z0 = false;
+  rc = pt_rewrite_wave_columns(c, true);
+  if (rc) return rc;
+  return nq_sync(c);
+}
+int nq_particles_get_rays(nq_ctx* c, double* k, double* l) {
+  NQ_SINGLE_RANK(c, "nq_particles_get_rays");
+  if (!c->pt) NQ_FAIL(c, -4, "nq_particles_get_rays: no particles attached");
+  if (!c->pt->rays) NQ_FAIL(c, -4, "nq_particles_get_rays: ray mode is off");
+  if (!k || !l) return -1;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(k, c->pt->k, sizeof(double) * c->pt->n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(l, c->pt->l, sizeof(double) * c->pt->n, hipMemcpyDeviceToHost, c->stream));
   return nq_sync(c);
 }
 int nq_particles_detach(nq_ctx* c) {
@@ -3501,6 +3607,8 @@ int nq_particles_sample(nq_ctx* c, int nnames, const int* names, double* out) {
   for (int i = 0; i < nnames; ++i) {
     if (!pt_name_ok(names[i])) NQ_FAIL(c, -1, "nq_particles_sample: name %d", names[i]);
     if (pt_name_needs_phi(names[i]) && !c->kernel_family) NQ_FAIL(c, -1, "nq_particles_sample: QGModel has no wave field (phi)");
+    if (pt_name_needs_waves(names[i]) && !c->kernel_family) NQ_FAIL(c, -1, "nq_particles_sample: name %d is the Kernel family's (zeta, rays)", names[i]);
+    if (pt_name_of_rays(names[i]) && !P->rays) NQ_FAIL(c, -1, "nq_particles_sample: name %d needs ray mode (nq_particles_rays)", names[i]);
   }
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = (size_t)P->n;
@@ -6272,6 +6380,33 @@ int nq_any_interp_wave(nq_any* e, void* out, const void* phi, const void* pos, i
   ANYCHK(e, hipGetLastError());
   return 0;
 }
+// Ray mode on engine planes: the step of nq_particles_rays, wv = k + i l beside pos = x + i y, Z0 / Z1
+// complex planes with zeta in the real part (every engine plane is complex); and omega at the rays.
+int nq_any_particles_rk4_rays(nq_any* e, void* pos, void* wv, int n, const void* U0, const void* U1, const void* Z0, const void* Z1, int nx,
+                              double Lx, double Ly, double Ub, double eta, double dt) {
+  if (!e || !pos || !wv || !U0 || !U1 || !Z0 || !Z1 || n < 1 || nx < 1) return -1;
+  if (!(Lx > 0.0) || !(Ly > 0.0)) ANYFAIL(e, -1, "nq_any_particles_rk4_rays: domain %g x %g", Lx, Ly);
+  if (!std::isfinite(eta)) ANYFAIL(e, -1, "nq_any_particles_rk4_rays: eta = %g", eta);
+  ANYCHK(e, hipSetDevice(e->device));
+  const PtGrid g{nx, Lx, Ly, Lx / nx, Ly / nx};
+  hipLaunchKernelGGL(k_pt_rk4_rc, dim3(pt_blocks(n)), dim3(256), 0, e->stream, reinterpret_cast<cd*>(pos), reinterpret_cast<cd*>(wv), n,
+                     reinterpret_cast<const cd*>(U0), reinterpret_cast<const cd*>(U1), reinterpret_cast<const cd*>(Z0),
+                     reinterpret_cast<const cd*>(Z1), g, Ub, eta, dt);
+  ANYCHK(e, hipGetLastError());
+  return 0;
+}
+int nq_any_interp_omega(nq_any* e, void* out, const void* U, const void* Z, const void* pos, const void* wv, int n, int nx, double Lx, double Ly,
+                        double Ub, double eta) {
+  if (!e || !out || !U || !Z || !pos || !wv || n < 1 || nx < 1) return -1;
+  if (!(Lx > 0.0) || !(Ly > 0.0)) ANYFAIL(e, -1, "nq_any_interp_omega: domain %g x %g", Lx, Ly);
+  if (!std::isfinite(eta)) ANYFAIL(e, -1, "nq_any_interp_omega: eta = %g", eta);
+  ANYCHK(e, hipSetDevice(e->device));
+  const PtGrid g{nx, Lx, Ly, Lx / nx, Ly / nx};
+  hipLaunchKernelGGL(k_pt_omega_c, dim3(pt_blocks(n)), dim3(256), 0, e->stream, reinterpret_cast<cd*>(out), reinterpret_cast<const cd*>(U),
+                     reinterpret_cast<const cd*>(Z), reinterpret_cast<const cd*>(pos), reinterpret_cast<const cd*>(wv), n, g, Ub, eta);
+  ANYCHK(e, hipGetLastError());
+  return 0;
+}
 // Stochastic forcing on engine planes: plane += sqrt_dt Re(amp) xi with the generator, counters and
 // Hermitian rule of the fused contexts.  layout 0: (rows, rows/2+1) half spectrum, the q rule; 1: full (rows, rows) plane,
 // independent values of `stream`; 2: full plane, the Hermitian extension of the q rule (the reference's full-plane qh).
@@ -7079,7 +7214,7 @@ int nq_lagr_spectrum(nq_ctx* c, int kind, int T, int F, const double* window, in
   if (held < 2) NQ_FAIL(c, -1, "nq_lagr_spectrum: %d record held (at least 2)", held);
   if (T != held) NQ_FAIL(c, -1, "nq_lagr_spectrum: a window of %d values, %d records are held", T, held);
   if (F < T || (F > 8192 && F != 16384)) NQ_FAIL(c, -1, "nq_lagr_spectrum: nfft = %d (from T = %d to 8192, or 16384)", F, T);
-  if (!(pt_name_ok(kind) || kind == LG_UV || kind == LG_UVW || kind == LG_UVT))
+  if (!(pt_name_ok(kind) || kind == LG_UV || kind == LG_UVW || kind == LG_UVT) || kind == PT_ZETA || pt_name_of_rays(kind))
     NQ_FAIL(c, -1, "nq_lagr_spectrum: name %d (0 u, 1 v, 2 q, 3 phi, 4 u + i v, 5 uw, 6 vw, 7 uw + i vw, 8 (u + uw) + i (v + vw))", kind);
   // the columns of the series: re + i im, plus re2 + i im2 for the sum of two velocities
   int cre, cim = -1, cre2 = -1, cim2 = -1;

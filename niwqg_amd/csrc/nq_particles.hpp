@@ -1,6 +1,7 @@
 // Lagrangian particles advected inside the step: the velocity plane of a state, the periodic cubic
 // convolution that interpolates a physical plane at a particle, the RK4 step linear in time, and sampling; the same step with
-// the near-inertial wave velocity a phi e^{-i f0 t} added (drifter mode, section 5s).
+// the near-inertial wave velocity a phi e^{-i f0 t} added (drifter mode, section 5s); and the rays of near-inertial wave packets,
+// each particle carrying a wavevector through the flow and its vorticity zeta (ray mode, section 5t).
 //
 // Grid value [j, i] of an (n, n) physical plane sits at ((i + 1/2) dx, (j + 1/2) dy) (the reference's _initialize_grid).
 // Interpolation is the tensor product of Keys' cubic convolution kernel (a = -1/2) on the 4 x 4 nearest nodes: exact at the
@@ -8,7 +9,7 @@
 // arithmetic after the cast, so no input -- NaN and +-inf included -- addresses outside the plane.  A non-finite coordinate
 // gives NaN without any load (its indices and weights are zeroed and pt_gather returns before reading the plane).
 #pragma once
-#include "nq_step.hpp"
+#include "nq_hist.hpp"
 
 namespace nq {
 
@@ -209,6 +210,207 @@ __global__ void __launch_bounds__(256) k_pt_rk4_wc(cd* __restrict__ pos, int n, 
   }
 }
 
+// ---- ray mode: near-inertial wave packets traced through the flow -----------------------------------------
+// A packet at (x, y) with wavevector (k, l) follows Hamilton's equations of
+//   omega = (Ub + u) k + v l + zeta / 2 + (eta / 2) (k^2 + l^2),        eta = f / kappa^2, zeta = q_psi:
+//   dx/dt = Ub + u + eta k                    dy/dt = v + eta l
+//   dk/dt = -(k u_x + l v_x) - zeta_x / 2     dl/dt = -(k u_y + l v_y) - zeta_y / 2
+// u, v, zeta AND their gradients come from the one interpolant: the derivative of the tensor-product Keys interpolant is the
+// contraction of the same 16 nodes with the derivative weights w'(t) / d along one axis, so the discrete system is Hamilton's
+// of the interpolated omega exactly.
+// d/dt of pt_keys' weights
+__device__ __forceinline__ void pt_keys_d(double t, double w[4]) {
+  w[0] = (-1.5 * t + 2.0) * t - 0.5;
+  w[1] = (4.5 * t - 5.0) * t;
+  w[2] = (-4.5 * t + 4.0) * t + 0.5;
+  w[3] = (1.5 * t - 1.0) * t;
+}
+// pt_axis with the derivative weights dw = w'(t) / d beside w
+__device__ __forceinline__ bool pt_axis_d(double x, double L, double d, int n, int idx[4], double w[4], double dw[4]) {
+  if (!isfinite(x)) {
+#pragma unroll
+    for (int o = 0; o < 4; ++o) { idx[o] = 0; w[o] = 0.0; dw[o] = 0.0; }
+    return false;
+  }
+  double r = fmod(x, L);
+  if (r < 0.0) r += L;
+  if (r >= L) r -= L;
+  const double s = r / d - 0.5;
+  double f = floor(s);
+  if (!(f >= -1.0 && f <= (double)n)) f = 0.0;
+  const int i0 = (int)f;
+  pt_keys(s - f, w);
+  pt_keys_d(s - f, dw);
+#pragma unroll
+  for (int o = 0; o < 4; ++o) {
+    dw[o] /= d;
+    int m = (i0 - 1 + o) % n;
+    if (m < 0) m += n;
+    idx[o] = m;
+  }
+  return true;
+}
+struct PtStencilD {
+  int ix[4], iy[4];
+  double wx[4], wy[4], dwx[4], dwy[4];
+  bool ok;
+};
+__device__ __forceinline__ PtStencilD pt_stencil_d(const PtGrid& g, double x, double y) {
+  PtStencilD s;
+  const bool okx = pt_axis_d(x, g.Lx, g.dx, g.n, s.ix, s.wx, s.dwx);
+  const bool oky = pt_axis_d(y, g.Ly, g.dy, g.n, s.iy, s.wy, s.dwy);
+  s.ok = okx && oky;
+  return s;
+}
+// value, d/dx and d/dy of the interpolant: the three contractions w (x) w, w' (x) w, w (x) w' of the 16 loaded nodes; per row the
+// sums over i with wx and with dwx first, then over j (the numpy restatement follows this order)
+template <typename T>
+struct PtJet {
+  T f, fx, fy;
+};
+template <typename T>
+__device__ __forceinline__ PtJet<T> pt_gather_d(const T* __restrict__ plane, const PtGrid& g, const PtStencilD& s) {
+  PtJet<T> a;
+  if (!s.ok) {
+    pt_nan(a.f);
+    pt_nan(a.fx);
+    pt_nan(a.fy);
+    return a;
+  }
+  pt_zero(a.f);
+  pt_zero(a.fx);
+  pt_zero(a.fy);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const T* row = plane + (size_t)s.iy[j] * g.n;
+    T r, rd;
+    pt_zero(r);
+    pt_zero(rd);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const T v = row[s.ix[i]];
+      pt_madd(r, s.wx[i], v);
+      pt_madd(rd, s.dwx[i], v);
+    }
+    pt_madd(a.f, s.wy[j], r);
+    pt_madd(a.fx, s.wy[j], rd);
+    pt_madd(a.fy, s.dwy[j], r);
+  }
+  return a;
+}
+__device__ __forceinline__ double pt_mean(double a, double b) { return 0.5 * (a + b); }
+__device__ __forceinline__ cd pt_mean(cd a, cd b) { return make_double2(0.5 * (a.x + b.x), 0.5 * (a.y + b.y)); }
+template <typename T>
+__device__ __forceinline__ PtJet<T> pt_mean(const PtJet<T>& a, const PtJet<T>& b) {
+  PtJet<T> m;
+  m.f = pt_mean(a.f, b.f);
+  m.fx = pt_mean(a.fx, b.fx);
+  m.fy = pt_mean(a.fy, b.fy);
+  return m;
+}
+// the jet of plane 0 (st == 0), of plane 1 (st == 2) or the mean of the two (st == 1: the half step, fields linear in time);
+// A0 == A1: a steady plane, one gather
+template <typename T>
+__device__ __forceinline__ PtJet<T> pt_jet_at(const T* __restrict__ A0, const T* __restrict__ A1, const PtGrid& g, const PtStencilD& s,
+                                              int st) {
+  if (st == 0 || A0 == A1) return pt_gather_d(A0, g, s);
+  if (st == 2) return pt_gather_d(A1, g, s);
+  return pt_mean(pt_gather_d(A0, g, s), pt_gather_d(A1, g, s));
+}
+// zeta planes are real (fused contexts) or complex with zeta in the real part (engine planes)
+__device__ __forceinline__ double pt_re(double a) { return a; }
+__device__ __forceinline__ double pt_re(cd a) { return a.x; }
+
+struct PtRay {
+  double x, y, k, l;
+};
+// the right-hand side of the four ray equations at one stage: ONE stencil serves every gather
+template <typename Z>
+__device__ __forceinline__ PtRay pt_ray_rhs(const cd* __restrict__ U0, const cd* __restrict__ U1, const Z* __restrict__ Z0,
+                                            const Z* __restrict__ Z1, const PtGrid& g, const PtRay& p, int st, double Ub, double eta) {
+  const PtStencilD s = pt_stencil_d(g, p.x, p.y);
+  const PtJet<cd> U = pt_jet_at(U0, U1, g, s, st);
+  const PtJet<Z> z = pt_jet_at(Z0, Z1, g, s, st);
+  PtRay d;
+  d.x = (U.f.x + Ub) + eta * p.k;
+  d.y = U.f.y + eta * p.l;
+  d.k = -(p.k * U.fx.x + p.l * U.fx.y) - 0.5 * pt_re(z.fx);
+  d.l = -(p.k * U.fy.x + p.l * U.fy.y) - 0.5 * pt_re(z.fy);
+  return d;
+}
+__device__ __forceinline__ PtRay pt_ray_at(const PtRay& p, double h, const PtRay& d) {
+  PtRay q;
+  q.x = p.x + h * d.x;
+  q.y = p.y + h * d.y;
+  q.k = p.k + h * d.k;
+  q.l = p.l + h * d.l;
+  return q;
+}
+__device__ __forceinline__ double pt_rk4_sum(double a, double dt, double k1, double k2, double k3, double k4) {
+  return a + dt / 6.0 * (k1 + 2.0 * k2 + 2.0 * k3 + k4);
+}
+// one classical RK4 step of a ray, the time treatment of pt_rk4: stages at t, t + dt/2, t + dt/2, t + dt
+template <typename Z>
+__device__ __forceinline__ void pt_rk4_ray(const cd* __restrict__ U0, const cd* __restrict__ U1, const Z* __restrict__ Z0,
+                                           const Z* __restrict__ Z1, const PtGrid& g, double Ub, double eta, double dt, PtRay& p) {
+  const double h = 0.5 * dt;
+  const PtRay k1 = pt_ray_rhs(U0, U1, Z0, Z1, g, p, 0, Ub, eta);
+  const PtRay k2 = pt_ray_rhs(U0, U1, Z0, Z1, g, pt_ray_at(p, h, k1), 1, Ub, eta);
+  const PtRay k3 = pt_ray_rhs(U0, U1, Z0, Z1, g, pt_ray_at(p, h, k2), 1, Ub, eta);
+  const PtRay k4 = pt_ray_rhs(U0, U1, Z0, Z1, g, pt_ray_at(p, dt, k3), 2, Ub, eta);
+  p.x = pt_rk4_sum(p.x, dt, k1.x, k2.x, k3.x, k4.x);
+  p.y = pt_rk4_sum(p.y, dt, k1.y, k2.y, k3.y, k4.y);
+  p.k = pt_rk4_sum(p.k, dt, k1.k, k2.k, k3.k, k4.k);
+  p.l = pt_rk4_sum(p.l, dt, k1.l, k2.l, k3.l, k4.l);
+}
+// fused contexts: positions and wavevectors in four arrays, zeta in real planes
+__global__ void __launch_bounds__(256) k_pt_rk4_r(double* __restrict__ px, double* __restrict__ py, double* __restrict__ pk,
+                                                  double* __restrict__ pl, int n, const cd* U0, const cd* U1, const double* Z0,
+                                                  const double* Z1, PtGrid g, double Ub, double eta, double dt) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    PtRay p = {px[i], py[i], pk[i], pl[i]};
+    pt_rk4_ray(U0, U1, Z0, Z1, g, Ub, eta, dt, p);
+    px[i] = p.x;
+    py[i] = p.y;
+    pk[i] = p.k;
+    pl[i] = p.l;
+  }
+}
+// any-size engine: pos = x + i y and wv = k + i l, zeta in the real part of complex planes (every engine plane is complex)
+__global__ void __launch_bounds__(256) k_pt_rk4_rc(cd* __restrict__ pos, cd* __restrict__ wv, int n, const cd* U0, const cd* U1,
+                                                   const cd* Z0, const cd* Z1, PtGrid g, double Ub, double eta, double dt) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    PtRay p = {pos[i].x, pos[i].y, wv[i].x, wv[i].y};
+    pt_rk4_ray(U0, U1, Z0, Z1, g, Ub, eta, dt, p);
+    pos[i] = make_double2(p.x, p.y);
+    wv[i] = make_double2(p.k, p.l);
+  }
+}
+// omega at the rays from the current state: (Ub + u) k + v l + zeta / 2 + (eta / 2) (k^2 + l^2), in this order of operations
+__device__ __forceinline__ double pt_omega(double u, double v, double zeta, double k, double l, double Ub, double eta) {
+  return (((u + Ub) * k + v * l) + 0.5 * zeta) + 0.5 * eta * (k * k + l * l);
+}
+__global__ void __launch_bounds__(256) k_pt_omega(const cd* __restrict__ U, const double* __restrict__ Z, const double* __restrict__ px,
+                                                  const double* __restrict__ py, const double* __restrict__ pk,
+                                                  const double* __restrict__ pl, int n, PtGrid g, double Ub, double eta,
+                                                  double* __restrict__ out) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const PtStencil s = pt_stencil(g, px[i], py[i]);
+    const cd uv = pt_gather(U, g, s);
+    out[i] = pt_omega(uv.x, uv.y, pt_gather(Z, g, s), pk[i], pl[i], Ub, eta);
+  }
+}
+// any-size engine: out[i] = omega + 0 i from pos, wv, the velocity plane and the zeta plane (real part)
+__global__ void __launch_bounds__(256) k_pt_omega_c(cd* __restrict__ out, const cd* __restrict__ U, const cd* __restrict__ Z,
+                                                    const cd* __restrict__ pos, const cd* __restrict__ wv, int n, PtGrid g, double Ub,
+                                                    double eta) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const PtStencil s = pt_stencil(g, pos[i].x, pos[i].y);
+    const cd uv = pt_gather(U, g, s);
+    out[i] = make_double2(pt_omega(uv.x, uv.y, pt_gather(Z, g, s).x, wv[i].x, wv[i].y, Ub, eta), 0.0);
+  }
+}
+
 // values of a physical plane at the particles: T = double (out0), T = cd (out0 = real part, out1 = imaginary part; either may be
 // null)
 template <typename T>
@@ -297,6 +499,23 @@ k_x_get_uv(MArr hu, MArr hp, cd* __restrict__ rows, int nrows, const cd* __restr
       else rows[at] = make_double2(u[ONE ? 0 : t], r[t].x);
     }
   }
+}
+
+// the zeta plane of ray mode (section 5t): q_psi of the state the last inversion saw, as x_row_values forms it from the (q, q_w)
+// mixed-space rows (q - q_w on CoupledModel, q elsewhere), stored as an (N, N) plane of doubles.  One row block per workgroup, the
+// grid of k_x_hist.
+template <int N, int MODE, bool SLAB = false>
+__global__ void __launch_bounds__(XPlan<N>::THREADS, XPlan<N>::MIN_WAVES)
+k_x_get_zeta(MArr Mq, MArr Mqw, const cd* __restrict__ tw, const double* __restrict__ kk, double* __restrict__ zeta) {
+  typedef XPlan<N> X;
+  constexpr int P = X::P, T = X::T;
+  double q[P], qpsi[P];
+  cd w[P];
+  x_row_values<N, MODE, SLAB, false>(Mq, Mqw, Mq, tw, kk, q, qpsi, w);
+  const int j = threadIdx.x % T, c = threadIdx.x / T;
+  double* __restrict__ out = zeta + ((size_t)blockIdx.x * X::C + c) * N + j;           // point t of the thread: out + t * T
+#pragma unroll
+  for (int t = 0; t < P; ++t) out[t * T] = qpsi[t];
 }
 
 }  // namespace nq

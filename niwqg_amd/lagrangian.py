@@ -48,11 +48,12 @@ def _integer(v):
 
 def available(record):
     """series names the recorded columns give: the columns themselves, "uv" first in place of u and v when both are there,
-    likewise "uvw" in place of uw and vw, and "uvt" when all four are"""
+    likewise "uvw" in place of uw and vw, and "uvt" when all four are; the columns of ray mode ("k", "l", "zeta", "omega":
+    particles.py) are no series here"""
     record = list(record)
     made = [c for c in ("uv", "uvw", "uvt") if all(n in record for n in COMPOSITES[c])]
     used = set(n for c in made for n in COMPOSITES[c])
-    return made + [n for n in record if n not in used]
+    return made + [n for n in record if n not in used and n in SERIES]
 
 
 def check_names(record, names, what="spectrum"):

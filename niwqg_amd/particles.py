@@ -1,7 +1,7 @@
 """Lagrangian particles advected on the device inside the step.
 
     from niwqg_amd import particles
-    P = particles.attach(m, x, y, record_every=0, capacity=1024, record=(), wave=None)
+    P = particles.attach(m, x, y, record_every=0, capacity=1024, record=(), wave=None, rays=None, eta=None)
     m.run()                                   # the particles move inside every step, batched or not
     x, y = P.positions()                      # unwrapped coordinates
     s = P.sample(("u", "v", "q", "phi"))      # {name: array(n)} at the current positions, from the current state
@@ -44,6 +44,22 @@ above.  ``rk4_wave`` below is one such step in numpy, in the kernel's operation 
 
 ``"uw"``, ``"vw"`` in ``record=`` and ``sample()`` (Kernel family): a Re / Im [phi(x_p) e^{-i f0 t_s}] at the particle, the wave
 velocity a drifter at that depth feels; without drifter mode a = 1.
+
+Ray mode: ``attach(..., rays=(k0, l0), eta=None)``, two arrays of n finite wavenumbers -- every particle
+is a near-inertial wave packet and carries its wavevector.  With eta = f / kappa^2 (default ``m.hslash``) and zeta = q_psi, the
+YBJ operator of this package has omega = (m.U + u) k + v l + zeta/2 + (eta/2)(k^2 + l^2), and the rays are its Hamilton's equations
+
+    dx/dt = m.U + u + eta k     dy/dt = v + eta l     dk/dt = -(k u_x + l v_x) - zeta_x/2     dl/dt = -(k u_y + l v_y) - zeta_y/2
+
+advanced by one classical RK4 step after every model step, with the time treatment of the particles (U0, Z0 at the start, U1, Z1
+after the step, linear in between).  u, v, zeta and their gradients come from ONE interpolant: the gradients are the analytic
+derivative of the Keys interpolant (``keys_dweights``), so the discrete rays are Hamilton's equations of the interpolated omega
+exactly; on a steady flow its drift measures the time stepping alone (second order at best: w'' jumps at cell faces).  zeta is
+q_psi = q - q_w of the state the last inversion saw, ``ifft2(-wv2 * m.ph).real + m.q.mean()``; a bare ``set_phi`` on CoupledModel
+(quirk Q2) inverts nothing and leaves zeta, like U0, what it was.  ``rays`` and ``wave`` exclude each other; QGModel raises
+ValueError, slab-decomposed models NotImplementedError.  ``P.wavevectors()`` returns (k, l); ``"k"``, ``"l"``, ``"omega"`` (ray mode)
+and ``"zeta"`` (any mode) are names of ``record=`` and ``sample()``.  ``rk4_rays`` is one step in numpy, ``ray_omega`` the omega.
+``rays=None`` is the step of the first paragraph, bit for bit.
 """
 import ctypes
 
@@ -53,9 +69,12 @@ from . import _attach, _lib
 
 FIELDS = ("u", "v", "q", "phi")                                          # the fields of the state
 NAMES = FIELDS + ("uw", "vw")                                            # and the wave velocity at the particle (section 5s)
+RAY_NAMES = ("zeta", "k", "l", "omega")                                  # q_psi at the particle; the ray's own (section 5t)
+_NEED_RAYS = ("k", "l", "omega")                                         # names only ray mode has
 _CODES = dict(u=0, v=1, q=2, phi=3, uw=_lib.PT_UW, vw=_lib.PT_VW)        # the new codes: include/niwqg_amd.h
 # nq_lagr_spectrum's names: the columns, and the composites u + i v, uw + i vw, (u + uw) + i (v + vw)
 _LAGR_CODES = dict(_CODES, uv=4, uvw=_lib.LAGR_UVW, uvt=_lib.LAGR_UVT)
+_CODES.update(k=_lib.PT_K, l=_lib.PT_L, zeta=_lib.PT_ZETA, omega=_lib.PT_OMEGA)
 
 
 def _is_qg(m):
@@ -63,21 +82,26 @@ def _is_qg(m):
     return isinstance(m, QG)
 
 
-def available(m, wave=False):
+def available(m, wave=False, rays=False):
     """names ``record`` and ``sample`` accept for this model: the fields of the state ("phi": the Kernel family only), which
-    ``sample()`` returns by default, and with ``wave=True`` also the wave velocity columns "uw", "vw" (Kernel family only)"""
+    ``sample()`` returns by default, with ``wave=True`` also the wave velocity columns "uw", "vw" and with ``rays=True`` "zeta" and
+    the ray's "k", "l", "omega" (Kernel family only; the last three in ray mode)"""
     if _is_qg(m):
         return ["u", "v", "q"]
-    return list(NAMES) if wave else list(FIELDS)
+    return (list(NAMES) if wave else list(FIELDS)) + (list(RAY_NAMES) if rays else [])
 
 
-def _names(m, names, what):
+def _names(m, names, what, rays=True):
+    """the names as a list, checked; rays=False: the particles are not in ray mode"""
     names = [names] if isinstance(names, str) else list(names)
-    valid = available(m, wave=True)
+    valid = available(m, wave=True, rays=True)
     bad = [n for n in names if n not in valid]
     if bad:
         raise ValueError("particles.%s: %s not available for %s; valid names: %s"
                          % (what, ", ".join(map(repr, bad)), type(m).__name__, ", ".join(valid)))
+    bad = [n for n in names if n in _NEED_RAYS and not rays]
+    if bad:
+        raise ValueError("particles.%s: %s need ray mode (attach(..., rays=(k0, l0)))" % (what, ", ".join(map(repr, bad))))
     return names
 
 
@@ -186,6 +210,102 @@ def rk4_wave(x, y, U0, U1, P0, P1, Ub, a, f0, t, dt, L):
     return (x + dt / 6.0 * (k1[0] + 2.0 * k2[0] + 2.0 * k3[0] + k4[0]), y + dt / 6.0 * (k1[1] + 2.0 * k2[1] + 2.0 * k3[1] + k4[1]))
 
 
+# ---- ray mode in numpy (section 5t): the kernels' restatement, in their order of sums ---------------------------------------
+def keys_dweights(t):
+    """d/dt of ``keys_weights``: the derivative weights of the nodes at offsets -1, 0, 1, 2 (they sum to 0; sum o_i w'_i = 1)"""
+    t = np.asarray(t, np.float64)
+    return ((-1.5 * t + 2.0) * t - 0.5, (4.5 * t - 5.0) * t, (-4.5 * t + 4.0) * t + 0.5, (1.5 * t - 1.0) * t)
+
+
+def _axis_d(x, L, n):
+    """_axis with the derivative weights w'(t) / d beside the weights"""
+    x = np.asarray(x, np.float64)
+    ok = np.isfinite(x)
+    xs = np.where(ok, x, 0.0)
+    r = np.fmod(xs, L)
+    r = np.where(r < 0, r + L, r)
+    r = np.where(r >= L, r - L, r)
+    d = L / n
+    s = r / d - 0.5
+    f = np.floor(s)
+    i0 = f.astype(np.int64)
+    w = keys_weights(s - f)
+    dw = [v / d for v in keys_dweights(s - f)]
+    idx = [np.mod(i0 - 1 + o, n) for o in range(4)]
+    return ok, idx, w, dw
+
+
+def interpolate_d(plane, x, y, L, W=None):
+    """(f, df/dx, df/dy) of the Keys interpolant of plane (n, n) at the points (x, y): the three contractions of the 16 nodes with
+    w (x) w, w' (x) w and w (x) w', the row sums first (the order of pt_gather_d); NaN for non-finite points"""
+    plane = np.asarray(plane)
+    n = plane.shape[0]
+    W = L if W is None else W
+    okx, ix, wx, dwx = _axis_d(x, L, n)
+    oky, iy, wy, dwy = _axis_d(y, W, n)
+    f = np.zeros(np.shape(x), plane.dtype)
+    fx, fy = f.copy(), f.copy()
+    for j in range(4):
+        r = np.zeros(np.shape(x), plane.dtype)
+        rd = r.copy()
+        for i in range(4):
+            v = plane[iy[j], ix[i]]
+            r = r + wx[i] * v
+            rd = rd + dwx[i] * v
+        f = f + wy[j] * r
+        fx = fx + wy[j] * rd
+        fy = fy + dwy[j] * r
+    ok = okx & oky
+    return np.where(ok, f, np.nan), np.where(ok, fx, np.nan), np.where(ok, fy, np.nan)
+
+
+def ray_omega(u, v, zeta, k, l, Ub, eta):
+    """omega = (Ub + u) k + v l + zeta/2 + (eta/2)(k^2 + l^2) of values at the rays, in the operation order of the kernel (what
+    "omega" records, from the "u", "v", "zeta", "k", "l" of the same record)"""
+    u, v, zeta, k, l = (np.asarray(a, np.float64) for a in (u, v, zeta, k, l))
+    return (((u + Ub) * k + v * l) + 0.5 * zeta) + 0.5 * eta * (k * k + l * l)
+
+
+def ray_omega_at(x, y, k, l, U, Z, Ub, eta, L):
+    """``ray_omega`` with u, v, zeta interpolated from the velocity plane U (u + i v, or the pair (u, v)) and the zeta plane Z"""
+    uv = interpolate(_uv_plane(U), x, y, L)
+    return ray_omega(uv.real, uv.imag, interpolate(np.asarray(Z, np.float64), x, y, L), k, l, Ub, eta)
+
+
+def rk4_rays(x, y, k, l, U0, U1, Z0, Z1, Ub, eta, dt, L):
+    """One step of the rays from t to t + dt in numpy, in the operation order of the kernel (k_pt_rk4_r): U0, U1 the velocity planes
+    u + i v (or pairs (u, v)) and Z0, Z1 the zeta planes of the state the step starts from and of the state after it (``U0 is U1``,
+    ``Z0 is Z1``: steady, one gather per stage); returns the new (x, y, k, l)."""
+    A0, A1 = _uv_plane(U0), _uv_plane(U1)
+    B0, B1 = np.asarray(Z0, np.float64), np.asarray(Z1, np.float64)
+    steady_u, steady_z = U0 is U1, Z0 is Z1
+
+    def jet(P0, P1, steady, px, py, st):
+        if st == 0 or steady:
+            return interpolate_d(P0, px, py, L)
+        if st == 2:
+            return interpolate_d(P1, px, py, L)
+        a, b = interpolate_d(P0, px, py, L), interpolate_d(P1, px, py, L)
+        return tuple(0.5 * (p + q) for p, q in zip(a, b))
+
+    def rhs(p, st):
+        px, py, pk, pl = p
+        U, Ux, Uy = jet(A0, A1, steady_u, px, py, st)
+        _, zx, zy = jet(B0, B1, steady_z, px, py, st)
+        return ((U.real + Ub) + eta * pk, U.imag + eta * pl,
+                -(pk * Ux.real + pl * Ux.imag) - 0.5 * zx, -(pk * Uy.real + pl * Uy.imag) - 0.5 * zy)
+
+    def at(p, h, d):
+        return tuple(a + h * b for a, b in zip(p, d))
+    p = tuple(np.asarray(a, np.float64) for a in (x, y, k, l))
+    h = 0.5 * dt
+    k1 = rhs(p, 0)
+    k2 = rhs(at(p, h, k1), 1)
+    k3 = rhs(at(p, h, k2), 1)
+    k4 = rhs(at(p, dt, k3), 2)
+    return tuple(a + dt / 6.0 * (d1 + 2.0 * d2 + 2.0 * d3 + d4) for a, d1, d2, d3, d4 in zip(p, k1, k2, k3, k4))
+
+
 # ---- the public object -------------------------------------------------------------------------------------------------
 class Trajectory(object):
     """records oldest first: step (T,), t (T,), x, y (T, n), values {name: (T, n)}"""
@@ -204,11 +324,19 @@ class Particles(_attach.Attachment):
     NO_SLAB = ("particles.attach: slab-decomposed models have no particles yet (they need the interpolation "
                "partials exchanged between the ranks at every stage; DESIGN.md section 7)")
 
-    def __init__(self, m, n, record_every, capacity, record, wave=None):
+    def __init__(self, m, n, record_every, capacity, record, wave=None, rays=None, eta=None):
         self.m, self.n = m, n
         self.record_every, self.capacity, self.record = record_every, capacity, tuple(record)
         self.tc0, self.t0 = m.tc, m.t
         self.wave = wave                          # drifter mode: the amplitude a, or None
+        self.rays, self.eta = rays is not None, eta       # ray mode: on or off, and eta = f / kappa^2 (None when off)
+
+    def wavevectors(self):
+        """(k, l): the wavevectors of the rays now (host copies; ray mode)"""
+        self._check()
+        if not self.rays:
+            raise RuntimeError("particles.wavevectors: attached without rays=")
+        return self._wavevectors()
 
     def wave_time(self, step):
         """t_s = t0 + s dt of step s after attach: the clock of the wave phase, counted by the particles"""
@@ -223,7 +351,7 @@ class Particles(_attach.Attachment):
         """{name: array(n)} at the current positions from the current state ("phi": complex); names: a subset of
         available(m) (default: all of them)"""
         self._check()
-        names = available(self.m) if names is None else _names(self.m, names, "sample")
+        names = available(self.m) if names is None else _names(self.m, names, "sample", self.rays)
         return self._sample(names)
 
     def _times(self, offsets):
@@ -261,8 +389,8 @@ class Particles(_attach.Attachment):
 class _Fused(Particles):
     """fused contexts: positions, velocity planes and records live in the library (nq_particles_*)"""
 
-    def __init__(self, m, x, y, record_every, capacity, record, wave=None):
-        Particles.__init__(self, m, len(x), record_every, capacity, record, wave)
+    def __init__(self, m, x, y, record_every, capacity, record, wave=None, rays=None, eta=None):
+        Particles.__init__(self, m, len(x), record_every, capacity, record, wave, rays, eta)
         self.ctx = m._ctx
         self.ctx.particles_attach(x, y, m.L, m.W, record_every, capacity, [_CODES[r] for r in record])
         if _is_qg(m):
@@ -272,12 +400,17 @@ class _Fused(Particles):
                 self.ctx.particles_clock(m.f, m.t)
             else:
                 self.ctx.particles_wave(wave, m.f, m.t)
+            if rays is not None:
+                self.ctx.particles_rays(rays[0], rays[1], eta)
         except Exception:
             self.ctx.particles_detach()
             raise
 
     def _positions(self):
         return self.ctx.particles_get(self.n)
+
+    def _wavevectors(self):
+        return self.ctx.particles_get_rays(self.n)
 
     def _sample(self, names):
         ncols = sum(2 if nm == "phi" else 1 for nm in names)
@@ -309,12 +442,14 @@ class _AnySize(Particles):
     """any-size path: positions (x + i y), velocity planes (u + i v) and records are engine planes; the model's _step_etdrk4 calls
     _before_step / _after_step (nq_any_particles_rk4); U0, U1 are formed from m.ph with the Plane operations"""
 
-    def __init__(self, m, x, y, record_every, capacity, record, wave=None):
+    def __init__(self, m, x, y, record_every, capacity, record, wave=None, rays=None, eta=None):
         from ._anysize import Plane
-        Particles.__init__(self, m, len(x), record_every, capacity, record, wave)
+        Particles.__init__(self, m, len(x), record_every, capacity, record, wave, rays, eta)
         self.eng = m._eng
         self.pos = self.eng.plane((x + 1j * y).reshape(1, -1), real=False)
         self.U, self.src = None, None       # velocity plane of the state src (the psi-hat Plane it was formed from)
+        self.Z, self.zsrc = None, None      # zeta plane (real part), likewise
+        self.wv = self.eng.plane((rays[0] + 1j * rays[1]).reshape(1, -1), real=False) if self.rays else None
         self.rg = _attach.Ring(capacity if record_every > 0 else 0, record_every)
         self.ring = [None] * self.rg.cap
         self._Plane = Plane
@@ -335,6 +470,21 @@ class _AnySize(Particles):
         if self.U is None or self.src is not self.m._d["ph"]:
             self.U, self.src = self._velocity()
         return self.U
+
+    def _current_Z(self):
+        """q_psi of the state the last inversion saw: Re ifft2(-wv2 ph) + mean(q), formed again when ph is another Plane"""
+        m = self.m
+        d = m._d
+        if self.Z is None or self.zsrc is not d["ph"]:
+            self.Z, self.zsrc = m._ifft(m._K["mwv2"] * d["ph"]).real + d["q"].mean(), d["ph"]
+        return self.Z
+
+    def _interp_omega(self):
+        e, m = self.eng, self.m
+        out = self._Plane(e, (1, self.n))
+        e.chk(e.L.nq_any_interp_omega(e.h, out.ptr, self._current_U().ptr, self._current_Z().ptr, self.pos.ptr, self.wv.ptr, self.n, m.nx,
+                                      float(m.L), float(m.W), float(m.U), self.eta), "nq_any_interp_omega")
+        return out
 
     def _interp(self, plane):
         e = self.eng
@@ -361,6 +511,12 @@ class _AnySize(Particles):
             elif nm in ("uw", "vw"):
                 w = self._interp_wave()
                 out[nm] = w.real if nm == "uw" else w.imag
+            elif nm == "zeta":
+                out[nm] = self._interp(self._current_Z())
+            elif nm in ("k", "l"):
+                out[nm] = self.wv.real if nm == "k" else self.wv.imag
+            elif nm == "omega":
+                out[nm] = self._interp_omega()
             else:
                 out[nm] = self._interp(d[nm])
         return out
@@ -375,11 +531,17 @@ class _AnySize(Particles):
         self.U0 = self._current_U()
         if self.wave is not None:
             self.P0 = self.m._d["phi"]            # the Plane of the state the step starts from (the step puts a new one in its place)
+        if self.rays:
+            self.Z0 = self._current_Z()
 
     def _after_step(self):
         e, m = self.eng, self.m
         U1 = self._current_U()
-        if self.wave is None:
+        if self.rays:
+            e.chk(e.L.nq_any_particles_rk4_rays(e.h, self.pos.ptr, self.wv.ptr, self.n, self.U0.ptr, U1.ptr, self.Z0.ptr, self._current_Z().ptr,
+                                                m.nx, float(m.L), float(m.W), float(m.U), self.eta, float(m.dt)), "nq_any_particles_rk4_rays")
+            self.Z0 = None
+        elif self.wave is None:
             e.chk(e.L.nq_any_particles_rk4(e.h, self.pos.ptr, self.n, self.U0.ptr, U1.ptr, m.nx, float(m.L), float(m.W), float(m.U),
                                            float(m.dt)), "nq_any_particles_rk4")
         else:
@@ -394,6 +556,10 @@ class _AnySize(Particles):
     def _positions(self):
         p = self.pos.get().reshape(-1)
         return p.real.copy(), p.imag.copy()
+
+    def _wavevectors(self):
+        w = self.wv.get().reshape(-1)
+        return w.real.copy(), w.imag.copy()
 
     def _sample(self, names):
         pl = self._planes(names)
@@ -453,7 +619,7 @@ class _AnySize(Particles):
         return out, outp
 
     def _detach(self):
-        self.pos = self.U = self.src = self.U0 = self.P0 = None
+        self.pos = self.U = self.src = self.U0 = self.P0 = self.Z = self.zsrc = self.Z0 = self.wv = None
         self.ring = []
         self.eng.sync()
 
@@ -472,19 +638,46 @@ def _wave(m, wave):
     return a
 
 
-def attach(m, x, y, record_every=0, capacity=1024, record=(), wave=None):
+def _rays(m, n, rays, eta, wave):
+    """the wavevectors of ray mode: None, or ((k0, l0) two arrays of n finite reals, eta finite)"""
+    if rays is None:
+        if eta is not None:
+            raise ValueError("particles.attach: eta = %r without rays=" % (eta,))
+        return None, None
+    if wave is not None:
+        raise ValueError("particles.attach: rays= and wave= exclude each other (a ray is no drifter)")
+    if _is_qg(m):
+        raise ValueError("particles.attach: rays=: QGModel has no near-inertial waves")
+    try:
+        k, l = rays
+        k, l = np.array(k, np.float64), np.array(l, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("particles.attach: rays = (k0, l0), two arrays of real wavenumbers")
+    if k.ndim != 1 or l.ndim != 1 or k.size != n or l.size != n:
+        raise ValueError("particles.attach: rays: k0 and l0 of shapes %s, %s for %d particles" % (k.shape, l.shape, n))
+    if not (np.all(np.isfinite(k)) and np.all(np.isfinite(l))):
+        raise ValueError("particles.attach: rays: non-finite wavenumbers")
+    eta = m.hslash if eta is None else eta
+    if isinstance(eta, (bool, np.bool_)) or not isinstance(eta, (int, float, np.integer, np.floating)) or not np.isfinite(float(eta)):
+        raise ValueError("particles.attach: eta = %r (a finite real number; default m.hslash)" % (eta,))
+    return (k, l), float(eta)
+
+
+def attach(m, x, y, record_every=0, capacity=1024, record=(), wave=None, rays=None, eta=None):
     """Attach n particles at (x, y) to model m (one set per model); see the module's doc.  ``wave=a``: drifter mode, the wave
-    velocity a phi e^{-i f0 t} added to the advecting velocity.  Argument errors raise ValueError before the device is touched;
-    slab-decomposed models raise NotImplementedError."""
+    velocity a phi e^{-i f0 t} added to the advecting velocity.  ``rays=(k0, l0)``: ray mode, every particle a near-inertial wave
+    packet with its wavevector, ``eta`` = f / kappa^2 (default ``m.hslash``).  Argument errors raise ValueError before the device is
+    touched; slab-decomposed models raise NotImplementedError."""
     x, y = _coords(x, y)
     wave = _wave(m, wave)
+    rays, eta = _rays(m, x.size, rays, eta, wave)
     if isinstance(record_every, bool) or int(record_every) != record_every or record_every < 0:
         raise ValueError("particles.attach: record_every = %r (an integer >= 0)" % (record_every,))
     record_every = int(record_every)
     if record_every > 0 and (int(capacity) != capacity or capacity < 1):
         raise ValueError("particles.attach: capacity = %r (>= 1 while recording)" % (capacity,))
     capacity = int(capacity) if record_every > 0 else 0
-    record = tuple(_names(m, record, "attach"))
+    record = tuple(_names(m, record, "attach", rays is not None))
     if len(set(record)) != len(record):
         raise ValueError("particles.attach: a name appears twice in record: %s" % (record,))
-    return _attach.attach(m, _AnySize, _Fused, x, y, record_every, capacity, record, wave)
+    return _attach.attach(m, _AnySize, _Fused, x, y, record_every, capacity, record, wave, rays, eta)
