@@ -228,7 +228,7 @@ struct nq_ctx {
   // in-step budget integrals (ref Kernel.py:319-322, :390-392)
   bool bud = false;
   int nww = 0, nwq = 0;                           // workgroups of the two kernels that emit partial sums
-  double *partW = nullptr, *partQ = nullptr;      // [4 stages][workgroups][NQ_PARTW | 3]
+  double *partW = nullptr, *partQ = nullptr;      // [4 stages][workgroups][NQ_PARTW | 3]; partW: + 2 (BudgetW.w00)
   double *part0W = nullptr, *part0Q = nullptr;    // partials of set_phi / set_q / nq_invert
   double *diag_part = nullptr, *diag_out = nullptr;   // diagnostics tick: workgroup partials, 32 reduced sums
   double *spec_out = nullptr, *spec_r = nullptr;     // isotropic spectra of the tick: 32 x nb shell sums, two real planes
@@ -1534,6 +1534,8 @@ static BudgetW budget_w(nq_ctx* c, double* part, const cd* y_start) {
   bw.nu4w = c->p.nu4w;
   bw.nuw = c->p.nuw;
   bw.muw = c->p.muw;
+  bw.part_prev = nullptr;
+  bw.w00 = nullptr;
   return bw;
 }
 // ophi, ophiy: where phi and phiy of the stage result go, when not to Mphi, Mphiy (do_step_ybj)
@@ -1554,13 +1556,27 @@ static void launch_sphi(nq_ctx* c, const EtdArrays& ea_, int stage, const cd* y_
     if (stage == 1 || stage == 2) y_start = nullptr;
   }
   BudgetW bw = budget_w(c, c->partW + (size_t)stage * c->nww * NQ_PARTW, y_start);
+  if (bw.part && !pf.store) {
+    // SG, SX of stage 1 come from the stage-2 launch.  Every reader of partW (k_budget_sums, k_budget_small, and through
+    // bsums the slab all-reduce and the host's increments) runs after stage 3 of the step that wrote it, in every step.
+    if (stage == 2) bw.part_prev = c->partW + (size_t)(stage - 1) * c->nww * NQ_PARTW;
+    bw.w00 = c->partW + (size_t)4 * c->nww * NQ_PARTW;
+  }
   const cd* jpass = c->ybj ? nullptr : c->mUq.ys + c->mUq.W;     // YBJModel.jacobian_psi_phi keeps [0,0] (YBJModel.py:123-133)
   const cd* jown = (jpass && c->redir_now) ? c->mUq.xs + c->mUq.W : jpass;     // the own block was not copied across (ArrayListR)
   const int own0 = c->redir_now ? c->rank * c->Nloc : 0, own1 = c->redir_now ? own0 + c->Nloc : 0;
   with_col_plan(c, [&](auto s1, auto cly) {
     constexpr int S = decltype(s1)::value, CLX = decltype(cly)::value;
     typedef YPlanT<S, CLX> Y;
-    hipLaunchKernelGGL((k_s_phi<S, CLX>), dim3(c->Wf / CLX, c->S2), dim3(Y::THREADS), Y::LDS_BYTES, c->stream, c->mW, jpass, jown, own0, own1, c->mUq.pitch, ea, stage, geom_full(c), ophi, ophiy, 1.0 / ((double)c->N * c->N), c->kk, c->ll, c->tw, 1, bw, pf);
+    auto launch = [&](auto st) {
+      hipLaunchKernelGGL((k_s_phi<S, CLX, decltype(st)::value>), dim3(c->Wf / CLX, c->S2), dim3(Y::THREADS), Y::LDS_BYTES, c->stream, c->mW, jpass, jown, own0, own1, c->mUq.pitch, ea, geom_full(c), ophi, ophiy, 1.0 / ((double)c->N * c->N), c->kk, c->ll, c->tw, 1, bw, pf);
+    };
+    switch (stage) {
+      case 0: launch(Int<0>{}); break;
+      case 1: launch(Int<1>{}); break;
+      case 2: launch(Int<2>{}); break;
+      default: launch(Int<3>{}); break;
+    }
   });
 }
 static void launch_emit_phi(nq_ctx* c, const cd* phih) {
@@ -2944,7 +2960,7 @@ static int create_impl(const nq_params* p_in, const double* kk, const double* ll
       c->carryQ = c->bsums + 48;
       c->gradS1 = c->bsums + 51;
       if (c->kernel_family) {
-        ALLOC(c, c->partW, (size_t)4 * c->nww * NQ_PARTW);
+        ALLOC(c, c->partW, (size_t)4 * c->nww * NQ_PARTW + 2);       // + BudgetW.w00
         ALLOC(c, c->part0W, (size_t)c->nww * NQ_PARTW);
       }
     }

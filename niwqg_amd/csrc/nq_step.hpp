@@ -1381,15 +1381,24 @@ struct BudgetW {
   double* part;        // [workgroup][6]: S0..S3 of the NEW phih, then SG, SX of this stage; null = off
   const cd* y_start;   // phih at the start of this stage (what the tendency was computed from)
   double nu4w, nuw, muw;
+  // Without PhiFlow.store the SG, SX of stage 1 are formed by the stage-2 launch, which holds both operands anyway (a from u
+  // and N1, and N2), and go into slots 4, 5 of the STAGE-1 record of the same workgroup: every launch of k_s_phi has the same
+  // tiles, thread order and reduction, so the sums keep their bits, and nothing reads the records before the step's last stage.
+  double* part_prev;   // stage 2: the stage-1 records; null elsewhere and with PhiFlow.store
+  // [2]: the tendency of stage 1 at [0,0] as its transform gave it (the stored N2 has the Jacobian's domain sum added, the
+  // projection wants it without).  One thread of the stage-1 launch writes it, one thread of the stage-2 launch reads it.
+  // Invariant, for part_prev as well: the stage-2 launch follows the stage-1 launch of the SAME step on the same stream and
+  // under the same PhiFlow.store; every step path does that, and a caller of nq_phase must keep the stages in order too.
+  double* w00;
 };
 constexpr int NQ_PARTW = 6;
 
 // ---- ETDRK4 stage update of one phi-hat element ------------------------------------------------------
 // Same recursion as etd_update, but the results a, b of stages 0 and 1 are inputs of nothing except this kernel's next
 // launches (the stage-2 operand and the `ys` of the projections), and both are Eh*u + Q*N of operands those launches load
-// anyway or can load at the price of loading a or b: stage 1 forms a from u and N1, stage 2 forms a and b from u, N1 and
-// N2, and stages 0 and 1 store no state at all.  c (stage 2) stays stored: the host reads it (NQ_F_PHIH_STAGE4) and N3 is
-// gone once it is folded into N2 + N3.
+// anyway or can load at the price of loading a or b: stage 2 forms a and b from u, N1 and N2 (and with them the projection
+// of stage 1 next to its own, so stage 1 reads no N1), and stages 0 and 1 store no state at all.  c (stage 2) stays stored:
+// the host reads it (NQ_F_PHIH_STAGE4) and N3 is gone once it is folded into N2 + N3.
 // PhiFlow.store (NIWQG_AMD_PHI_STAGE_STORE=1) keeps the stores of a, b and reads them back.
 struct PhiFlow {
   const cd* y_n;       // y(t_n): the operand a and b are formed from again (stage 2; stages 0, 1 have it as y_in)
@@ -1407,9 +1416,10 @@ __device__ __forceinline__ cd etd_half_step(cd eh, cd q, cd y, cd n) {
   return cmake(r1 + r2, i1 + i2);
 }
 
-// returns the stage result; ys <- phih at the start of this stage (with budgets only)
+// returns the stage result; ys <- phih at the start of this stage (with budgets only; not in stage 1 unless pf.store: that
+// projection is left to stage 2, which hands out its operands in y1 <- a and n1 <- N2)
 __device__ __forceinline__ cd phi_stage_update(const EtdArrays& a, const PhiFlow& pf, const BudgetW& bw, bool bud, size_t idx,
-                                               size_t ci, cd Nl, int stage, cd& ys) {
+                                               size_t ci, cd Nl, int stage, cd& ys, cd& y1, cd& n1) {
   cd y;
   if (stage == 3) {
     const cd n0 = a.fn0[idx], nab = a.fna[idx];
@@ -1428,7 +1438,7 @@ __device__ __forceinline__ cd phi_stage_update(const EtdArrays& a, const PhiFlow
     if (pf.store) a.y_out[idx] = y;
   } else if (stage == 1) {
     const cd u = a.y_in[idx];
-    if (bud) ys = pf.store ? bw.y_start[idx] : etd_half_step(eh, q, u, a.fn0[idx]);
+    if (bud && pf.store) ys = bw.y_start[idx];
     y = etd_half_step(eh, q, u, Nl);
     a.fna[idx] = Nl;
     if (pf.store) a.y_out[idx] = y;
@@ -1442,6 +1452,8 @@ __device__ __forceinline__ cd phi_stage_update(const EtdArrays& a, const PhiFlow
       const cd u = pf.y_n[idx];
       ya = etd_half_step(eh, q, u, n0);
       if (bud) ys = etd_half_step(eh, q, u, na);
+      y1 = ya;
+      n1 = na;
     }
     const cd comb = cmake(__builtin_fma(2.0, Nl.x, -n0.x), __builtin_fma(2.0, Nl.y, -n0.y));      // 2 N3 - N1, fused as it was
     y = etd_half_step(eh, q, ya, comb);
@@ -1449,6 +1461,17 @@ __device__ __forceinline__ cd phi_stage_update(const EtdArrays& a, const PhiFlow
     a.y_out[idx] = y;
   }
   return y;
+}
+
+// s += {-wv2 Re(conj(ys) w), -d Im(conj(ys) w)}: one element of the Parseval projections.  Like etd_half_step, every rounding is
+// spelled out and contraction is off: stage 1's sums are formed in another instantiation of k_s_phi than the one that holds ys
+// as a stored value (PhiFlow.store), and no site's context may decide which multiply is fused.  The shape is the one the
+// compiler gave the plain expressions while `stage` was a run-time argument.
+__device__ __forceinline__ void phi_project(double (&s)[2], double wv2, double d, cd ys, cd w) {
+#pragma clang fp contract(off)
+  const double re = __builtin_fma(ys.x, w.x, ys.y * w.y), im = __builtin_fma(ys.x, w.y, -(ys.y * w.x));
+  s[0] = __builtin_fma(-wv2, re, s[0]);
+  s[1] = __builtin_fma(-d, im, s[1]);
 }
 
 // a[], b[] hold y/M and i*l*y/M on return; budgets: sums over the new y
@@ -1474,13 +1497,15 @@ __device__ __forceinline__ void phi_outputs(const cd (&y)[P], cd (&a)[P], cd (&b
   }
 }
 
-template <int S1, int CLX = CL>
+// STAGE is a template argument: the four stages load different operands, and registers and schedule of a run-time `stage`
+// would be those of the heaviest one in every launch
+template <int S1, int CLX, int STAGE>
 __global__ void __launch_bounds__((YPlanT<S1, CLX>::THREADS))
-k_s_phi(MArr Hw, const cd* __restrict__ jpass, const cd* __restrict__ jpass_own, int own0, int own1, int jpitch, EtdArrays ea, int stage, YGeom g, MArr Hphi, MArr Hphiy,
+k_s_phi(MArr Hw, const cd* __restrict__ jpass, const cd* __restrict__ jpass_own, int own0, int own1, int jpitch, EtdArrays ea, YGeom g, MArr Hphi, MArr Hphiy,
         double invM, const double* __restrict__ kk, const double* __restrict__ ll, const cd* __restrict__ tw,
         int tw_step_N, BudgetW bw, PhiFlow pf) {
   typedef YPlanT<S1, CLX> Y;
-  constexpr int P = Y::P, T = Y::T;
+  constexpr int P = Y::P, T = Y::T, stage = STAGE;
   const int c = threadIdx.x % CLX, j = threadIdx.x / CLX;
   const int k = blockIdx.x * CLX + c, l1 = pair_order(blockIdx.y, g.S2);
   const int kg = g.k0 + k, S2 = g.S2;
@@ -1506,8 +1531,10 @@ k_s_phi(MArr Hw, const cd* __restrict__ jpass, const cd* __restrict__ jpass_own,
     block_sum_thread0<2>(jfix, red);
   }
   Y::F::template run<false>(a, j, c, lds, twr);
-  double sj[2] = {0.0, 0.0};
+  double sj[2] = {0.0, 0.0}, sj1[2] = {0.0, 0.0};
   const double kx = kk[kg];
+  // the stage-1 projection is formed one launch later (BudgetW.part_prev): stage 1 neither forms nor stores it
+  const bool own = !(bud && stage == 1 && !pf.store), prev = bud && stage == 2 && !pf.store;
 #pragma unroll
   for (int t = 0; t < P; ++t) {
     const int l = l1 + S2 * (j + t * T);
@@ -1515,15 +1542,23 @@ k_s_phi(MArr Hw, const cd* __restrict__ jpass, const cd* __restrict__ jpass_own,
     cd Nl = a[t];                                       // N_phi = -J - 0.5 i R
     if (l == 0 && kg == 0) Nl = cmake(Nl.x + jfix[0], Nl.y + jfix[1]);
     cd ys = cmake(0, 0);                                // phih at the start of this stage (what the tendency was computed from)
-    y[t] = phi_stage_update(ea, pf, bw, bud, idx, (size_t)crow(g, l, N) * g.pitch_s + k, Nl, stage, ys);
+    cd y1 = cmake(0, 0), n1 = cmake(0, 0);              // the same pair of stage 1 (stage 2, when it forms that projection)
+    y[t] = phi_stage_update(ea, pf, bw, bud, idx, (size_t)crow(g, l, N) * g.pitch_s + k, Nl, stage, ys, y1, n1);
     if (bud) {
       // With W = F[-J - (i/2) phi q_psi] (un-zeroed), lap_h = -wv2 ys, diss_h = -d ys (ref Kernel.py:691-700):
       //   gamma1 + gamma2 = -hslash/2 sum Re(conj(lap_h) W) / (M^2 f),   xi1 + xi2 = -sum Im(conj(diss_h) W) / (M^2 f)
       const double ly = ll[l];
       const double wv2 = kx * kx + ly * ly;
       const double d = bw.nu4w * wv2 * wv2 + bw.nuw * wv2 + bw.muw;
-      sj[0] += -wv2 * (ys.x * a[t].x + ys.y * a[t].y);
-      sj[1] += -d * (ys.x * a[t].y - ys.y * a[t].x);
+      if (own) phi_project(sj, wv2, d, ys, a[t]);
+      if (l == 0 && kg == 0) {                          // W is un-zeroed, the stored N2 is not: [0,0] goes by its own way
+        if (!own) {
+          bw.w00[0] = a[t].x;
+          bw.w00[1] = a[t].y;
+        }
+        if (prev) n1 = cmake(bw.w00[0], bw.w00[1]);
+      }
+      if (prev) phi_project(sj1, wv2, d, y1, n1);
     }
   }
   double s4[4] = {0.0, 0.0, 0.0, 0.0};
@@ -1538,7 +1573,8 @@ k_s_phi(MArr Hw, const cd* __restrict__ jpass, const cd* __restrict__ jpass_own,
   }
   if (bud) {
     block_sum_store<4>(s4, red, part);
-    block_sum_store<2>(sj, red, part + 4);
+    if (own) block_sum_store<2>(sj, red, part + 4);
+    if (prev) block_sum_store<2>(sj1, red, bw.part_prev + NQ_PARTW * ((size_t)blockIdx.y * gridDim.x + blockIdx.x) + 4);
   }
 }
 

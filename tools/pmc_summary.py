@@ -43,9 +43,11 @@ PER_STEP = [("k_x_products<", 4), ("k_x_wavepv", 4), ("k_s_q<", 4), ("k_s_phi<",
             ("k_budget_sums", 1), ("k_budget_accumulate", 1)]
 step = 0.0
 for prefix, n in PER_STEP:
-    for k, e in res["kernels"].items():
-        if k.startswith(prefix) and "hbm_bytes_per_launch" in e:
-            step += n * e["hbm_bytes_per_launch"]
+    # (k_s_phi is one instantiation per stage: the n launches of a step are spread over the kernels of that prefix as sampled)
+    hits = [e for k, e in res["kernels"].items() if k.startswith(prefix) and "hbm_bytes_per_launch" in e]
+    total = sum(e.get("launches_sampled", 1) for e in hits)
+    for e in hits:
+        step += n * e["hbm_bytes_per_launch"] * e.get("launches_sampled", 1) / total
 for k, e in res["kernels"].items():
     if k.startswith("k_y_A<") and "hbm_bytes_per_launch" in e:
         step += (8 if "true" in k else 12) * e["hbm_bytes_per_launch"]
