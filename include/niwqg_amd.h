@@ -338,6 +338,39 @@ enum { NQ_PT_K = 9, NQ_PT_L = 10, NQ_PT_ZETA = 11, NQ_PT_OMEGA = 12 };
 int nq_particles_rays(nq_ctx* ctx, const double* k, const double* l, double eta);
 int nq_particles_get_rays(nq_ctx* ctx, double* k, double* l);
 
+/* Stretch mode, every model class (QGModel included: the mode needs the velocity plane only): each particle
+ * also carries the deformation gradient F = d x(t) / d x0 of its trajectory, dF/dt = A F with A = [[u_x, u_y], [v_x, v_y]] at the
+ * particle.  The six values (x, y, f11, f12, f21, f22) take one classical RK4 step after every step of the model, with the
+ * particles' time treatment (stages at t, t + dt/2 twice, t + dt; the fields linear in time between U0 and U1; the F stages from
+ * the stage values of F).  A comes from the derivative of the Keys interpolant on the 16 nodes that give (u, v), and a Runge-Kutta
+ * step commutes with differentiation: F is the exact Jacobian of the discrete map the positions follow, not an approximation
+ * beside it.  With drifter mode on (either order of the two calls) A gains the gradient of a phi e^{-i f0 t}: the compressible
+ * case, det F != 1.  Ray mode and stretch mode exclude each other (the ray map lives in four dimensions).
+ * tangent: right after nq_particles_attach, before any step.  F0 NULL: the identity; else [4][n] in the order f11, f12, f21, f22,
+ * every value finite (-1 otherwise).  -4 with no particles, on a slab context, after the first step, when the mode is on already
+ * or with ray mode on (nq_particles_rays returns -4 once the tangent is on).  Four arrays of n doubles more (32 B a particle, no
+ * plane), counted by nq_device_bytes and freed by detach (-5: none of them stays, the particles are as they were).
+ * get_tangent: F now, [4][n] (-4 without the mode).
+ * tangent_reset: F = I now, so that a long run can renormalise before F overflows (overflow itself stays loud: inf, then NaN; no
+ * clamp).  It writes no record.  tangent_step0: the particle step count (steps since attach) at which F was last the identity or
+ * F0: 0, or the count at the last reset.
+ * Names of attach and sample, one column each: NQ_PT_F11 .. NQ_PT_F22 the entries of F; NQ_PT_LNSIGMA the ln of the largest singular
+ * value of F,  s = ((f11^2 + f12^2) + f21^2) + f22^2,  p = ((f11 - f22)^2 + (f12 + f21)^2) ((f11 + f22)^2 + (f21 - f12)^2)
+ * (= s^2 - 4 det^2, without the cancellation near F = I),  ln sigma_1 = 1/2 ln(1/2 (s + sqrt p)), every product rounded on its
+ * own; NQ_PT_DET f11 f22 - f12 f21.  Sampling them without the mode: -1.  Attach accepts them, for the mode is set after it:
+ * nq_particles_tangent writes those columns of the record taken at attach again; records taken without the mode hold NaN there.
+ * nq_lagr_spectrum does not take the six (-1).
+ * nq_lagr_stretching: with the T held records and the group-sorted index list of nq_lagr_dispersion, out[T][G][4] = the sums over
+ * run g of ln sigma_1, (ln sigma_1)^2, det F and (det F)^2, formed from the recorded f-columns (-1 unless all four are recorded)
+ * by the summation of nq_lagr_dispersion: no floating-point atomics, two calls return the same bits.  A held record written before
+ * the last reset is refused (-1; the text names the step count of the reset): call it once those records have left the ring.    */
+enum { NQ_PT_F11 = 13, NQ_PT_F12 = 14, NQ_PT_F21 = 15, NQ_PT_F22 = 16, NQ_PT_LNSIGMA = 17, NQ_PT_DET = 18 };
+int nq_particles_tangent(nq_ctx* ctx, const double* F0);
+int nq_particles_get_tangent(nq_ctx* ctx, double* F);
+int nq_particles_tangent_reset(nq_ctx* ctx);
+int nq_particles_tangent_step0(nq_ctx* ctx, long long* step);
+int nq_lagr_stretching(nq_ctx* ctx, int T, int G, const int* order, const int* offsets, double* out);
+
 /* Lagrangian spectra and dispersion of the particle records, formed on the device, single-rank contexts
  * only (-4 on slab contexts, -4 with no particles attached; -1 with record_every = 0 or fewer than 2 held records).  With the
  * T held records (T must be their number), oldest first, and the particles taken in the order of a group-sorted index list --
@@ -703,7 +736,8 @@ int nq_event_elapsed(nq_ctx* ctx, int slot_a, int slot_b, float* elapsed_ms);
 /* Per-kernel timing with HIP events on the context's stream.  While enabled, every launch of the
  * selected kernel class inside nq_step is bracketed by an event pair (cost ~2 us per launch).
  * class: 0 x_products, 1 x_wavepv, 2 s_q, 3 s_phi, 4 s_invert, 5 y_A (all A sub-passes);
- * 6 the zeta row pass and 7 the ray step of ray mode (nq_particles_rays), read with nq_profile_read           */
+ * 6 the zeta row pass and 7 the ray step of ray mode (nq_particles_rays), 8 the step of stretch mode (nq_particles_tangent),
+ * read with nq_profile_read           */
 /* best of `reps` timed launches of a 1-read + 1-write stream copy of `bytes` bytes (16 B per lane, grid-stride), in GB/s
  * of bytes moved (read + written): the copy rate of THIS device, bench.py's second roofline denominator */
 int nq_stream_copy_gbs(nq_ctx* ctx, long long bytes, int reps, double* gbs_out);
@@ -797,6 +831,16 @@ int nq_any_particles_rk4_rays(nq_any* eng, void* pos, void* wv, int n, const voi
                               int nx, double Lx, double Ly, double U, double eta, double dt);
 int nq_any_interp_omega(nq_any* eng, void* out, const void* U, const void* Z, const void* pos, const void* wv, int n, int nx, double Lx,
                         double Ly, double Ub, double eta);
+/* Stretch mode on engine planes (nq_particles_tangent above): one step of pos[i] = x + i y and of the columns of F, fa[i] = f11 + i f21
+ * and fb[i] = f12 + i f22; U0, U1 the velocity planes u + i v (U0 == U1: steady); with the wave, P0, P1 the physical phi planes and
+ * the step's start time t (amplitude finite and > 0): drifter mode's velocity and its gradient.  tangent_value: out[i] = ln sigma_1
+ * (which 0) or det F (1) of (fa[i], fb[i]), imaginary part 0. */
+int nq_any_particles_rk4_tangent(nq_any* eng, void* pos, void* fa, void* fb, int n, const void* U0, const void* U1, int nx, double Lx,
+                                 double Ly, double U, double dt);
+int nq_any_particles_rk4_wave_tangent(nq_any* eng, void* pos, void* fa, void* fb, int n, const void* U0, const void* U1, const void* P0,
+                                      const void* P1, int nx, double Lx, double Ly, double U, double dt, double amplitude, double f0,
+                                      double t);
+int nq_any_tangent_value(nq_any* eng, void* out, const void* fa, const void* fb, int n, int which);
 /* Stochastic forcing on engine planes (nq_forcing_attach above: the same generator, counters and Hermitian rule):
  * plane += sqrt_dt Re(amp_plane) xi(.; s).  layout 0: (rows, rows/2+1) half spectrum under the q rule; 1: full (rows, rows) plane,
  * independent values of `stream`; 2: full plane, the Hermitian extension of the q rule (columns k > rows/2 take the conjugate of
@@ -820,6 +864,10 @@ int nq_any_lagr_spectrum(nq_any* eng, int n, int T, const void* const* re, const
                          int demean, int G, const int* order, const int* offsets, int chunk, double* out);
 int nq_any_lagr_dispersion(nq_any* eng, int n, int T, const void* const* pos, int G, const int* order, const int* offsets, int npairs,
                            const int* pi, const int* pj, double* out, double* out_pairs);
+/* nq_lagr_stretching on engine planes: f[r][4] = the device addresses of particle 0's f11, f12, f21, f22 in record r (T x 4
+ * pointers, oldest first), stride the doubles between particles; out[T][G][4].                                               */
+int nq_any_lagr_stretching(nq_any* eng, int n, int T, const void* const* f, int stride, int G, const int* order, const int* offsets,
+                           double* out);
 /* One sample of the averages on engine planes (nq_avg_attach above: the same rule, QGModel's kernel).  src[i]: complex planes of
  * `elems` values read as what[i] (0: Re, 1: |a|^2, 2: the complex value, at most once and in no product) and added to sums[i]
  * (elems doubles; what 2: elems complex); pairs: 2 x nproducts indices into src, psums[p] += the product.  Not synchronous.  */

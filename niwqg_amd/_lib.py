@@ -436,6 +436,7 @@ class Context:
 
     KERNEL_CLASSES = {"x_products": 0, "x_wavepv": 1, "s_q": 2, "s_phi": 3, "s_invert": 4, "y_A": 5}
     RAY_KERNEL_CLASSES = {"pt_zeta": 6, "pt_rays": 7}       # ray mode's row pass and step: one at a time, profile_read()
+    STRETCH_KERNEL_CLASSES = {"pt_tangent": 8}              # stretch mode's step (with or without the wave), likewise
 
     def profile_enable(self, kernel_class):
         self._chk(self.L.nq_profile_enable(self.h, int(kernel_class)), "nq_profile_enable")
@@ -481,6 +482,25 @@ class Context:
         self._chk(self.L.nq_particles_get_rays(self.h, _dptr(k), _dptr(l)), "nq_particles_get_rays")
         return k, l
 
+    def particles_tangent(self, F0=None):
+        """stretch mode: right after particles_attach; F0 (4, n) in the order f11, f12, f21, f22, or None: I"""
+        if F0 is not None:
+            F0 = np.ascontiguousarray(F0, np.float64)
+        self._chk(self.L.nq_particles_tangent(self.h, None if F0 is None else _dptr(F0)), "nq_particles_tangent")
+
+    def particles_get_tangent(self, n):
+        F = np.empty((4, n))
+        self._chk(self.L.nq_particles_get_tangent(self.h, _dptr(F)), "nq_particles_get_tangent")
+        return F
+
+    def particles_tangent_reset(self):
+        self._chk(self.L.nq_particles_tangent_reset(self.h), "nq_particles_tangent_reset")
+
+    def particles_tangent_step0(self):
+        s = ctypes.c_longlong()
+        self._chk(self.L.nq_particles_tangent_step0(self.h, ctypes.byref(s)), "nq_particles_tangent_step0")
+        return int(s.value)
+
     def particles_detach(self):
         self._chk(self.L.nq_particles_detach(self.h), "nq_particles_detach")
 
@@ -504,6 +524,12 @@ class Context:
         out = np.empty((m, w, n))
         self._chk(self.L.nq_particles_records(self.h, info, steps, _dptr(out)), "nq_particles_records")
         return np.array(steps[:m], np.int64), out
+
+    def particles_steps(self):
+        """steps since attach"""
+        info = (ctypes.c_longlong * 4)()
+        self._chk(self.L.nq_particles_records(self.h, info, None, None), "nq_particles_records")
+        return int(info[3])
 
     def particles_held(self, steps=False):
         """records the ring holds; steps=True: their steps since attach (m,), oldest first (nothing is downloaded)"""
@@ -534,6 +560,12 @@ class Context:
                                             _iptr(pairs[1]) if npairs else None, _dptr(out), _dptr(outp) if npairs else None),
                   "nq_lagr_dispersion")
         return out, outp
+
+    def lagr_stretching(self, T, G, order, offsets):
+        """(T, G, 4) sums over each group of ln sigma_1, its square, det F and its square"""
+        out = np.empty((T, G, 4))
+        self._chk(self.L.nq_lagr_stretching(self.h, int(T), int(G), _iptr(order), _iptr(offsets), _dptr(out)), "nq_lagr_stretching")
+        return out
 
     # ---- PDFs of the physical fields (include/niwqg_amd.h: nq_field_hist; niwqg_amd/pdfs.py) --------------------------------
     def field_minmax(self, codes):

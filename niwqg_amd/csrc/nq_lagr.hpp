@@ -13,6 +13,7 @@
 // order (the scheme of k_fq_bin): no floating-point atomics, bit-identical tables from call to call.
 #pragma once
 #include "nq_step.hpp"
+#include "nq_particles.hpp"
 
 namespace nq {
 
@@ -24,7 +25,7 @@ struct LgSeries {
   long long stride;      // doubles between consecutive particles
 };
 
-enum { LG_SINGLE_SUMS = 6, LG_PAIR_SUMS = 5 };
+enum { LG_SINGLE_SUMS = 6, LG_PAIR_SUMS = 5, LG_STRETCH_SUMS = 4 };
 
 // the sum of v over the 256 threads of the workgroup, valid in thread 0; sh: 4 doubles.  Callers that reduce several values in
 // turn pass a slice of their own for each.
@@ -121,6 +122,31 @@ __global__ void __launch_bounds__(256) k_lg_disp(const LgSeries* __restrict__ po
   for (int k = 0; k < LG_SINGLE_SUMS; ++k) {
     const double t = lg_block_sum(v[k], sh[k]);
     if (threadIdx.x == 0) out[((size_t)n * G + g) * LG_SINGLE_SUMS + k] = t;
+  }
+}
+
+// Stretching statistics of stretch mode.  Workgroup (g, n): over the particles i of group g in record n,
+// out[(n * G + g) * 4 + .] = the sums of ln sigma_1, (ln sigma_1)^2, det F and (det F)^2, from the recorded f-columns.  ser: one
+// LgSeries per record with re = f11, im = f12, re2 = f21, im2 = f22 (four series of one stride), the summation of k_lg_disp.
+__global__ void __launch_bounds__(256) k_lg_stretch(const LgSeries* __restrict__ ser, const int* __restrict__ order, const int* __restrict__ offs,
+                                                    int G, double* __restrict__ out) {
+  const int g = blockIdx.x, n = blockIdx.y;
+  const LgSeries b = ser[n];
+  double v[LG_STRETCH_SUMS] = {0.0, 0.0, 0.0, 0.0};
+  for (int s = offs[g] + (int)threadIdx.x; s < offs[g + 1]; s += 256) {
+    const size_t at = (size_t)order[s] * b.stride;
+    const double f11 = b.re[at], f12 = b.im[at], f21 = b.re2[at], f22 = b.im2[at];
+    const double ls = pt_ln_sigma(f11, f12, f21, f22), dt = pt_det(f11, f12, f21, f22);
+    v[0] += ls;
+    v[1] += ls * ls;
+    v[2] += dt;
+    v[3] += dt * dt;
+  }
+  __shared__ double sh[LG_STRETCH_SUMS][4];
+#pragma unroll
+  for (int k = 0; k < LG_STRETCH_SUMS; ++k) {
+    const double t = lg_block_sum(v[k], sh[k]);
+    if (threadIdx.x == 0) out[((size_t)n * G + g) * LG_STRETCH_SUMS + k] = t;
   }
 }
 

@@ -114,6 +114,10 @@ struct NqParticles : DevOwned {            // Lagrangian particles (section 5g)
   double* zeta[2] = {nullptr, nullptr};    // q_psi planes beside uv[0], uv[1] (YBJModel: one, as uv): zeta[cur] is the current state's
   bool z0 = false;                         // zeta[cur] is q_psi of the state the next step starts from
   double* zplane = nullptr;                // q_psi for PT_ZETA without ray mode, allocated when first needed
+  // stretch mode (section 5u): each particle carries the deformation gradient F of its trajectory, four arrays of n doubles
+  bool tan = false;
+  double* f[4] = {nullptr, nullptr, nullptr, nullptr};      // f11, f12, f21, f22
+  long long tan_step0 = 0, tan_count0 = 0; // steps since attach, and records written, when F was last set (attach or reset)
   // Lagrangian spectra and dispersion (section 5r): work plane, window, series table, index lists and tables, allocated by the
   // first call and grown when a later call needs more; the transform of the record axis runs on an engine of its own
   enum { LG_WORK = 0, LG_WIN, LG_SER, LG_ORDER, LG_OFFS, LG_TAB, LG_PAIRS, LG_NBUF };
@@ -1197,7 +1201,8 @@ static dim3 rows_grid(int rows) { return dim3((rows + X::C - 1) / X::C); }
 
 // per-kernel event profiling ---------------------------------------------------------------------
 enum { PK_PRODUCTS = 0, PK_WAVEPV = 1, PK_SQ = 2, PK_SPHI = 3, PK_INVERT = 4, PK_A = 5,
-       PK_PT_ZETA = 6, PK_PT_RAYS = 7 };   // ray mode's two kernels (section 5t): read one class at a time (nq_profile_read)
+       PK_PT_ZETA = 6, PK_PT_RAYS = 7,     // ray mode's two kernels (section 5t): read one class at a time (nq_profile_read)
+       PK_PT_TANGENT = 8 };                // stretch mode's step (section 5u), with or without the wave
 struct ProfScope {
   nq_ctx* c;
   bool on;
@@ -3274,10 +3279,12 @@ int nq_get_stage4_max(nq_ctx* c, double* out2) {
 // re-runs do_invert_now after its stale inversion, YBJModel's step writes neither, and a dual-q context inverts the mean of its
 // two copies exactly where ph takes it.  So a velocity plane is ONE row kernel (k_x_get_uv) away at any point between steps.
 enum { PT_U = 0, PT_V = 1, PT_Q = 2, PT_PHI = 3, PT_UW = NQ_PT_UW, PT_VW = NQ_PT_VW, PT_K = NQ_PT_K, PT_L = NQ_PT_L, PT_ZETA = NQ_PT_ZETA,
-       PT_OMEGA = NQ_PT_OMEGA };
+       PT_OMEGA = NQ_PT_OMEGA, PT_F11 = NQ_PT_F11, PT_F22 = NQ_PT_F22, PT_LNSIGMA = NQ_PT_LNSIGMA, PT_DET = NQ_PT_DET };
 static bool pt_name_of_rays(int name) { return name == PT_K || name == PT_L || name == PT_OMEGA; }   // values only ray mode has
+static bool pt_name_of_tangent(int name) { return name >= PT_F11 && name <= PT_DET; }                // values only stretch mode has
 static bool pt_name_ok(int name) {
-  return (name >= PT_U && name <= PT_PHI) || name == PT_UW || name == PT_VW || name == PT_ZETA || pt_name_of_rays(name);
+  return (name >= PT_U && name <= PT_PHI) || name == PT_UW || name == PT_VW || name == PT_ZETA || pt_name_of_rays(name) ||
+         pt_name_of_tangent(name);
 }
 static bool pt_name_needs_phi(int name) { return name == PT_PHI || name == PT_UW || name == PT_VW; }
 // q_psi comes from the Kernel family's row pass, and ray mode is the Kernel family's
@@ -3393,6 +3400,15 @@ static int pt_sample_into(nq_ctx* c, int name, double* o0, double* o1) {
     } else {
       HIPCHK(c, hipMemcpyAsync(o0, name == PT_K ? P->k : P->l, sizeof(double) * (size_t)P->n, hipMemcpyDeviceToDevice, c->stream));
     }
+  } else if (pt_name_of_tangent(name)) {
+    if (!P->tan) {                            // a column recorded without the mode (nq_particles_sample refuses): NaN, every bit set
+      HIPCHK(c, hipMemsetAsync(o0, 0xff, sizeof(double) * (size_t)P->n, c->stream));
+    } else if (name == PT_LNSIGMA || name == PT_DET) {
+      hipLaunchKernelGGL(k_pt_tan_value, dim3(nb), dim3(256), 0, c->stream, (const double*)P->f[0], (const double*)P->f[1], (const double*)P->f[2],
+                         (const double*)P->f[3], 1, P->n, name == PT_LNSIGMA ? 0 : 1, o0, 1);
+    } else {
+      HIPCHK(c, hipMemcpyAsync(o0, P->f[name - PT_F11], sizeof(double) * (size_t)P->n, hipMemcpyDeviceToDevice, c->stream));
+    }
   } else {
     NQ_FAIL(c, -1, "particles: unknown sample name %d", name);
   }
@@ -3431,14 +3447,24 @@ static int pt_after_step(nq_ctx* c) {
     pt_phase(P->wf0, t, &wv.c[0], &wv.s[0]);
     pt_phase(P->wf0, t + 0.5 * dt, &wv.c[1], &wv.s[1]);
     pt_phase(P->wf0, t + dt, &wv.c[2], &wv.s[2]);
-    hipLaunchKernelGGL(k_pt_rk4_w, dim3(pt_blocks(P->n)), dim3(256), 0, c->stream, P->x, P->y, P->n, U0, U1, (const cd*)P->wphi[P->wcur],
-                       (const cd*)P->wphi[P->wcur ^ 1], g, c->p.U, dt, wv);
+    if (P->tan) {
+      ProfScope ps(c, PK_PT_TANGENT);
+      hipLaunchKernelGGL(k_pt_rk4_wt, dim3(pt_blocks(P->n)), dim3(256), 0, c->stream, P->x, P->y, P->f[0], P->f[1], P->f[2], P->f[3], P->n, U0, U1,
+                         (const cd*)P->wphi[P->wcur], (const cd*)P->wphi[P->wcur ^ 1], g, c->p.U, dt, wv);
+    } else {
+      hipLaunchKernelGGL(k_pt_rk4_w, dim3(pt_blocks(P->n)), dim3(256), 0, c->stream, P->x, P->y, P->n, U0, U1, (const cd*)P->wphi[P->wcur],
+                         (const cd*)P->wphi[P->wcur ^ 1], g, c->p.U, dt, wv);
+    }
     P->wcur ^= 1;
   } else if (P->rays) {                    // zeta1 beside U1 (YBJModel: q is steady as psi is, one plane)
     if (!c->ybj) pt_form_zeta(c, P->zeta[P->cur ^ 1]);
     ProfScope ps(c, PK_PT_RAYS);
     hipLaunchKernelGGL(k_pt_rk4_r, dim3(pt_blocks(P->n)), dim3(256), 0, c->stream, P->x, P->y, P->k, P->l, P->n, U0, U1, (const double*)P->zeta[P->cur],
                        (const double*)P->zeta[c->ybj ? P->cur : P->cur ^ 1], g, c->p.U, P->eta, c->p.dt);
+  } else if (P->tan) {
+    ProfScope ps(c, PK_PT_TANGENT);
+    hipLaunchKernelGGL(k_pt_rk4_t, dim3(pt_blocks(P->n)), dim3(256), 0, c->stream, P->x, P->y, P->f[0], P->f[1], P->f[2], P->f[3], P->n, U0, U1, g,
+                       c->p.U, c->p.dt);
   } else {
     hipLaunchKernelGGL(k_pt_rk4, dim3(pt_blocks(P->n)), dim3(256), 0, c->stream, P->x, P->y, P->n, U0, U1, g, c->p.U, c->p.dt);
   }
@@ -3493,15 +3519,15 @@ int nq_particles_attach(nq_ctx* c, int n, const double* x, const double* y, doub
   return nq_sync(c);
 }
 // the "uw" / "vw" columns of the record written at attach, again with the clock (and amplitude) just set; rays: the "k", "l"
-// and "omega" columns instead, with the mode just set
-static int pt_rewrite_wave_columns(nq_ctx* c, bool rays = false) {
+// and "omega" columns instead, with the mode just set; which == 2: the columns of stretch mode
+static int pt_rewrite_wave_columns(nq_ctx* c, int which = 0) {
   NqParticles* P = c->pt;
   if (P->rg.every <= 0 || P->rg.count != 1) return 0;
   const size_t n = (size_t)P->n;
   double* r = P->ring + (size_t)P->rg.oldest(0) * (2 + P->ncol) * n;
   int col = 2;
   for (int name : P->names) {
-    if (rays ? pt_name_of_rays(name) : (name == PT_UW || name == PT_VW)) {
+    if (which == 2 ? pt_name_of_tangent(name) : which == 1 ? pt_name_of_rays(name) : (name == PT_UW || name == PT_VW)) {
       const int rc = pt_sample_into(c, name, r + col * n, nullptr);
       if (rc) return rc;
     }
@@ -3562,6 +3588,7 @@ int nq_particles_rays(nq_ctx* c, const double* k, const double* l, double eta) {
   if (!c->kernel_family) NQ_FAIL(c, -4, "nq_particles_rays: QGModel has no near-inertial waves");
   if (P->rays) NQ_FAIL(c, -4, "nq_particles_rays: ray mode is on already");
   if (P->wave) NQ_FAIL(c, -4, "nq_particles_rays: drifter mode is on (the two modes exclude each other)");
+  if (P->tan) NQ_FAIL(c, -4, "nq_particles_rays: stretch mode is on (the ray map lives in four dimensions; the two modes exclude each other)");
   if (P->rg.steps > 0) NQ_FAIL(c, -4, "nq_particles_rays: the particles have moved already (call it right after nq_particles_attach)");
   if (!k || !l) NQ_FAIL(c, -1, "nq_particles_rays: both wavevector arrays");
   if (!std::isfinite(eta)) NQ_FAIL(c, -1, "nq_particles_rays: eta = %g", eta);
@@ -3586,7 +3613,7 @@ int nq_particles_rays(nq_ctx* c, const double* k, const double* l, double eta) {
   P->eta = eta;
   P->rays = true;
   P->z0 = false;
-  rc = pt_rewrite_wave_columns(c, true);
+  rc = pt_rewrite_wave_columns(c, 1);
   if (rc) return rc;
   return nq_sync(c);
 }
@@ -3599,6 +3626,70 @@ int nq_particles_get_rays(nq_ctx* c, double* k, double* l) {
   HIPCHK(c, hipMemcpyAsync(k, c->pt->k, sizeof(double) * c->pt->n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(l, c->pt->l, sizeof(double) * c->pt->n, hipMemcpyDeviceToHost, c->stream));
   return nq_sync(c);
+}
+// stretch mode
+int nq_particles_tangent(nq_ctx* c, const double* F0) {
+  NQ_SINGLE_RANK(c, "nq_particles_tangent");
+  NqParticles* P = c->pt;
+  if (!P) NQ_FAIL(c, -4, "nq_particles_tangent: no particles attached");
+  if (P->tan) NQ_FAIL(c, -4, "nq_particles_tangent: stretch mode is on already");
+  if (P->rays) NQ_FAIL(c, -4, "nq_particles_tangent: ray mode is on (the ray map lives in four dimensions; the two modes exclude each other)");
+  if (P->rg.steps > 0) NQ_FAIL(c, -4, "nq_particles_tangent: the particles have moved already (call it right after nq_particles_attach)");
+  const size_t n = (size_t)P->n;
+  if (F0)
+    for (size_t i = 0; i < 4 * n; ++i)
+      if (!std::isfinite(F0[i])) NQ_FAIL(c, -1, "nq_particles_tangent: F0 is not finite at entry %zu of particle %zu", i / n, i % n);
+  HIPCHK(c, hipSetDevice(c->device));
+  const DevMark before = P->mark();
+  int rc = 0;
+  for (int k = 0; k < 4 && !rc; ++k) rc = att_alloc(c, P, &P->f[k], n, "nq_particles_tangent");
+  if (rc) {                                // the particles stay as they were
+    c->bytes -= P->rollback(before);
+    P->f[0] = P->f[1] = P->f[2] = P->f[3] = nullptr;
+    return rc;
+  }
+  if (F0) {
+    for (int k = 0; k < 4; ++k) HIPCHK(c, hipMemcpyAsync(P->f[k], F0 + (size_t)k * n, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+  } else {
+    hipLaunchKernelGGL(k_pt_tan_identity, dim3(pt_blocks(P->n)), dim3(256), 0, c->stream, P->f[0], P->f[1], P->f[2], P->f[3], P->n);
+    HIPCHK(c, hipGetLastError());
+  }
+  P->tan = true;
+  P->tan_step0 = 0;
+  P->tan_count0 = 0;
+  rc = pt_rewrite_wave_columns(c, 2);
+  if (rc) return rc;
+  return nq_sync(c);
+}
+int nq_particles_get_tangent(nq_ctx* c, double* F) {
+  NQ_SINGLE_RANK(c, "nq_particles_get_tangent");
+  if (!c->pt) NQ_FAIL(c, -4, "nq_particles_get_tangent: no particles attached");
+  if (!c->pt->tan) NQ_FAIL(c, -4, "nq_particles_get_tangent: stretch mode is off");
+  if (!F) return -1;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n = (size_t)c->pt->n;
+  for (int k = 0; k < 4; ++k) HIPCHK(c, hipMemcpyAsync(F + (size_t)k * n, c->pt->f[k], sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+  return nq_sync(c);
+}
+int nq_particles_tangent_reset(nq_ctx* c) {
+  NQ_SINGLE_RANK(c, "nq_particles_tangent_reset");
+  NqParticles* P = c->pt;
+  if (!P) NQ_FAIL(c, -4, "nq_particles_tangent_reset: no particles attached");
+  if (!P->tan) NQ_FAIL(c, -4, "nq_particles_tangent_reset: stretch mode is off");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipLaunchKernelGGL(k_pt_tan_identity, dim3(pt_blocks(P->n)), dim3(256), 0, c->stream, P->f[0], P->f[1], P->f[2], P->f[3], P->n);
+  HIPCHK(c, hipGetLastError());
+  P->tan_step0 = P->rg.steps;
+  P->tan_count0 = P->rg.count;
+  return nq_sync(c);
+}
+int nq_particles_tangent_step0(nq_ctx* c, long long* step) {
+  NQ_SINGLE_RANK(c, "nq_particles_tangent_step0");
+  if (!c->pt) NQ_FAIL(c, -4, "nq_particles_tangent_step0: no particles attached");
+  if (!c->pt->tan) NQ_FAIL(c, -4, "nq_particles_tangent_step0: stretch mode is off");
+  if (!step) return -1;
+  *step = c->pt->tan_step0;
+  return 0;
 }
 int nq_particles_detach(nq_ctx* c) {
   NQ_SINGLE_RANK(c, "nq_particles_detach");
@@ -3625,6 +3716,7 @@ int nq_particles_sample(nq_ctx* c, int nnames, const int* names, double* out) {
     if (pt_name_needs_phi(names[i]) && !c->kernel_family) NQ_FAIL(c, -1, "nq_particles_sample: QGModel has no wave field (phi)");
     if (pt_name_needs_waves(names[i]) && !c->kernel_family) NQ_FAIL(c, -1, "nq_particles_sample: name %d is the Kernel family's (zeta, rays)", names[i]);
     if (pt_name_of_rays(names[i]) && !P->rays) NQ_FAIL(c, -1, "nq_particles_sample: name %d needs ray mode (nq_particles_rays)", names[i]);
+    if (pt_name_of_tangent(names[i]) && !P->tan) NQ_FAIL(c, -1, "nq_particles_sample: name %d needs stretch mode (nq_particles_tangent)", names[i]);
   }
   HIPCHK(c, hipSetDevice(c->device));
   const size_t n = (size_t)P->n;
@@ -6423,6 +6515,47 @@ int nq_any_interp_omega(nq_any* e, void* out, const void* U, const void* Z, cons
   ANYCHK(e, hipGetLastError());
   return 0;
 }
+// Stretch mode on engine planes: the step of nq_particles_tangent, fa = f11 + i f21 and fb = f12 + i f22
+// beside pos = x + i y; with the wave, drifter mode's velocity and its gradient from P0 / P1 at time t
+int nq_any_particles_rk4_tangent(nq_any* e, void* pos, void* fa, void* fb, int n, const void* U0, const void* U1, int nx, double Lx, double Ly,
+                                 double Ub, double dt) {
+  if (!e || !pos || !fa || !fb || !U0 || !U1 || n < 1 || nx < 1) return -1;
+  if (!(Lx > 0.0) || !(Ly > 0.0)) ANYFAIL(e, -1, "nq_any_particles_rk4_tangent: domain %g x %g", Lx, Ly);
+  ANYCHK(e, hipSetDevice(e->device));
+  const PtGrid g = {nx, Lx, Ly, Lx / nx, Ly / nx};
+  hipLaunchKernelGGL(k_pt_rk4_tc, dim3(pt_blocks(n)), dim3(256), 0, e->stream, reinterpret_cast<cd*>(pos), reinterpret_cast<cd*>(fa),
+                     reinterpret_cast<cd*>(fb), n, reinterpret_cast<const cd*>(U0), reinterpret_cast<const cd*>(U1), g, Ub, dt);
+  ANYCHK(e, hipGetLastError());
+  return 0;
+}
+int nq_any_particles_rk4_wave_tangent(nq_any* e, void* pos, void* fa, void* fb, int n, const void* U0, const void* U1, const void* P0, const void* P1,
+                                      int nx, double Lx, double Ly, double Ub, double dt, double amplitude, double f0, double t) {
+  if (!e || !pos || !fa || !fb || !U0 || !U1 || !P0 || !P1 || n < 1 || nx < 1) return -1;
+  if (!(Lx > 0.0) || !(Ly > 0.0)) ANYFAIL(e, -1, "nq_any_particles_rk4_wave_tangent: domain %g x %g", Lx, Ly);
+  if (!(amplitude > 0.0) || !std::isfinite(amplitude) || !std::isfinite(f0) || !std::isfinite(t))
+    ANYFAIL(e, -1, "nq_any_particles_rk4_wave_tangent: amplitude = %g (finite, > 0), f0 = %g, t = %g", amplitude, f0, t);
+  ANYCHK(e, hipSetDevice(e->device));
+  const PtGrid g = {nx, Lx, Ly, Lx / nx, Ly / nx};
+  PtWave wv;
+  wv.a = amplitude;
+  pt_phase(f0, t, &wv.c[0], &wv.s[0]);
+  pt_phase(f0, t + 0.5 * dt, &wv.c[1], &wv.s[1]);
+  pt_phase(f0, t + dt, &wv.c[2], &wv.s[2]);
+  hipLaunchKernelGGL(k_pt_rk4_wtc, dim3(pt_blocks(n)), dim3(256), 0, e->stream, reinterpret_cast<cd*>(pos), reinterpret_cast<cd*>(fa),
+                     reinterpret_cast<cd*>(fb), n, reinterpret_cast<const cd*>(U0), reinterpret_cast<const cd*>(U1), reinterpret_cast<const cd*>(P0),
+                     reinterpret_cast<const cd*>(P1), g, Ub, dt, wv);
+  ANYCHK(e, hipGetLastError());
+  return 0;
+}
+// out[i] = ln sigma_1 (which 0) or det F (1) of the columns fa[i], fb[i], imaginary part 0
+int nq_any_tangent_value(nq_any* e, void* out, const void* fa, const void* fb, int n, int which) {
+  if (!e || !out || !fa || !fb || n < 1 || which < 0 || which > 1) return -1;
+  ANYCHK(e, hipSetDevice(e->device));
+  const double *a = static_cast<const double*>(fa), *b = static_cast<const double*>(fb);
+  hipLaunchKernelGGL(k_pt_tan_value, dim3(pt_blocks(n)), dim3(256), 0, e->stream, a, b, a + 1, b + 1, 2, n, which, static_cast<double*>(out), 2);
+  ANYCHK(e, hipGetLastError());
+  return 0;
+}
 // Stochastic forcing on engine planes: plane += sqrt_dt Re(amp) xi with the generator, counters and
 // Hermitian rule of the fused contexts.  layout 0: (rows, rows/2+1) half spectrum, the q rule; 1: full (rows, rows) plane,
 // independent values of `stream`; 2: full plane, the Hermitian extension of the q rule (the reference's full-plane qh).
@@ -7158,6 +7291,20 @@ static hipError_t lg_dispersion_run(hipStream_t st, const LgDev& d, const LgSeri
   return hipStreamSynchronize(st);
 }
 
+// The stretching pass on `st` (section 5u): ser[r] holds the four f-columns of record r; out (T, G, 4) host sums
+static hipError_t lg_stretching_run(hipStream_t st, const LgDev& d, const LgSeries* ser, int n, int T, int G, const int* order, const int* offsets,
+                                    double* out) {
+  hipError_t r = hipMemcpyAsync(d.ser, ser, sizeof(LgSeries) * T, hipMemcpyHostToDevice, st);
+  if (r == hipSuccess) r = hipMemcpyAsync(d.order, order, sizeof(int) * n, hipMemcpyHostToDevice, st);
+  if (r == hipSuccess) r = hipMemcpyAsync(d.offs, offsets, sizeof(int) * (G + 1), hipMemcpyHostToDevice, st);
+  if (r != hipSuccess) return r;
+  hipLaunchKernelGGL(k_lg_stretch, dim3(G, T), dim3(256), 0, st, (const LgSeries*)d.ser, (const int*)d.order, (const int*)d.offs, G, d.tab);
+  if ((r = hipGetLastError()) != hipSuccess) return r;
+  r = hipMemcpyAsync(out, d.tab, sizeof(double) * (size_t)T * G * LG_STRETCH_SUMS, hipMemcpyDeviceToHost, st);
+  if (r != hipSuccess) return r;
+  return hipStreamSynchronize(st);
+}
+
 // ---- fused contexts: the records are the particles' ring; work memory hangs on NqParticles ----------------------------------
 static int lg_column(const NqParticles* P, int name) {
   int col = 2;
@@ -7230,7 +7377,7 @@ int nq_lagr_spectrum(nq_ctx* c, int kind, int T, int F, const double* window, in
   if (held < 2) NQ_FAIL(c, -1, "nq_lagr_spectrum: %d record held (at least 2)", held);
   if (T != held) NQ_FAIL(c, -1, "nq_lagr_spectrum: a window of %d values, %d records are held", T, held);
   if (F < T || (F > 8192 && F != 16384)) NQ_FAIL(c, -1, "nq_lagr_spectrum: nfft = %d (from T = %d to 8192, or 16384)", F, T);
-  if (!(pt_name_ok(kind) || kind == LG_UV || kind == LG_UVW || kind == LG_UVT) || kind == PT_ZETA || pt_name_of_rays(kind))
+  if (!(pt_name_ok(kind) || kind == LG_UV || kind == LG_UVW || kind == LG_UVT) || kind == PT_ZETA || pt_name_of_rays(kind) || pt_name_of_tangent(kind))
     NQ_FAIL(c, -1, "nq_lagr_spectrum: name %d (0 u, 1 v, 2 q, 3 phi, 4 u + i v, 5 uw, 6 vw, 7 uw + i vw, 8 (u + uw) + i (v + vw))", kind);
   // the columns of the series: re + i im, plus re2 + i im2 for the sum of two velocities
   int cre, cim = -1, cre2 = -1, cim2 = -1;
@@ -7333,6 +7480,50 @@ int nq_lagr_dispersion(nq_ctx* c, int T, int G, const int* order, const int* off
   return 0;
 }
 
+int nq_lagr_stretching(nq_ctx* c, int T, int G, const int* order, const int* offsets, double* out) {
+  NQ_SINGLE_RANK(c, "nq_lagr_stretching");
+  NqParticles* P = c->pt;
+  if (!P) NQ_FAIL(c, -4, "nq_lagr_stretching: no particles attached");
+  if (!out) return -1;
+  if (P->rg.every <= 0) NQ_FAIL(c, -1, "nq_lagr_stretching: the particles were attached with record_every = 0");
+  if (!P->tan) NQ_FAIL(c, -1, "nq_lagr_stretching: stretch mode is off (nq_particles_tangent)");
+  int col[4];
+  for (int k = 0; k < 4; ++k) {
+    col[k] = lg_column(P, PT_F11 + k);
+    if (col[k] < 0) NQ_FAIL(c, -1, "nq_lagr_stretching: all of f11, f12, f21, f22 must be recorded (name %d is not)", PT_F11 + k);
+  }
+  const int held = (int)P->rg.held();
+  if (held < 2) NQ_FAIL(c, -1, "nq_lagr_stretching: %d record held (at least 2)", held);
+  if (T != held) NQ_FAIL(c, -1, "nq_lagr_stretching: tables of %d records, %d are held", T, held);
+  if (P->rg.count - held < P->tan_count0)
+    NQ_FAIL(c, -1, "nq_lagr_stretching: the ring still holds %lld records written before the reset at particle step %lld", P->tan_count0 - (P->rg.count - held),
+            P->tan_step0);
+  const int n = P->n;
+  if (const char* bad = lg_check_groups(n, G, order, offsets)) NQ_FAIL(c, -1, "nq_lagr_stretching: %s", bad);
+  HIPCHK(c, hipSetDevice(c->device));
+  size_t need[NqParticles::LG_NBUF] = {};
+  need[NqParticles::LG_SER] = sizeof(LgSeries) * T;
+  need[NqParticles::LG_ORDER] = sizeof(int) * (size_t)n;
+  need[NqParticles::LG_OFFS] = sizeof(int) * (G + 1);
+  need[NqParticles::LG_TAB] = sizeof(double) * (size_t)T * G * LG_STRETCH_SUMS;
+  int rc = lg_reserve(c, P, need, "nq_lagr_stretching");
+  if (rc) return rc;
+  rc = nq_sync(c);
+  if (rc) return rc;
+  const size_t rec = (size_t)(2 + P->ncol) * n;
+  std::vector<LgSeries> ser((size_t)T);
+  for (int r = 0; r < T; ++r) {
+    const double* base = P->ring + (size_t)P->rg.oldest(r) * rec;
+    ser[r].re = base + (size_t)col[0] * n;
+    ser[r].im = base + (size_t)col[1] * n;
+    ser[r].re2 = base + (size_t)col[2] * n;
+    ser[r].im2 = base + (size_t)col[3] * n;
+    ser[r].stride = 1;
+  }
+  HIPCHK(c, lg_stretching_run(c->stream, lg_dev(P), ser.data(), n, T, G, order, offsets, out));
+  return 0;
+}
+
 // The same passes on engine planes (the any-size path keeps one plane per record and name).  re[r], im[r]: the device address of
 // particle 0's real and imaginary part in record r, oldest first (im NULL: a real series; an entry of a complex plane: the plane's
 // address and that plus 8 bytes); stride: doubles between particles (2 on a complex plane).  The work memory lives for the call.
@@ -7394,6 +7585,34 @@ int nq_any_lagr_dispersion(nq_any* e, int n, int T, const void* const* pos, int 
     ser[r].stride = 2;
   }
   const hipError_t r = lg_dispersion_run(e->stream, d, ser.data(), n, T, G, order, offsets, npairs, pi, pj, out, out_pairs);
+  if (r != hipSuccess) (void)hipStreamSynchronize(e->stream);
+  ANYCHK(e, r);
+  return 0;
+}
+
+// f[4 r + k]: the device address of particle 0's f11, f12, f21, f22 (k = 0..3) in record r, oldest first
+int nq_any_lagr_stretching(nq_any* e, int n, int T, const void* const* f, int stride, int G, const int* order, const int* offsets, double* out) {
+  if (!e || !f || !out) return -1;
+  if (n < 1 || T < 2 || stride < 1) ANYFAIL(e, -1, "nq_any_lagr_stretching: n = %d, %d records (at least 2), stride %d", n, T, stride);
+  for (int k = 0; k < 4 * T; ++k)
+    if (!f[k]) ANYFAIL(e, -1, "nq_any_lagr_stretching: record %d has no plane of entry %d", k / 4, k % 4);
+  if (const char* bad = lg_check_groups(n, G, order, offsets)) ANYFAIL(e, -1, "nq_any_lagr_stretching: %s", bad);
+  ANYCHK(e, hipSetDevice(e->device));
+  LgDev d = {};
+  AnyScratch tmp;
+  ANYCHK(e, tmp.get(&d.ser, (size_t)T));
+  ANYCHK(e, tmp.get(&d.order, (size_t)n));
+  ANYCHK(e, tmp.get(&d.offs, (size_t)G + 1));
+  ANYCHK(e, tmp.get(&d.tab, (size_t)T * G * LG_STRETCH_SUMS));
+  std::vector<LgSeries> ser((size_t)T);
+  for (int r = 0; r < T; ++r) {
+    ser[r].re = static_cast<const double*>(f[4 * r]);
+    ser[r].im = static_cast<const double*>(f[4 * r + 1]);
+    ser[r].re2 = static_cast<const double*>(f[4 * r + 2]);
+    ser[r].im2 = static_cast<const double*>(f[4 * r + 3]);
+    ser[r].stride = stride;
+  }
+  const hipError_t r = lg_stretching_run(e->stream, d, ser.data(), n, T, G, order, offsets, out);
   if (r != hipSuccess) (void)hipStreamSynchronize(e->stream);
   ANYCHK(e, r);
   return 0;

@@ -1,7 +1,8 @@
 // Lagrangian particles advected inside the step: the velocity plane of a state, the periodic cubic
 // convolution that interpolates a physical plane at a particle, the RK4 step linear in time, and sampling; the same step with
 // the near-inertial wave velocity a phi e^{-i f0 t} added (drifter mode, section 5s); and the rays of near-inertial wave packets,
-// each particle carrying a wavevector through the flow and its vorticity zeta (ray mode, section 5t).
+// each particle carrying a wavevector through the flow and its vorticity zeta (ray mode, section 5t); and the deformation gradient
+// F = d x(t) / d x0 carried along each trajectory, with or without the wave velocity (stretch mode, section 5u).
 //
 // Grid value [j, i] of an (n, n) physical plane sits at ((i + 1/2) dx, (j + 1/2) dy) (the reference's _initialize_grid).
 // Interpolation is the tensor product of Keys' cubic convolution kernel (a = -1/2) on the 4 x 4 nearest nodes: exact at the
@@ -408,6 +409,163 @@ __global__ void __launch_bounds__(256) k_pt_omega_c(cd* __restrict__ out, const 
     const PtStencil s = pt_stencil(g, pos[i].x, pos[i].y);
     const cd uv = pt_gather(U, g, s);
     out[i] = make_double2(pt_omega(uv.x, uv.y, pt_gather(Z, g, s).x, wv[i].x, wv[i].y, Ub, eta), 0.0);
+  }
+}
+
+// ---- stretch mode: each particle carries the deformation gradient F = d x(t) / d x0 ----------------------
+// dF/dt = A F with A = [[u_x, u_y], [v_x, v_y]] at the particle, the gradients of the one interpolant (pt_gather_d: the same 16
+// nodes).  (x, y, f11, f12, f21, f22) take ONE classical RK4 step with the particles' time treatment, the F stages from the stage
+// values of F: a Runge-Kutta step commutes with differentiation, so the new F is the exact Jacobian of the discrete position map
+// (times the old F).  WAVE: drifter mode's velocity, a phi e^{-i f0 t} and ITS gradient added (the compressible case).
+struct PtTan {
+  double x, y, f11, f12, f21, f22;
+};
+template <bool WAVE>
+__device__ __forceinline__ PtTan pt_tan_rhs(const cd* __restrict__ U0, const cd* __restrict__ U1, const cd* __restrict__ P0,
+                                            const cd* __restrict__ P1, const PtGrid& g, const PtTan& p, int st, double Ub,
+                                            const PtWave& wv) {
+  const PtStencilD s = pt_stencil_d(g, p.x, p.y);
+  const PtJet<cd> U = pt_jet_at(U0, U1, g, s, st);
+  double u = U.f.x + Ub, v = U.f.y, ux = U.fx.x, vx = U.fx.y, uy = U.fy.x, vy = U.fy.y;
+  if constexpr (WAVE) {
+    const PtJet<cd> W = pt_jet_at(P0, P1, g, s, st);
+    const cd w = pt_wave_vel(W.f, wv.a, wv.c[st], wv.s[st]);
+    const cd wx = pt_wave_vel(W.fx, wv.a, wv.c[st], wv.s[st]), wy = pt_wave_vel(W.fy, wv.a, wv.c[st], wv.s[st]);
+    u += w.x;
+    v += w.y;
+    ux += wx.x;
+    vx += wx.y;
+    uy += wy.x;
+    vy += wy.y;
+  }
+  PtTan d;
+  d.x = u;
+  d.y = v;
+  d.f11 = ux * p.f11 + uy * p.f21;
+  d.f12 = ux * p.f12 + uy * p.f22;
+  d.f21 = vx * p.f11 + vy * p.f21;
+  d.f22 = vx * p.f12 + vy * p.f22;
+  return d;
+}
+__device__ __forceinline__ PtTan pt_tan_at(const PtTan& p, double h, const PtTan& d) {
+  PtTan q;
+  q.x = p.x + h * d.x;
+  q.y = p.y + h * d.y;
+  q.f11 = p.f11 + h * d.f11;
+  q.f12 = p.f12 + h * d.f12;
+  q.f21 = p.f21 + h * d.f21;
+  q.f22 = p.f22 + h * d.f22;
+  return q;
+}
+// acc += w d: the RK4 sum k1 + 2 k2 + 2 k3 + k4 formed as the stages arrive, in pt_rk4_sum's order, so that only the state, the
+// running sum and one stage are live at a time
+__device__ __forceinline__ void pt_tan_acc(PtTan& a, double w, const PtTan& d) {
+  a.x += w * d.x;
+  a.y += w * d.y;
+  a.f11 += w * d.f11;
+  a.f12 += w * d.f12;
+  a.f21 += w * d.f21;
+  a.f22 += w * d.f22;
+}
+template <bool WAVE>
+__device__ __forceinline__ void pt_rk4_tan(const cd* __restrict__ U0, const cd* __restrict__ U1, const cd* __restrict__ P0,
+                                           const cd* __restrict__ P1, const PtGrid& g, double Ub, double dt, const PtWave& wv, PtTan& p) {
+  const double h = 0.5 * dt;
+  PtTan k = pt_tan_rhs<WAVE>(U0, U1, P0, P1, g, p, 0, Ub, wv);
+  PtTan acc = k;
+  k = pt_tan_rhs<WAVE>(U0, U1, P0, P1, g, pt_tan_at(p, h, k), 1, Ub, wv);
+  pt_tan_acc(acc, 2.0, k);
+  k = pt_tan_rhs<WAVE>(U0, U1, P0, P1, g, pt_tan_at(p, h, k), 1, Ub, wv);
+  pt_tan_acc(acc, 2.0, k);
+  k = pt_tan_rhs<WAVE>(U0, U1, P0, P1, g, pt_tan_at(p, dt, k), 2, Ub, wv);
+  pt_tan_acc(acc, 1.0, k);
+  p = pt_tan_at(p, dt / 6.0, acc);
+}
+// fused contexts: positions in two arrays, F in four arrays of n doubles (f11, f12, f21, f22)
+template <bool WAVE>
+__device__ __forceinline__ void pt_rk4_tan_arrays(double* __restrict__ px, double* __restrict__ py, double* __restrict__ f11,
+                                                  double* __restrict__ f12, double* __restrict__ f21, double* __restrict__ f22, int n,
+                                                  const cd* U0, const cd* U1, const cd* P0, const cd* P1, const PtGrid& g, double Ub,
+                                                  double dt, const PtWave& wv) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    PtTan p = {px[i], py[i], f11[i], f12[i], f21[i], f22[i]};
+    pt_rk4_tan<WAVE>(U0, U1, P0, P1, g, Ub, dt, wv, p);
+    px[i] = p.x;
+    py[i] = p.y;
+    f11[i] = p.f11;
+    f12[i] = p.f12;
+    f21[i] = p.f21;
+    f22[i] = p.f22;
+  }
+}
+__global__ void __launch_bounds__(256) k_pt_rk4_t(double* __restrict__ px, double* __restrict__ py, double* __restrict__ f11,
+                                                  double* __restrict__ f12, double* __restrict__ f21, double* __restrict__ f22, int n,
+                                                  const cd* U0, const cd* U1, PtGrid g, double Ub, double dt) {
+  pt_rk4_tan_arrays<false>(px, py, f11, f12, f21, f22, n, U0, U1, nullptr, nullptr, g, Ub, dt, PtWave());
+}
+__global__ void __launch_bounds__(256) k_pt_rk4_wt(double* __restrict__ px, double* __restrict__ py, double* __restrict__ f11,
+                                                   double* __restrict__ f12, double* __restrict__ f21, double* __restrict__ f22, int n,
+                                                   const cd* U0, const cd* U1, const cd* P0, const cd* P1, PtGrid g, double Ub, double dt,
+                                                   PtWave wv) {
+  pt_rk4_tan_arrays<true>(px, py, f11, f12, f21, f22, n, U0, U1, P0, P1, g, Ub, dt, wv);
+}
+// any-size engine: pos = x + i y and the columns of F as two complex arrays, fa = f11 + i f21, fb = f12 + i f22
+template <bool WAVE>
+__device__ __forceinline__ void pt_rk4_tan_planes(cd* __restrict__ pos, cd* __restrict__ fa, cd* __restrict__ fb, int n, const cd* U0,
+                                                  const cd* U1, const cd* P0, const cd* P1, const PtGrid& g, double Ub, double dt,
+                                                  const PtWave& wv) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    PtTan p = {pos[i].x, pos[i].y, fa[i].x, fb[i].x, fa[i].y, fb[i].y};
+    pt_rk4_tan<WAVE>(U0, U1, P0, P1, g, Ub, dt, wv, p);
+    pos[i] = make_double2(p.x, p.y);
+    fa[i] = make_double2(p.f11, p.f21);
+    fb[i] = make_double2(p.f12, p.f22);
+  }
+}
+__global__ void __launch_bounds__(256) k_pt_rk4_tc(cd* __restrict__ pos, cd* __restrict__ fa, cd* __restrict__ fb, int n, const cd* U0,
+                                                   const cd* U1, PtGrid g, double Ub, double dt) {
+  pt_rk4_tan_planes<false>(pos, fa, fb, n, U0, U1, nullptr, nullptr, g, Ub, dt, PtWave());
+}
+__global__ void __launch_bounds__(256) k_pt_rk4_wtc(cd* __restrict__ pos, cd* __restrict__ fa, cd* __restrict__ fb, int n, const cd* U0,
+                                                    const cd* U1, const cd* P0, const cd* P1, PtGrid g, double Ub, double dt, PtWave wv) {
+  pt_rk4_tan_planes<true>(pos, fa, fb, n, U0, U1, P0, P1, g, Ub, dt, wv);
+}
+// ln of the largest singular value of F, written with no cancellation near F = I:
+//   s = ((f11^2 + f12^2) + f21^2) + f22^2,   p = ((f11 - f22)^2 + (f12 + f21)^2) ((f11 + f22)^2 + (f21 - f12)^2) = s^2 - 4 det^2,
+//   ln sigma_1 = 1/2 ln(1/2 (s + sqrt p)),
+// in this order of operations and with every product rounded on its own (no contraction), as particles.ln_sigma restates it
+__host__ __device__ inline double pt_ln_sigma(double f11, double f12, double f21, double f22) {
+#pragma clang fp contract(off)
+  const double s = ((f11 * f11 + f12 * f12) + f21 * f21) + f22 * f22;
+  const double a = f11 - f22, b = f12 + f21, c = f11 + f22, d = f21 - f12;
+  const double p = (a * a + b * b) * (c * c + d * d);
+  return 0.5 * log(0.5 * (s + sqrt(p)));
+}
+// det F = f11 f22 - f12 f21, each product rounded on its own
+__host__ __device__ inline double pt_det(double f11, double f12, double f21, double f22) {
+#pragma clang fp contract(off)
+  return f11 * f22 - f12 * f21;
+}
+// "lnsigma" (which == 0) or "det" (1) of F at every particle; the entries of F are `stride` doubles apart (fused arrays: 1; the
+// engine's complex arrays: 2, with f21 = f11 + 1 and f22 = f12 + 1), out likewise `ostride` apart
+__global__ void __launch_bounds__(256) k_pt_tan_value(const double* __restrict__ f11, const double* __restrict__ f12,
+                                                      const double* __restrict__ f21, const double* __restrict__ f22, int stride, int n,
+                                                      int which, double* __restrict__ out, int ostride) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    const size_t at = (size_t)i * stride;
+    const double a = f11[at], b = f12[at], c = f21[at], d = f22[at];
+    out[(size_t)i * ostride] = which == 0 ? pt_ln_sigma(a, b, c, d) : pt_det(a, b, c, d);
+    if (ostride == 2) out[(size_t)i * 2 + 1] = 0.0;
+  }
+}
+// F = I at every particle (nq_particles_tangent with no F0, nq_particles_tangent_reset)
+__global__ void __launch_bounds__(256) k_pt_tan_identity(double* __restrict__ f11, double* __restrict__ f12, double* __restrict__ f21,
+                                                         double* __restrict__ f22, int n) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    f11[i] = 1.0;
+    f12[i] = 0.0;
+    f21[i] = 0.0;
+    f22[i] = 1.0;
   }
 }
 

@@ -7,6 +7,8 @@
     S = lagrangian.spectrum(P, groups=labels)           # .omega (F,), .values {"uv": (F, G), "phi": (F, G)}, .counts (G,)
     R = lagrangian.autocovariance(P, "uv")              # .lag (K + 1,), .values (K + 1,); R.diffusivity()
     D = lagrangian.dispersion(P, pairs=(i, j))          # .t (T,), .A2, .D2, ...; D.kurtosis(), D.pair_kurtosis()
+    S = lagrangian.stretching(P, groups=labels)         # stretch mode: .mean_lnsigma, .var_lnsigma, .mean_det, .var_det; S.ftle()
+    lam = lagrangian.ftle(P)                            # (n,) ln sigma_1 / (t - t0) of every particle now
 
 Only the small tables leave the device; ``P.trajectory()``, which downloads the whole ring, is not called.
 
@@ -26,6 +28,11 @@ comes from the same device pass with a boxcar window and F = 2 T, and a transfor
 
 Dispersion, with d = r_n(i) - r_0(i) of the unwrapped positions, per record n and group: the means of dx, dy, A_xx = <dx^2>, A_yy,
 A_xy, A2 = A_xx + A_yy and <|d|^4>; with pairs (i, j) and s = r_n(i) - r_n(j): D_xx = <sx^2>, D_yy, D_xy, D2 = <|s|^2>, <|s|^4>.
+
+Stretching (stretch mode of the particles; "f11", "f12", "f21", "f22" recorded): per record and group the mean
+and the variance (the mean square minus the squared mean) of ln sigma_1, the ln of the largest singular value of the deformation
+gradient F, and of det F; ``ftle()`` = <ln sigma_1> / (t - t0), t0 the time F was last the identity (the attach, or the last
+``P.reset_deformation()``; every held record must be later than that reset).  These are no series of ``spectrum``.
 
 A particle whose coordinate went non-finite has NaN records (section 5g); the tables of its group are NaN.  An empty group has
 count 0 and NaN tables.  ``reference_spectrum``, ``reference_autocovariance`` and ``reference_dispersion`` are the same definitions
@@ -271,6 +278,77 @@ def dispersion(P, pairs=None, groups=None):
     pairs = check_pairs(pairs, P.n)
     single, pair = P._lagr_dispersion(T, G, order, offsets, pairs)
     return Dispersion(P._times(step), step + P.tc0, counts, single, pair, 0 if pairs is None else len(pairs[0]), groups is not None)
+
+
+class Stretching(object):
+    """per record (T,) or per record and group (T, G): mean_lnsigma, var_lnsigma, mean_det, var_det; t, step (T,), t0 the time at
+    which F was last set, counts (G,)"""
+
+    def __init__(self, t, step, t0, counts, sums, grouped):
+        self.t, self.step, self.t0, self.counts = t, step, t0, counts
+        m = _per_group(np.moveaxis(sums, 1, 2), counts, grouped)            # (T, 4, G) -> means
+        self.mean_lnsigma, ms, self.mean_det, md = (np.ascontiguousarray(m[:, k]) for k in range(4))
+        self.var_lnsigma = ms - self.mean_lnsigma ** 2
+        self.var_det = md - self.mean_det ** 2
+
+    def ftle(self):
+        """<ln sigma_1> / (t - t0), the finite-time Lyapunov exponent of each group; NaN at t = t0"""
+        T = (self.t - self.t0).reshape((-1,) + (1,) * (self.mean_lnsigma.ndim - 1))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(T != 0.0, self.mean_lnsigma / np.where(T != 0.0, T, np.nan), np.nan)
+
+
+STRETCH_COLUMNS = ("f11", "f12", "f21", "f22")
+
+
+def _stretch_t0(P):
+    """the time of the particle step at which F was last set, on the clock of ``trajectory().t``"""
+    return float(P._times(np.array([P.stretch_step0], np.int64))[0])
+
+
+def stretching(P, groups=None):
+    """stretching statistics of stretch mode per group at every held record, from the device tables alone; see the module's doc"""
+    P._check()
+    if not getattr(P, "stretch", False):
+        raise ValueError("lagrangian.stretching: the particles were attached without stretch=")
+    T, step = _records(P, "stretching")
+    if any(c not in P.record for c in STRETCH_COLUMNS):
+        raise ValueError("lagrangian.stretching: needs %s recorded; recorded: %s" % (", ".join(map(repr, STRETCH_COLUMNS)), ", ".join(P.record) or "nothing"))
+    order, offsets, counts, G = check_groups(groups, P.n, "stretching")
+    sums = P._lagr_stretching(T, G, order, offsets)
+    return Stretching(P._times(step), step + P.tc0, _stretch_t0(P), counts, sums, groups is not None)
+
+
+def ftle(P):
+    """ln sigma_1 / (t - t0) of every particle now, (n,), from one ``sample(("lnsigma",))``; NaN at t = t0"""
+    P._check()
+    if not getattr(P, "stretch", False):
+        raise ValueError("lagrangian.ftle: the particles were attached without stretch=")
+    ls = P.sample(("lnsigma",))["lnsigma"]
+    steps = P._steps_now()
+    dt = float(P._times(np.array([steps], np.int64))[0]) - _stretch_t0(P)
+    return ls / dt if dt != 0.0 else np.full_like(ls, np.nan)
+
+
+def reference_stretching(tr, groups=None):
+    """``stretching`` in numpy on a ``particles.Trajectory`` that holds the four f-columns: a dict of mean_lnsigma, var_lnsigma,
+    mean_det, var_det, each (T,) or (T, G), and counts"""
+    from . import particles
+    v = tr.values
+    F = np.stack([np.stack([v["f11"], v["f12"]], -1), np.stack([v["f21"], v["f22"]], -1)], -2)          # (T, n, 2, 2)
+    T, n = F.shape[:2]
+    order, offsets, counts, G = check_groups(groups, n, "reference_stretching")
+    ls, dt = particles.ln_sigma(F), particles.det(F)
+    out = {}
+    for key, a in (("mean_lnsigma", ls), ("ms", ls * ls), ("mean_det", dt), ("md", dt * dt)):
+        sums = np.zeros((T, G))
+        for g in range(G):
+            sums[:, g] = a[:, order[offsets[g]:offsets[g + 1]]].sum(axis=1)
+        out[key] = _per_group(sums, counts, groups is not None)
+    out["var_lnsigma"] = out.pop("ms") - out["mean_lnsigma"] ** 2
+    out["var_det"] = out.pop("md") - out["mean_det"] ** 2
+    out["counts"] = counts
+    return out
 
 
 # ---- the same definitions in numpy, on a downloaded trajectory (tests use them) -----------------------------------------------------

@@ -1,7 +1,7 @@
 """Lagrangian particles advected on the device inside the step.
 
     from niwqg_amd import particles
-    P = particles.attach(m, x, y, record_every=0, capacity=1024, record=(), wave=None, rays=None, eta=None)
+    P = particles.attach(m, x, y, record_every=0, capacity=1024, record=(), wave=None, rays=None, eta=None, stretch=None)
     m.run()                                   # the particles move inside every step, batched or not
     x, y = P.positions()                      # unwrapped coordinates
     s = P.sample(("u", "v", "q", "phi"))      # {name: array(n)} at the current positions, from the current state
@@ -60,6 +60,20 @@ q_psi = q - q_w of the state the last inversion saw, ``ifft2(-wv2 * m.ph).real +
 ValueError, slab-decomposed models NotImplementedError.  ``P.wavevectors()`` returns (k, l); ``"k"``, ``"l"``, ``"omega"`` (ray mode)
 and ``"zeta"`` (any mode) are names of ``record=`` and ``sample()``.  ``rk4_rays`` is one step in numpy, ``ray_omega`` the omega.
 ``rays=None`` is the step of the first paragraph, bit for bit.
+
+Stretch mode: ``attach(..., stretch=True)`` (or an (n, 2, 2) array, the starting F) -- every particle carries
+the deformation gradient F = d x(t) / d x0 of its own trajectory, dF/dt = A F with A = [[u_x, u_y], [v_x, v_y]] at the particle.
+The six values (x, y, f11, f12, f21, f22) take ONE classical RK4 step, with the time treatment above and the F stages from the
+stage values of F.  A is the analytic derivative of the Keys interpolant on the 16 nodes that give (u, v), and a Runge-Kutta step
+commutes with differentiation, so F is the exact Jacobian of the discrete map the positions follow, not an approximation beside
+it: central differences of neighbouring runs converge to it.  (The interpolated velocity is solenoidal to second order only:
+det F - 1 = O(dx^2).)  With ``wave=a`` A gains the gradient of a phi e^{-i f0 t}: the drifter velocity is compressible and det F
+measures clustering.  Every model class, QGModel included; ``rays=`` with ``stretch`` raises ValueError (the ray map lives in four
+dimensions), slab-decomposed models NotImplementedError.  ``P.deformation()`` returns (n, 2, 2); ``P.reset_deformation()`` makes
+F = I on the device (renormalise before F overflows: overflow itself is loud, inf then NaN) and ``P.stretch_step0`` is the particle
+step count at which F was last set.  ``"f11"``, ``"f12"``, ``"f21"``, ``"f22"``, ``"lnsigma"`` (ln of the largest singular value:
+``ln_sigma``) and ``"det"`` are names of ``record=`` and ``sample()``.  ``rk4_tangent`` is one step in numpy; ``lattice(m, n)`` places
+n x n particles so that ``lagrangian.ftle(P).reshape(n, n)`` is a map.  ``stretch=None`` runs the kernels of the other paragraphs.
 """
 import ctypes
 
@@ -75,6 +89,8 @@ _CODES = dict(u=0, v=1, q=2, phi=3, uw=_lib.PT_UW, vw=_lib.PT_VW)        # the n
 # nq_lagr_spectrum's names: the columns, and the composites u + i v, uw + i vw, (u + uw) + i (v + vw)
 _LAGR_CODES = dict(_CODES, uv=4, uvw=_lib.LAGR_UVW, uvt=_lib.LAGR_UVT)
 _CODES.update(k=_lib.PT_K, l=_lib.PT_L, zeta=_lib.PT_ZETA, omega=_lib.PT_OMEGA)
+STRETCH_NAMES = ("f11", "f12", "f21", "f22", "lnsigma", "det")           # stretch mode's own (section 5u), every model class
+_CODES.update(f11=_lib.PT_F11, f12=_lib.PT_F12, f21=_lib.PT_F21, f22=_lib.PT_F22, lnsigma=_lib.PT_LNSIGMA, det=_lib.PT_DET)
 
 
 def _is_qg(m):
@@ -82,26 +98,31 @@ def _is_qg(m):
     return isinstance(m, QG)
 
 
-def available(m, wave=False, rays=False):
+def available(m, wave=False, rays=False, stretch=False):
     """names ``record`` and ``sample`` accept for this model: the fields of the state ("phi": the Kernel family only), which
     ``sample()`` returns by default, with ``wave=True`` also the wave velocity columns "uw", "vw" and with ``rays=True`` "zeta" and
-    the ray's "k", "l", "omega" (Kernel family only; the last three in ray mode)"""
+    the ray's "k", "l", "omega" (Kernel family only; the last three in ray mode); with ``stretch=True`` the entries of F, "lnsigma"
+    and "det" (every model class; in stretch mode)"""
+    tail = list(STRETCH_NAMES) if stretch else []
     if _is_qg(m):
-        return ["u", "v", "q"]
-    return (list(NAMES) if wave else list(FIELDS)) + (list(RAY_NAMES) if rays else [])
+        return ["u", "v", "q"] + tail
+    return (list(NAMES) if wave else list(FIELDS)) + (list(RAY_NAMES) if rays else []) + tail
 
 
-def _names(m, names, what, rays=True):
-    """the names as a list, checked; rays=False: the particles are not in ray mode"""
+def _names(m, names, what, rays=True, stretch=True):
+    """the names as a list, checked; rays=False: the particles are not in ray mode; stretch=False: not in stretch mode"""
     names = [names] if isinstance(names, str) else list(names)
     valid = available(m, wave=True, rays=True)
-    bad = [n for n in names if n not in valid]
-    if bad:
-        raise ValueError("particles.%s: %s not available for %s; valid names: %s"
-                         % (what, ", ".join(map(repr, bad)), type(m).__name__, ", ".join(valid)))
+    bad = [n for n in names if n not in valid and n not in STRETCH_NAMES]
+    if bad:                                       # (the names of stretch mode come first: the list of the state's names ends the text)
+        raise ValueError("particles.%s: %s not available for %s; stretch mode adds %s; valid names: %s"
+                         % (what, ", ".join(map(repr, bad)), type(m).__name__, ", ".join(STRETCH_NAMES), ", ".join(valid)))
     bad = [n for n in names if n in _NEED_RAYS and not rays]
     if bad:
         raise ValueError("particles.%s: %s need ray mode (attach(..., rays=(k0, l0)))" % (what, ", ".join(map(repr, bad))))
+    bad = [n for n in names if n in STRETCH_NAMES and not stretch]
+    if bad:
+        raise ValueError("particles.%s: %s need stretch mode (attach(..., stretch=True))" % (what, ", ".join(map(repr, bad))))
     return names
 
 
@@ -306,6 +327,77 @@ def rk4_rays(x, y, k, l, U0, U1, Z0, Z1, Ub, eta, dt, L):
     return tuple(a + dt / 6.0 * (d1 + 2.0 * d2 + 2.0 * d3 + d4) for a, d1, d2, d3, d4 in zip(p, k1, k2, k3, k4))
 
 
+# ---- stretch mode in numpy (section 5u): the kernels' restatement, in their order of sums ------------------------------------
+def ln_sigma(F):
+    """ln of the largest singular value of F (..., 2, 2), in the library's order of operations (pt_ln_sigma; what "lnsigma" records),
+    written with no cancellation near F = I:  s = ((f11^2 + f12^2) + f21^2) + f22^2,
+    p = ((f11 - f22)^2 + (f12 + f21)^2) ((f11 + f22)^2 + (f21 - f12)^2) = s^2 - 4 det^2,  ln sigma_1 = 1/2 ln(1/2 (s + sqrt p))"""
+    F = np.asarray(F, np.float64)
+    f11, f12, f21, f22 = F[..., 0, 0], F[..., 0, 1], F[..., 1, 0], F[..., 1, 1]
+    s = ((f11 * f11 + f12 * f12) + f21 * f21) + f22 * f22
+    a, b, c, d = f11 - f22, f12 + f21, f11 + f22, f21 - f12
+    p = (a * a + b * b) * (c * c + d * d)
+    return 0.5 * np.log(0.5 * (s + np.sqrt(p)))
+
+
+def det(F):
+    """det F of F (..., 2, 2) as the library forms it (what "det" records): f11 f22 - f12 f21"""
+    F = np.asarray(F, np.float64)
+    return F[..., 0, 0] * F[..., 1, 1] - F[..., 0, 1] * F[..., 1, 0]
+
+
+def rk4_tangent(x, y, F, U0, U1, Ub, dt, L, P0=None, P1=None, a=0.0, f0=0.0, t=0.0):
+    """One step of stretch mode from t to t + dt in numpy, in the operation order of the kernels (k_pt_rk4_t; with P0, P1 and a != 0
+    k_pt_rk4_wt): U0, U1 the velocity planes u + i v (or pairs (u, v)) of the state the step starts from and of the state after it
+    (``U0 is U1``: steady, one gather per stage), P0, P1 the physical phi likewise, F (n, 2, 2); returns the new (x, y, F)."""
+    A0, A1 = _uv_plane(U0), _uv_plane(U1)
+    steady = U0 is U1
+    wave = P0 is not None and a != 0.0
+    if wave:
+        P0, P1, steady_p = np.asarray(P0, np.complex128), np.asarray(P1, np.complex128), P0 is P1
+
+    def jet(B0, B1, same, px, py, st):
+        if st == 0 or same:
+            return interpolate_d(B0, px, py, L)
+        if st == 2:
+            return interpolate_d(B1, px, py, L)
+        p, q = interpolate_d(B0, px, py, L), interpolate_d(B1, px, py, L)
+        return tuple(0.5 * (v + w) for v, w in zip(p, q))
+
+    def rhs(p, st):
+        px, py, f11, f12, f21, f22 = p
+        U, Ux, Uy = jet(A0, A1, steady, px, py, st)
+        u, v, ux, vx, uy, vy = U.real + Ub, U.imag, Ux.real, Ux.imag, Uy.real, Uy.imag
+        if wave:
+            ts = (t, t + 0.5 * dt, t + dt)[st]
+            W, Wx, Wy = (wave_velocity(w, a, f0, ts) for w in jet(P0, P1, steady_p, px, py, st))
+            u, v, ux, vx, uy, vy = u + W.real, v + W.imag, ux + Wx.real, vx + Wx.imag, uy + Wy.real, vy + Wy.imag
+        return (u, v, ux * f11 + uy * f21, ux * f12 + uy * f22, vx * f11 + vy * f21, vx * f12 + vy * f22)
+
+    def at(p, h, d):
+        return tuple(v + h * w for v, w in zip(p, d))
+    F = np.asarray(F, np.float64)
+    p = tuple(np.asarray(v, np.float64) for v in (x, y, F[:, 0, 0], F[:, 0, 1], F[:, 1, 0], F[:, 1, 1]))
+    h = 0.5 * dt
+    k1 = rhs(p, 0)
+    k2 = rhs(at(p, h, k1), 1)
+    k3 = rhs(at(p, h, k2), 1)
+    k4 = rhs(at(p, dt, k3), 2)
+    out = tuple(v + dt / 6.0 * (d1 + 2.0 * d2 + 2.0 * d3 + d4) for v, d1, d2, d3, d4 in zip(p, k1, k2, k3, k4))
+    return out[0], out[1], np.stack([np.stack([out[2], out[3]], -1), np.stack([out[4], out[5]], -1)], -2)
+
+
+def lattice(m, n):
+    """(x, y) of an n x n lattice at the centres of n x n equal boxes of the domain of ``m``, flattened row-major (y the slow axis):
+    a per-particle value v becomes a map as ``v.reshape(n, n)``, [j, i] at ((i + 1/2) L / n, (j + 1/2) W / n)"""
+    if isinstance(n, bool) or int(n) != n or n < 1:
+        raise ValueError("particles.lattice: n = %r (an integer >= 1)" % (n,))
+    n = int(n)
+    xs, ys = (np.arange(n) + 0.5) * (float(m.L) / n), (np.arange(n) + 0.5) * (float(m.W) / n)
+    X, Y = np.meshgrid(xs, ys)
+    return X.reshape(-1).copy(), Y.reshape(-1).copy()
+
+
 # ---- the public object -------------------------------------------------------------------------------------------------
 class Trajectory(object):
     """records oldest first: step (T,), t (T,), x, y (T, n), values {name: (T, n)}"""
@@ -324,8 +416,9 @@ class Particles(_attach.Attachment):
     NO_SLAB = ("particles.attach: slab-decomposed models have no particles yet (they need the interpolation "
                "partials exchanged between the ranks at every stage; DESIGN.md section 7)")
 
-    def __init__(self, m, n, record_every, capacity, record, wave=None, rays=None, eta=None):
+    def __init__(self, m, n, record_every, capacity, record, wave=None, rays=None, eta=None, stretch=None):
         self.m, self.n = m, n
+        self.stretch = stretch is not None        # stretch mode: on or off
         self.record_every, self.capacity, self.record = record_every, capacity, tuple(record)
         self.tc0, self.t0 = m.tc, m.t
         self.wave = wave                          # drifter mode: the amplitude a, or None
@@ -337,6 +430,29 @@ class Particles(_attach.Attachment):
         if not self.rays:
             raise RuntimeError("particles.wavevectors: attached without rays=")
         return self._wavevectors()
+
+    def deformation(self):
+        """F (n, 2, 2): the deformation gradient of every particle now (a host copy; stretch mode)"""
+        self._check()
+        if not self.stretch:
+            raise RuntimeError("particles.deformation: attached without stretch=")
+        f = self._deformation()                   # (4, n): f11, f12, f21, f22
+        return np.ascontiguousarray(f.T).reshape(self.n, 2, 2)
+
+    def reset_deformation(self):
+        """F = I on the device, now; no record is written.  ``stretch_step0`` moves to the present step count."""
+        self._check()
+        if not self.stretch:
+            raise RuntimeError("particles.reset_deformation: attached without stretch=")
+        self._reset_deformation()
+
+    @property
+    def stretch_step0(self):
+        """the particle step count (steps since attach) at which F was last set: 0, or the count at the last reset"""
+        self._check()
+        if not self.stretch:
+            raise RuntimeError("particles.stretch_step0: attached without stretch=")
+        return self._stretch_step0()
 
     def wave_time(self, step):
         """t_s = t0 + s dt of step s after attach: the clock of the wave phase, counted by the particles"""
@@ -351,7 +467,7 @@ class Particles(_attach.Attachment):
         """{name: array(n)} at the current positions from the current state ("phi": complex); names: a subset of
         available(m) (default: all of them)"""
         self._check()
-        names = available(self.m) if names is None else _names(self.m, names, "sample", self.rays)
+        names = available(self.m) if names is None else _names(self.m, names, "sample", self.rays, self.stretch)
         return self._sample(names)
 
     def _times(self, offsets):
@@ -389,19 +505,20 @@ class Particles(_attach.Attachment):
 class _Fused(Particles):
     """fused contexts: positions, velocity planes and records live in the library (nq_particles_*)"""
 
-    def __init__(self, m, x, y, record_every, capacity, record, wave=None, rays=None, eta=None):
-        Particles.__init__(self, m, len(x), record_every, capacity, record, wave, rays, eta)
+    def __init__(self, m, x, y, record_every, capacity, record, wave=None, rays=None, eta=None, stretch=None):
+        Particles.__init__(self, m, len(x), record_every, capacity, record, wave, rays, eta, stretch)
         self.ctx = m._ctx
         self.ctx.particles_attach(x, y, m.L, m.W, record_every, capacity, [_CODES[r] for r in record])
-        if _is_qg(m):
-            return
         try:                                      # the clock of "uw" / "vw" (host values only) or, with it, drifter mode
-            if wave is None:
-                self.ctx.particles_clock(m.f, m.t)
-            else:
-                self.ctx.particles_wave(wave, m.f, m.t)
-            if rays is not None:
-                self.ctx.particles_rays(rays[0], rays[1], eta)
+            if not _is_qg(m):
+                if wave is None:
+                    self.ctx.particles_clock(m.f, m.t)
+                else:
+                    self.ctx.particles_wave(wave, m.f, m.t)
+                if rays is not None:
+                    self.ctx.particles_rays(rays[0], rays[1], eta)
+            if stretch is not None:
+                self.ctx.particles_tangent(None if stretch is True else stretch)
         except Exception:
             self.ctx.particles_detach()
             raise
@@ -411,6 +528,21 @@ class _Fused(Particles):
 
     def _wavevectors(self):
         return self.ctx.particles_get_rays(self.n)
+
+    def _deformation(self):
+        return self.ctx.particles_get_tangent(self.n)
+
+    def _reset_deformation(self):
+        self.ctx.particles_tangent_reset()
+
+    def _stretch_step0(self):
+        return self.ctx.particles_tangent_step0()
+
+    def _lagr_stretching(self, T, G, order, offsets):
+        return self.ctx.lagr_stretching(T, G, order, offsets)
+
+    def _steps_now(self):
+        return self.ctx.particles_steps()
 
     def _sample(self, names):
         ncols = sum(2 if nm == "phi" else 1 for nm in names)
@@ -442,10 +574,17 @@ class _AnySize(Particles):
     """any-size path: positions (x + i y), velocity planes (u + i v) and records are engine planes; the model's _step_etdrk4 calls
     _before_step / _after_step (nq_any_particles_rk4); U0, U1 are formed from m.ph with the Plane operations"""
 
-    def __init__(self, m, x, y, record_every, capacity, record, wave=None, rays=None, eta=None):
+    def __init__(self, m, x, y, record_every, capacity, record, wave=None, rays=None, eta=None, stretch=None):
         from ._anysize import Plane
-        Particles.__init__(self, m, len(x), record_every, capacity, record, wave, rays, eta)
+        Particles.__init__(self, m, len(x), record_every, capacity, record, wave, rays, eta, stretch)
         self.eng = m._eng
+        self.Fa = self.Fb = None            # the columns of F: f11 + i f21 and f12 + i f22 (stretch mode)
+        self._step0 = self._count0 = 0      # steps since attach, and records written, when F was last set
+        if self.stretch:
+            one, zero = np.ones(len(x)), np.zeros(len(x))
+            f = (one, zero, zero, one) if stretch is True else stretch
+            self.Fa = self.eng.plane((f[0] + 1j * f[2]).reshape(1, -1), real=False)
+            self.Fb = self.eng.plane((f[1] + 1j * f[3]).reshape(1, -1), real=False)
         self.pos = self.eng.plane((x + 1j * y).reshape(1, -1), real=False)
         self.U, self.src = None, None       # velocity plane of the state src (the psi-hat Plane it was formed from)
         self.Z, self.zsrc = None, None      # zeta plane (real part), likewise
@@ -486,6 +625,18 @@ class _AnySize(Particles):
                                       float(m.L), float(m.W), float(m.U), self.eta), "nq_any_interp_omega")
         return out
 
+    def _tangent_plane(self, nm):
+        """a column of stretch mode as a real plane; NaN without the mode (what the library records there)"""
+        e = self.eng
+        if not self.stretch:
+            return e.plane(np.full((1, self.n), np.nan), real=True)
+        if nm in ("lnsigma", "det"):
+            out = self._Plane(e, (1, self.n), True)
+            e.chk(e.L.nq_any_tangent_value(e.h, out.ptr, self.Fa.ptr, self.Fb.ptr, self.n, 0 if nm == "lnsigma" else 1), "nq_any_tangent_value")
+            return out
+        col = self.Fa if nm in ("f11", "f21") else self.Fb
+        return col.real if nm in ("f11", "f12") else col.imag
+
     def _interp(self, plane):
         e = self.eng
         out = self._Plane(e, (1, self.n))
@@ -517,6 +668,8 @@ class _AnySize(Particles):
                 out[nm] = self.wv.real if nm == "k" else self.wv.imag
             elif nm == "omega":
                 out[nm] = self._interp_omega()
+            elif nm in STRETCH_NAMES:
+                out[nm] = self._tangent_plane(nm)
             else:
                 out[nm] = self._interp(d[nm])
         return out
@@ -541,6 +694,14 @@ class _AnySize(Particles):
             e.chk(e.L.nq_any_particles_rk4_rays(e.h, self.pos.ptr, self.wv.ptr, self.n, self.U0.ptr, U1.ptr, self.Z0.ptr, self._current_Z().ptr,
                                                 m.nx, float(m.L), float(m.W), float(m.U), self.eta, float(m.dt)), "nq_any_particles_rk4_rays")
             self.Z0 = None
+        elif self.stretch and self.wave is None:
+            e.chk(e.L.nq_any_particles_rk4_tangent(e.h, self.pos.ptr, self.Fa.ptr, self.Fb.ptr, self.n, self.U0.ptr, U1.ptr, m.nx, float(m.L),
+                                                   float(m.W), float(m.U), float(m.dt)), "nq_any_particles_rk4_tangent")
+        elif self.stretch:
+            e.chk(e.L.nq_any_particles_rk4_wave_tangent(e.h, self.pos.ptr, self.Fa.ptr, self.Fb.ptr, self.n, self.U0.ptr, U1.ptr, self.P0.ptr,
+                                                        m._d["phi"].ptr, m.nx, float(m.L), float(m.W), float(m.U), float(m.dt), self.wave,
+                                                        float(m.f), float(self.wave_time(self.rg.steps))), "nq_any_particles_rk4_wave_tangent")
+            self.P0 = None
         elif self.wave is None:
             e.chk(e.L.nq_any_particles_rk4(e.h, self.pos.ptr, self.n, self.U0.ptr, U1.ptr, m.nx, float(m.L), float(m.W), float(m.U),
                                            float(m.dt)), "nq_any_particles_rk4")
@@ -560,6 +721,32 @@ class _AnySize(Particles):
     def _wavevectors(self):
         w = self.wv.get().reshape(-1)
         return w.real.copy(), w.imag.copy()
+
+    def _deformation(self):
+        a, b = self.Fa.get().reshape(-1), self.Fb.get().reshape(-1)
+        return np.array([a.real, b.real, a.imag, b.imag])
+
+    def _reset_deformation(self):
+        one = np.ones((1, self.n), np.complex128)
+        self.Fa, self.Fb = self.eng.plane(one, real=False), self.eng.plane(1j * one, real=False)
+        self._step0, self._count0 = self.rg.steps, self.rg.count
+
+    def _stretch_step0(self):
+        return self._step0
+
+    def _steps_now(self):
+        return self.rg.steps
+
+    def _lagr_stretching(self, T, G, order, offsets):
+        e, recs = self.eng, self._held_records()
+        if self.rg.count - self.rg.held() < self._count0:
+            raise RuntimeError("lagrangian.stretching: the ring still holds %d records written before the reset at particle step %d"
+                               % (self._count0 - (self.rg.count - self.rg.held()), self._step0))
+        ptrs = [r[1][nm].ptr for r in recs for nm in ("f11", "f12", "f21", "f22")]
+        out = np.empty((T, G, 4))
+        e.chk(e.L.nq_any_lagr_stretching(e.h, self.n, T, (ctypes.c_void_p * (4 * T))(*ptrs), 2, G, _lib._iptr(order), _lib._iptr(offsets),
+                                         _lib._dptr(out)), "nq_any_lagr_stretching")
+        return out
 
     def _sample(self, names):
         pl = self._planes(names)
@@ -619,7 +806,7 @@ class _AnySize(Particles):
         return out, outp
 
     def _detach(self):
-        self.pos = self.U = self.src = self.U0 = self.P0 = self.Z = self.zsrc = self.Z0 = self.wv = None
+        self.pos = self.U = self.src = self.U0 = self.P0 = self.Z = self.zsrc = self.Z0 = self.wv = self.Fa = self.Fb = None
         self.ring = []
         self.eng.sync()
 
@@ -663,13 +850,36 @@ def _rays(m, n, rays, eta, wave):
     return (k, l), float(eta)
 
 
-def attach(m, x, y, record_every=0, capacity=1024, record=(), wave=None, rays=None, eta=None):
+def _stretch(n, stretch, rays):
+    """the starting F of stretch mode: None (off), True (the identity) or (4, n) float64 rows f11, f12, f21, f22 from an (n, 2, 2)
+    array of finite reals"""
+    if stretch is None or stretch is False:
+        return None
+    if rays is not None:
+        raise ValueError("particles.attach: rays= and stretch= exclude each other (the ray map lives in four dimensions; its 2 x 2 "
+                         "block is no deformation gradient)")
+    if stretch is True:
+        return True
+    try:
+        F = np.array(stretch, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("particles.attach: stretch = True, or the starting F: an (n, 2, 2) array of real numbers")
+    if F.shape != (n, 2, 2):
+        raise ValueError("particles.attach: stretch: F of shape %s for %d particles (expected (%d, 2, 2))" % (F.shape, n, n))
+    if not np.all(np.isfinite(F)):
+        raise ValueError("particles.attach: stretch: non-finite entries of F")
+    return np.ascontiguousarray(F.reshape(n, 4).T)
+
+
+def attach(m, x, y, record_every=0, capacity=1024, record=(), wave=None, rays=None, eta=None, stretch=None):
     """Attach n particles at (x, y) to model m (one set per model); see the module's doc.  ``wave=a``: drifter mode, the wave
     velocity a phi e^{-i f0 t} added to the advecting velocity.  ``rays=(k0, l0)``: ray mode, every particle a near-inertial wave
-    packet with its wavevector, ``eta`` = f / kappa^2 (default ``m.hslash``).  Argument errors raise ValueError before the device is
+    packet with its wavevector, ``eta`` = f / kappa^2 (default ``m.hslash``).  ``stretch=True`` (or an (n, 2, 2) starting F): stretch
+    mode, every particle carries the deformation gradient of its trajectory.  Argument errors raise ValueError before the device is
     touched; slab-decomposed models raise NotImplementedError."""
     x, y = _coords(x, y)
     wave = _wave(m, wave)
+    stretch = _stretch(x.size, stretch, rays)
     rays, eta = _rays(m, x.size, rays, eta, wave)
     if isinstance(record_every, bool) or int(record_every) != record_every or record_every < 0:
         raise ValueError("particles.attach: record_every = %r (an integer >= 0)" % (record_every,))
@@ -677,7 +887,7 @@ def attach(m, x, y, record_every=0, capacity=1024, record=(), wave=None, rays=No
     if record_every > 0 and (int(capacity) != capacity or capacity < 1):
         raise ValueError("particles.attach: capacity = %r (>= 1 while recording)" % (capacity,))
     capacity = int(capacity) if record_every > 0 else 0
-    record = tuple(_names(m, record, "attach", rays is not None))
+    record = tuple(_names(m, record, "attach", rays is not None, stretch is not None))
     if len(set(record)) != len(record):
         raise ValueError("particles.attach: a name appears twice in record: %s" % (record,))
-    return _attach.attach(m, _AnySize, _Fused, x, y, record_every, capacity, record, wave, rays, eta)
+    return _attach.attach(m, _AnySize, _Fused, x, y, record_every, capacity, record, wave, rays, eta, stretch)
