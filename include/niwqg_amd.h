@@ -264,6 +264,35 @@ int nq_field_hist(nq_ctx* ctx, int nfields, const int* fields, const double* lo,
                   int joint_b, int joint_bins, int accumulate);
 int nq_field_hist_read(nq_ctx* ctx, unsigned long long* out);
 
+/* Structure functions of the physical fields: raw plane SUMS of the moments of the x-increments
+ * d_r a(x, y) = a((x + r) mod nx, y) - a(x, y), periodic, for each listed separation r (integers in [1, nx - 1], strictly
+ * increasing, at most NQ_SF_MAX_SEPS).  fields: 1 to NQ_SF_MAX_FIELDS different ids out of those nq_field_hist takes for the model
+ * (the same values: the rows of the last inversion) and, on the Kernel family, NQ_SF_PHI, the complex wave field phi itself.
+ * NQ_SF_COLS = 9 columns per field and separation:
+ *   a real field   [p - 1] = sum d^p, p = 1..6;        [6] = sum |d|,  [7] = sum |d|^3,  [8] = sum |d|^5
+ *   NQ_SF_PHI      [p - 1] = sum |d phi|^p, p = 1..6;   [6] = sum Re d phi,  [7] = sum Im d phi,  [8] = 0
+ * triples: ntriples (0 to NQ_SF_MAX_TRIPLES) x 3 INDICES into `fields`: one more column each, sum d_a d_b d_c; NQ_SF_PHI may only be
+ * the last two entries together, (a, phi, phi) = sum d_a |d phi|^2.  A table row is one separation: 9 nfields + ntriples doubles.
+ *
+ * nq_structure: one state into the running table on the device; accumulate = 0 overwrites it, 1 adds to it and needs the fields,
+ *   separations and triples of the call that started it.  Nothing is copied to the host.
+ * nq_structure_read: *samples = states in the table, out = nsep x (9 nfields + ntriples) raw sums (divide by samples nx ny).
+ * Deterministic: workgroup partials (one slot per workgroup and separation), then a second kernel adds the slots in a fixed order;
+ * no floating-point atomics, so two calls on one state give the same bits.  The partials are allocated by the first call and grown
+ * by the largest one, NQ_SF_PART_MAX_BYTES at most (counted by nq_device_bytes, freed with the context).  Reads the state, writes
+ * only these buffers.  -1: bad arguments, a field the model lacks (any NQ_FLOW_* field or NQ_SF_PHI on a QGModel context), and at
+ * nx = 8192 (one value per device thread, one launch per field) a triple of different fields; -4: slab contexts, nothing set yet,
+ * no table yet; -5: an allocation failed.                                                                                     */
+enum { NQ_SF_PHI = 32 };
+#define NQ_SF_MAX_SEPS 64
+#define NQ_SF_MAX_FIELDS 3
+#define NQ_SF_MAX_TRIPLES 4
+#define NQ_SF_COLS 9
+#define NQ_SF_PART_MAX_BYTES (4096 * NQ_SF_MAX_SEPS * (NQ_SF_MAX_FIELDS * NQ_SF_COLS + NQ_SF_MAX_TRIPLES) * 8)
+int nq_structure(nq_ctx* ctx, int nfields, const int* fields, int nsep, const int* seps, int ntriples,
+                 const int* triples /* ntriples x 3 indices into fields */, int accumulate);
+int nq_structure_read(nq_ctx* ctx, long long* samples, double* out /* nsep x (9 nfields + ntriples) raw sums */);
+
 /* Lagrangian particles, single-rank contexts only (slab contexts refuse every call with -4).
  * After every step of nq_step the library moves each particle one classical RK4 step through U_tot = (U + u, v), u = -d psi/dy,
  * v = d psi/dx of the ph the context holds, linear in time between U0 (start of the step) and U1 (after it):
@@ -811,6 +840,11 @@ int nq_any_hist(nq_any* eng, const void* plane, long long elems, int what, doubl
 int nq_any_hist2(nq_any* eng, const void* plane_a, const void* plane_b, long long elems, int what_a, int what_b, const double* lo2,
                  const double* hi2, int bins, unsigned long long* out);
 int nq_any_minmax(nq_any* eng, const void* plane, long long elems, int what, double* out2);
+/* Structure functions on engine planes (nq_structure above: the same columns, the plane kernel of its QGModel route): (rows, cols)
+ * complex planes, what[i] = 0: the real part of plane i, 2: its complex value (the NQ_SF_PHI columns; one plane at most);
+ * increments along a row, separations in [1, cols - 1].  out: the raw sums of this one state, nsep x (9 nfields + ntriples). */
+int nq_any_increments(nq_any* eng, int nfields, const void* const* planes, const int* what /* 0 Re, 2 complex */, int rows, int cols,
+                      int nsep, const int* seps, int ntriples, const int* triples, double* out);
 /* Lagrangian particles on engine planes (the RK4 step and interpolation of nq_particles_attach above): pos holds n complex
  * x + i y; U0, U1 and plane are (nx, nx) complex planes, velocity planes as u + i v; out[i] = plane at pos[i] (real and
  * imaginary parts interpolated each) */

@@ -20,3 +20,4 @@ from . import YBJModel   # noqa: F401
 from . import coarse   # noqa: F401
 from . import shelltoshell   # noqa: F401
 from . import cospectra   # noqa: F401
+from . import structure   # noqa: F401

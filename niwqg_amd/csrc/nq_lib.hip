@@ -15,6 +15,7 @@
 #include "nq_hist.hpp"
 #include "nq_avg.hpp"
 #include "nq_flow.hpp"
+#include "nq_sf.hpp"
 #include "nq_forcing.hpp"
 
 using namespace nq;
@@ -242,6 +243,14 @@ struct nq_ctx {
   unsigned long long* hist_tab = nullptr;
   double* hist_part = nullptr;
   struct HistCfg { int nf = 0, fields[4] = {0, 0, 0, 0}, slot[4] = {0, 0, 0, 0}, bins = 0, jbins = 0, ja = -1, jb = -1; double lo[4] = {}, hi[4] = {}; } hist_cfg;
+  // structure functions (nq_structure): the running table of raw sums and the workgroup partials, sized by the largest call so
+  // far; the configuration of the call that zeroed the table (what accumulate = 1 must repeat and nq_structure_read copies out)
+  double *sf_tab = nullptr, *sf_part = nullptr;
+  int* sf_seps = nullptr;                         // the separations of the call on the device, from sf_seps_host
+  int sf_seps_host[SF_MAX_SEPS] = {};
+  void* sf_part_raw = nullptr;
+  size_t sf_part_count = 0;
+  struct SfCfg { int nf = 0, fields[SF_MAX_FIELDS] = {}, nsep = 0, seps[SF_MAX_SEPS] = {}, ntri = 0, tri[3 * SF_MAX_TRIPLES] = {}; long long samples = 0; } sf_cfg;
   cd *tr_h = nullptr, *tr_f = nullptr;               // its planes on slab contexts (two half, one full-width; P == 1: scr_*)
   double *carryW = nullptr, *carryQ = nullptr;    // spectral sums of the state at the start of the next step
   double *gradS1 = nullptr, *acc = nullptr;       // stale-aware sum wv2|phih_grad|^2 ; Ke,Pw,Kw increments
@@ -2488,6 +2497,19 @@ static void launch_xflow_moments_t(nq_ctx* c, const FlowSel& sel, const AvgArgs&
 static void launch_xflow_moments(nq_ctx* c, const FlowSel& sel, const AvgArgs& a) {
   if (c->p.model == NQ_MODEL_COUPLED) launch_xflow_moments_t<MODE_COUPLED>(c, sel, a);
   else launch_xflow_moments_t<MODE_UNCOUPLED>(c, sel, a);
+}
+// structure functions (csrc/nq_sf.hpp): the same row pass with the increments out of LDS rows after it
+template <int MODE>
+static void launch_xflow_sf_t(nq_ctx* c, const FlowSel& sel, const SfArgs& a) {
+  with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    typedef XPlan<N> X;
+    hipLaunchKernelGGL((k_x_flow_sf<N, MODE, false>), dim3(c->Nloc / X::C), dim3(X::THREADS), sf_lds_bytes<N>(a.nreal, a.phi), c->stream, c->mQ, c->mQw, c->mU, c->mP, c->mPhi, c->mPhiy, c->twx, c->kk, sel, a);
+  });
+}
+static void launch_xflow_sf(nq_ctx* c, const FlowSel& sel, const SfArgs& a) {
+  if (c->p.model == NQ_MODEL_COUPLED) launch_xflow_sf_t<MODE_COUPLED>(c, sel, a);
+  else launch_xflow_sf_t<MODE_UNCOUPLED>(c, sel, a);
 }
 static int hist_plane_grid(size_t n) { return (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024); }
 
@@ -5272,6 +5294,203 @@ int nq_field_hist_read(nq_ctx* c, unsigned long long* out) {
   return nq_sync(c);
 }
 
+// ---- structure functions of the physical fields (csrc/nq_sf.hpp) ------------------------------------------
+static_assert(SF_COLS == NQ_SF_COLS && SF_MAX_SEPS == NQ_SF_MAX_SEPS && SF_MAX_FIELDS == NQ_SF_MAX_FIELDS && SF_MAX_TRIPLES == NQ_SF_MAX_TRIPLES,
+              "limits of nq_structure");
+static_assert(NQ_SF_PHI > FLOW_LAST && NQ_SF_PHI != NQ_PDF_C && NQ_SF_PHI != NQ_AVG_PHI, "NQ_SF_PHI is no other field's id");
+// The call in the kernels' canonical order (csrc/nq_sf.hpp): canon[i] = slot of the call's field i (real fields first, in the
+// call's order, then the complex one); a: nsep, seps, nreal, phi and the triples in slots.  nullptr, or what is wrong.
+static const char* sf_plan(int n, int nfields, const bool* cplx, int nsep, const int* seps, int ntriples, const int* triples, SfArgs* a, int* canon) {
+  static char msg[256];
+  if (nfields < 1 || nfields > SF_MAX_FIELDS) return "1 to 3 fields (the value registers and the LDS rows of the row pass)";
+  if (!seps || nsep < 1 || nsep > SF_MAX_SEPS) return "1 to 64 separations";
+  if (ntriples < 0 || ntriples > SF_MAX_TRIPLES || (ntriples && !triples)) return "0 to 4 triples";
+  *a = SfArgs();
+  for (int i = 0; i < nfields; ++i) {
+    if (cplx[i]) {
+      if (a->phi) return "the complex field listed twice";
+      a->phi = 1;
+    } else {
+      canon[i] = a->nreal++;
+    }
+  }
+  for (int i = 0; i < nfields; ++i)
+    if (cplx[i]) canon[i] = a->nreal;
+  a->nsep = nsep;
+  for (int s = 0; s < nsep; ++s) {
+    if (seps[s] < 1 || seps[s] > n - 1 || (s && seps[s] <= seps[s - 1])) {
+      snprintf(msg, sizeof(msg), "separation %d at position %d (integers in [1, %d], strictly increasing)", seps[s], s, n - 1);
+      return msg;
+    }
+  }
+  a->ntri = ntriples;
+  for (int k = 0; k < ntriples; ++k) {
+    const int* t = triples + 3 * k;
+    for (int i = 0; i < 3; ++i)
+      if (t[i] < 0 || t[i] >= nfields) return "a triple holds three indices into the field list";
+    if (cplx[t[0]] || cplx[t[1]] != cplx[t[2]]) return "the complex field enters a triple only as its last two entries together: (a, phi, phi) = <d a |d phi|^2>";
+    for (int o = 0; o < k; ++o)
+      if (triples[3 * o] == t[0] && triples[3 * o + 1] == t[1] && triples[3 * o + 2] == t[2]) return "a triple listed twice";
+    a->ta[k] = canon[t[0]];
+    a->tb[k] = cplx[t[1]] ? -1 : canon[t[1]];
+    a->tc[k] = cplx[t[2]] ? -1 : canon[t[2]];
+  }
+  return nullptr;
+}
+// where the columns of a partial slot of NF field slots land in a table row of the call: field i at 9 i, triple k at 9 nfields + k
+static SfMap sf_map(int NF, int nfields, const int* canon, int ntriples) {
+  SfMap m;
+  for (int i = 0; i < sf_ncols<SF_MAX_FIELDS>(); ++i) m.col[i] = -1;
+  for (int i = 0; i < nfields; ++i)
+    for (int k = 0; k < SF_COLS; ++k) m.col[canon[i] * SF_COLS + k] = i * SF_COLS + k;
+  for (int k = 0; k < ntriples; ++k) m.col[NF * SF_COLS + k] = nfields * SF_COLS + k;
+  return m;
+}
+static int sf_plane_grid(int rows) { return rows < 1024 ? rows : 1024; }
+// the partials of a call: `count` doubles, allocated on first use and grown by the largest call (NQ_SF_PART_MAX_BYTES bounds it)
+static int sf_reserve(nq_ctx* c, size_t count) {
+  if (!c->sf_tab) {
+    ALLOC(c, c->sf_tab, (size_t)SF_MAX_SEPS * sf_ncols<SF_MAX_FIELDS>());
+    ALLOC(c, c->sf_seps, (size_t)SF_MAX_SEPS);
+  }
+  if (count <= c->sf_part_count) return 0;
+  if (c->sf_part_raw) {
+    const int rc = nq_sync(c);                           // a launch of the last call may still write them
+    if (rc) return rc;
+    for (size_t i = 0; i < c->allocs.size(); ++i)
+      if (c->allocs[i] == c->sf_part_raw) {
+        c->allocs.erase(c->allocs.begin() + i);
+        break;
+      }
+    (void)hipFree(c->sf_part_raw);
+    c->bytes -= (long long)(c->sf_part_count * sizeof(double));
+    c->sf_part_raw = nullptr;
+    c->sf_part = nullptr;
+    c->sf_part_count = 0;
+  }
+  void* p = nullptr;
+  if (hipMalloc(&p, count * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError();
+    NQ_FAIL(c, -5, "nq_structure: cannot allocate %zu bytes of device memory for the workgroup partials", count * sizeof(double));
+  }
+  c->allocs.push_back(p);
+  c->bytes += (long long)(count * sizeof(double));
+  c->sf_part_raw = p;
+  c->sf_part = static_cast<double*>(p);
+  c->sf_part_count = count;
+  return 0;
+}
+
+int nq_structure(nq_ctx* c, int nfields, const int* fields, int nsep, const int* seps, int ntriples, const int* triples, int accumulate) {
+  NQ_SINGLE_RANK(c, "nq_structure");
+  if (!fields || nfields < 1 || nfields > SF_MAX_FIELDS) NQ_FAIL(c, -1, "nq_structure: %d fields (1 to %d)", nfields, SF_MAX_FIELDS);
+  bool cplx[SF_MAX_FIELDS] = {};
+  for (int i = 0; i < nfields; ++i) {
+    cplx[i] = fields[i] == NQ_SF_PHI;
+    if ((cplx[i] || is_flow(fields[i])) && !c->kernel_family)
+      NQ_FAIL(c, -1, "nq_structure: field %d (NQ_FLOW_*, NQ_SF_PHI) on a QGModel context: its plane route has q and its passive scalar only (DESIGN.md section 7)", fields[i]);
+    if (!cplx[i] && !is_flow(fields[i]) && hist_slot(c, fields[i]) < 0)
+      NQ_FAIL(c, -1, "nq_structure: field %d is not available here (Kernel family: NQ_PDF_Q, NQ_PDF_QPSI, NQ_PDF_PHI2, the NQ_FLOW_* fields and NQ_SF_PHI; QGModel: NQ_PDF_Q, with its passive scalar NQ_PDF_C)", fields[i]);
+    for (int k = 0; k < i; ++k)
+      if (fields[k] == fields[i]) NQ_FAIL(c, -1, "nq_structure: field %d listed twice", fields[i]);
+  }
+  if (c->kernel_family ? !c->have_phi : !c->have_q) NQ_FAIL(c, -4, "nq_structure: %s has not been called", c->kernel_family ? "set_phi" : "set_q");
+  SfArgs a;
+  int canon[SF_MAX_FIELDS] = {};
+  if (const char* bad = sf_plan(c->N, nfields, cplx, nsep, seps, ntriples, triples, &a, canon)) NQ_FAIL(c, -1, "nq_structure: %s", bad);
+  const bool one = c->kernel_family && flow_nv_of(c) == 1;        // one value per thread: a launch per field
+  if (one && a.phi && nfields > 1)
+    NQ_FAIL(c, -1, "nq_structure: NQ_SF_PHI beside a real field at nx = %d: a thread of that row plan holds one value, so every field runs in a launch of its own (DESIGN.md section 7); NQ_SF_PHI alone works", c->N);
+  if (one)
+    for (int k = 0; k < ntriples; ++k)
+      if (triples[3 * k] != triples[3 * k + 1] || triples[3 * k] != triples[3 * k + 2])
+        NQ_FAIL(c, -1, "nq_structure: a triple of different fields at nx = %d: a thread of that row plan holds one value, so every field runs in a launch of its own (DESIGN.md section 7); single fields and (a, a, a) work", c->N);
+  nq_ctx::SfCfg cfg;
+  cfg.nf = nfields;
+  cfg.nsep = nsep;
+  cfg.ntri = ntriples;
+  for (int i = 0; i < nfields; ++i) cfg.fields[i] = fields[i];
+  for (int s = 0; s < nsep; ++s) cfg.seps[s] = seps[s];
+  for (int k = 0; k < 3 * ntriples; ++k) cfg.tri[k] = triples[k];
+  if (accumulate) {
+    const nq_ctx::SfCfg& o = c->sf_cfg;
+    bool same = c->sf_tab && o.samples > 0 && o.nf == cfg.nf && o.nsep == cfg.nsep && o.ntri == cfg.ntri;
+    for (int i = 0; same && i < nfields; ++i) same = o.fields[i] == cfg.fields[i];
+    for (int s = 0; same && s < nsep; ++s) same = o.seps[s] == cfg.seps[s];
+    for (int k = 0; same && k < 3 * ntriples; ++k) same = o.tri[k] == cfg.tri[k];
+    if (!same) NQ_FAIL(c, -1, "nq_structure: accumulate = 1 needs the fields, separations and triples of the call that zeroed the table");
+    cfg.samples = o.samples;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const int nout = nfields * SF_COLS + ntriples;
+  const int NF = one ? 1 : SF_MAX_FIELDS, nc = one ? sf_ncols<1>() : sf_ncols<SF_MAX_FIELDS>();
+  const int nblk = c->kernel_family ? xdiag_blocks(c) : sf_plane_grid(c->N);
+  {
+    const int rc = sf_reserve(c, (size_t)nblk * nsep * nc);
+    if (rc) return rc;
+  }
+  a.part = c->sf_part;
+  a.seps = c->sf_seps;
+  for (int s = 0; s < nsep; ++s) c->sf_seps_host[s] = seps[s];
+  HIPCHK(c, hipMemcpyAsync(c->sf_seps, c->sf_seps_host, sizeof(int) * nsep, hipMemcpyHostToDevice, c->stream));
+  const int tgrid = (nsep * nc + SF_TOTAL_ENTRIES - 1) / SF_TOTAL_ENTRIES;
+  if (!c->kernel_family) {
+    SfPlanes pl = {};
+    int mask = 0;
+    for (int i = 0; i < nfields; ++i) mask |= 1 << hist_slot(c, fields[i]);
+    const double* qc[2];
+    hist_qg_planes(c, mask, &qc[0], &qc[1]);
+    for (int i = 0; i < nfields; ++i) {
+      pl.p[canon[i]] = qc[hist_slot(c, fields[i])];
+      pl.stride[canon[i]] = 1;
+    }
+    pl.rows = pl.cols = c->N;
+    hipLaunchKernelGGL(k_sf_plane, dim3(nblk), dim3(SF_PLANE_THREADS), 0, c->stream, pl, a);
+    hipLaunchKernelGGL(k_sf_total, dim3(tgrid), dim3(SF_TOTAL_RUNS * SF_TOTAL_ENTRIES), 0, c->stream, (const double*)c->sf_part, nblk, nsep, nc, sf_map(NF, nfields, canon, ntriples), nout, accumulate, c->sf_tab);
+  } else if (!one) {
+    FlowSel sel = flow_sel_none(c);
+    for (int i = 0; i < nfields; ++i)
+      if (!cplx[i]) sel.code[canon[i]] = fields[i];
+    sel.phi = a.phi;
+    launch_xflow_sf(c, sel, a);
+    hipLaunchKernelGGL(k_sf_total, dim3(tgrid), dim3(SF_TOTAL_RUNS * SF_TOTAL_ENTRIES), 0, c->stream, (const double*)c->sf_part, nblk, nsep, nc, sf_map(NF, nfields, canon, ntriples), nout, accumulate, c->sf_tab);
+  } else {
+    for (int i = 0; i < nfields; ++i) {                 // one field per launch, in the launch's slot 0, into its own columns
+      FlowSel sel = flow_sel_none(c);
+      SfArgs g = a;
+      g.nreal = cplx[i] ? 0 : 1;
+      g.phi = cplx[i] ? 1 : 0;
+      g.ntri = 0;
+      if (!cplx[i]) sel.code[0] = fields[i];
+      sel.phi = g.phi;
+      SfMap m;
+      for (int k = 0; k < sf_ncols<SF_MAX_FIELDS>(); ++k) m.col[k] = k < SF_COLS ? i * SF_COLS + k : -1;
+      for (int k = 0; k < ntriples; ++k)
+        if (triples[3 * k] == i) {                       // (i, i, i): refused above otherwise
+          g.ta[g.ntri] = g.tb[g.ntri] = g.tc[g.ntri] = 0;
+          m.col[SF_COLS + g.ntri++] = nfields * SF_COLS + k;
+        }
+      launch_xflow_sf(c, sel, g);
+      hipLaunchKernelGGL(k_sf_total, dim3(tgrid), dim3(SF_TOTAL_RUNS * SF_TOTAL_ENTRIES), 0, c->stream, (const double*)c->sf_part, nblk, nsep, nc, m, nout, accumulate, c->sf_tab);
+    }
+  }
+  HIPCHK(c, hipGetLastError());
+  ++cfg.samples;
+  c->sf_cfg = cfg;
+  return 0;
+}
+
+int nq_structure_read(nq_ctx* c, long long* samples, double* out) {
+  NQ_SINGLE_RANK(c, "nq_structure_read");
+  if (!samples || !out) NQ_FAIL(c, -1, "nq_structure_read: null output");
+  const nq_ctx::SfCfg& g = c->sf_cfg;
+  if (!c->sf_tab || g.nf == 0) NQ_FAIL(c, -4, "nq_structure_read: no nq_structure call yet");
+  HIPCHK(c, hipSetDevice(c->device));
+  *samples = g.samples;
+  HIPCHK(c, hipMemcpyAsync(out, c->sf_tab, sizeof(double) * g.nsep * (g.nf * SF_COLS + g.ntri), hipMemcpyDeviceToHost, c->stream));
+  return nq_sync(c);
+}
+
 // ---- isotropic spectra of the diagnostics tick ----------------------------------------------------
 int nq_spectrum_shells(const nq_ctx* c) { return c ? nq_shell_count(c->N) : -1; }
 
@@ -6421,6 +6640,46 @@ int nq_any_minmax(nq_any* e, const void* plane, long long elems, int what, doubl
   out2[0] = lo;
   out2[1] = hi;
   return 0;
+}
+// Structure functions on engine planes: the raw sums of nq_structure for one state, from (rows, cols) complex
+// planes; what[i] = 0: the real part of plane i, 2: its complex value (the phi columns; one plane at most); k_sf_plane and
+// k_sf_total of the fused QGModel route.  out: nsep x (9 nfields + ntriples).  Synchronous, like nq_any_hist.
+int nq_any_increments(nq_any* e, int nfields, const void* const* planes, const int* what, int rows, int cols, int nsep, const int* seps,
+                      int ntriples, const int* triples, double* out) {
+  if (!e || !planes || !what || !out || rows < 1 || cols < 2) return -1;
+  if (nfields < 1 || nfields > SF_MAX_FIELDS) ANYFAIL(e, -1, "nq_any_increments: %d fields (1 to %d)", nfields, SF_MAX_FIELDS);
+  bool cplx[SF_MAX_FIELDS] = {};
+  for (int i = 0; i < nfields; ++i) {
+    if (!planes[i]) ANYFAIL(e, -1, "nq_any_increments: plane %d is null", i);
+    if (what[i] != 0 && what[i] != 2) ANYFAIL(e, -1, "nq_any_increments: what[%d] = %d (0: Re, 2: complex)", i, what[i]);
+    cplx[i] = what[i] == 2;
+  }
+  SfArgs a;
+  int canon[SF_MAX_FIELDS] = {};
+  if (const char* bad = sf_plan(cols, nfields, cplx, nsep, seps, ntriples, triples, &a, canon)) ANYFAIL(e, -1, "nq_any_increments: %s", bad);
+  ANYCHK(e, hipSetDevice(e->device));
+  constexpr int nc = sf_ncols<SF_MAX_FIELDS>();
+  const int nblk = sf_plane_grid(rows), nout = nfields * SF_COLS + ntriples;
+  double* tab = nullptr;
+  AnyScratch tmp;
+  ANYCHK(e, tmp.get(&a.part, (size_t)nblk * nsep * nc));
+  ANYCHK(e, tmp.get(&tab, (size_t)nsep * nout));
+  int* dseps = nullptr;
+  ANYCHK(e, tmp.get(&dseps, (size_t)nsep));
+  ANYCHK(e, hipMemcpyAsync(dseps, seps, sizeof(int) * nsep, hipMemcpyHostToDevice, e->stream));
+  a.seps = dseps;
+  SfPlanes pl = {};
+  for (int i = 0; i < nfields; ++i) {
+    pl.p[canon[i]] = reinterpret_cast<const double*>(planes[i]);
+    pl.stride[canon[i]] = 2;
+  }
+  pl.rows = rows;
+  pl.cols = cols;
+  hipLaunchKernelGGL(k_sf_plane, dim3(nblk), dim3(SF_PLANE_THREADS), 0, e->stream, pl, a);
+  hipLaunchKernelGGL(k_sf_total, dim3((nsep * nc + SF_TOTAL_ENTRIES - 1) / SF_TOTAL_ENTRIES), dim3(SF_TOTAL_RUNS * SF_TOTAL_ENTRIES), 0, e->stream, (const double*)a.part, nblk, nsep, nc, sf_map(SF_MAX_FIELDS, nfields, canon, ntriples), nout, 0, tab);
+  ANYCHK(e, hipGetLastError());
+  ANYCHK(e, hipMemcpyAsync(out, tab, sizeof(double) * nsep * nout, hipMemcpyDeviceToHost, e->stream));
+  return nq_any_sync(e);
 }
 int nq_any_set_elem(nq_any* e, void* plane, long long index, double re, double im) {
   if (!e || !plane || index < 0) return -1;
