@@ -293,6 +293,30 @@ int nq_structure(nq_ctx* ctx, int nfields, const int* fields, int nsep, const in
                  const int* triples /* ntriples x 3 indices into fields */, int accumulate);
 int nq_structure_read(nq_ctx* ctx, long long* samples, double* out /* nsep x (9 nfields + ntriples) raw sums */);
 
+/* Structure functions at two-dimensional separations: the same columns and triples for the increments
+ * d_r a(x, y) = a((x + r_x) mod nx, (y + r_y) mod ny) - a(x, y) at nvec (1 to NQ_SF2_MAX_VECS) lattice vectors, vecs = nvec x 2 ints
+ * (r_x, r_y) in any order with r_x in [-(nx - 1), nx - 1], r_y in [0, ny - 1], not (0, 0), no vector twice and none beside its
+ * own periodic image (r_x and r_x - nx).  A table row is one vector, in the caller's order.  proj (or NULL): nvec x 2 doubles
+ * (c_x, c_y), finite; the increments of the real fields proj_a and proj_b (different indices into `fields`; -1, -1 with proj =
+ * NULL) are rotated before anything is summed, d_L = c_x d_a + c_y d_b, d_T = -c_y d_a + c_x d_b: the columns and triples of
+ * proj_a hold L, those of proj_b hold T.  The library takes (c_x, c_y) as given (the unit vector of (r_x dx, r_y dy) is the
+ * caller's business) and needs no grid spacing.
+ *
+ * The Kernel family's values are first stored to physical planes of the context (at most NQ_SF_MAX_FIELDS real planes, or two and
+ * a complex one; allocated by the first call, grown by the largest), so every combination of fields and triples works at every
+ * fused size, nx = 8192 included.  The table, the planes and the owner of the running sums are this call's own: nq_structure's
+ * table is not touched (the workgroup partials are shared, within NQ_SF_PART_MAX_BYTES).  Deterministic like nq_structure.
+ * nq_structure2_read: *samples, out = nvec x (9 nfields + ntriples) raw sums.  Return codes as nq_structure's: -1 bad arguments
+ * (a vector out of range, zero or listed twice; a projection on NQ_SF_PHI or on one field twice; a non-finite proj; a field the
+ * model lacks); -4 slab contexts, nothing set yet, no table yet; -5 an allocation failed (the table, its sample count and the
+ * planes are as they were: a buffer that grows is allocated before the old one is freed; the shared partials are freed first, as
+ * nq_structure frees them, and are allocated again by the next call).                                                         */
+#define NQ_SF2_MAX_VECS 256
+int nq_structure2(nq_ctx* ctx, int nfields, const int* fields, int nvec, const int* vecs /* nvec x 2: r_x, r_y */,
+                  const double* proj /* NULL or nvec x 2: c_x, c_y */, int proj_a, int proj_b, int ntriples,
+                  const int* triples /* ntriples x 3 indices into fields */, int accumulate);
+int nq_structure2_read(nq_ctx* ctx, long long* samples, double* out /* nvec x (9 nfields + ntriples) raw sums */);
+
 /* Lagrangian particles, single-rank contexts only (slab contexts refuse every call with -4).
  * After every step of nq_step the library moves each particle one classical RK4 step through U_tot = (U + u, v), u = -d psi/dy,
  * v = d psi/dx of the ph the context holds, linear in time between U0 (start of the step) and U1 (after it):
@@ -845,6 +869,11 @@ int nq_any_minmax(nq_any* eng, const void* plane, long long elems, int what, dou
  * increments along a row, separations in [1, cols - 1].  out: the raw sums of this one state, nsep x (9 nfields + ntriples). */
 int nq_any_increments(nq_any* eng, int nfields, const void* const* planes, const int* what /* 0 Re, 2 complex */, int rows, int cols,
                       int nsep, const int* seps, int ntriples, const int* triples, double* out);
+/* The same at two-dimensional separations (nq_structure2 above: vectors, projection and return codes; r_x in [-(cols - 1),
+ * cols - 1], r_y in [0, rows - 1]).  out: the raw sums of this one state, nvec x (9 nfields + ntriples), in the caller's order. */
+int nq_any_increments2(nq_any* eng, int nfields, const void* const* planes, const int* what /* 0 Re, 2 complex */, int rows, int cols,
+                       int nvec, const int* vecs, const double* proj, int proj_a, int proj_b, int ntriples, const int* triples,
+                       double* out);
 /* Lagrangian particles on engine planes (the RK4 step and interpolation of nq_particles_attach above): pos holds n complex
  * x + i y; U0, U1 and plane are (nx, nx) complex planes, velocity planes as u + i v; out[i] = plane at pos[i] (real and
  * imaginary parts interpolated each) */

@@ -2,6 +2,7 @@
 // gfx950 only; build: hipcc --offload-arch=gfx950 -O3 -shared -fPIC nq_lib.hip -o libniwqg_amd.so
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -16,6 +17,7 @@
 #include "nq_avg.hpp"
 #include "nq_flow.hpp"
 #include "nq_sf.hpp"
+#include "nq_sf2.hpp"
 #include "nq_forcing.hpp"
 
 using namespace nq;
@@ -251,6 +253,20 @@ struct nq_ctx {
   void* sf_part_raw = nullptr;
   size_t sf_part_count = 0;
   struct SfCfg { int nf = 0, fields[SF_MAX_FIELDS] = {}, nsep = 0, seps[SF_MAX_SEPS] = {}, ntri = 0, tri[3 * SF_MAX_TRIPLES] = {}; long long samples = 0; } sf_cfg;
+  // structure functions at two-dimensional separations (nq_structure2): a running table, vectors and projection of their own, the
+  // physical planes the store pass writes (one pool: the real planes, then the complex one), and the call that zeroed the table
+  double *sf2_tab = nullptr, *sf2_proj = nullptr;
+  Sf2Vec* sf2_vecs = nullptr;
+  Sf2Vec sf2_vecs_host[SF2_MAX_VECS] = {};
+  double sf2_proj_host[2 * SF2_MAX_VECS] = {};
+  void* sf2_planes = nullptr;
+  size_t sf2_planes_count = 0;                    // doubles
+  struct Sf2Cfg {
+    int nf = 0, fields[SF_MAX_FIELDS] = {}, nvec = 0, vecs[2 * SF2_MAX_VECS] = {}, pa = -1, pb = -1, ntri = 0, tri[3 * SF_MAX_TRIPLES] = {};
+    bool has_proj = false;
+    double proj[2 * SF2_MAX_VECS] = {};
+    long long samples = 0;
+  } sf2_cfg;
   cd *tr_h = nullptr, *tr_f = nullptr;               // its planes on slab contexts (two half, one full-width; P == 1: scr_*)
   double *carryW = nullptr, *carryQ = nullptr;    // spectral sums of the state at the start of the next step
   double *gradS1 = nullptr, *acc = nullptr;       // stale-aware sum wv2|phih_grad|^2 ; Ke,Pw,Kw increments
@@ -2510,6 +2526,83 @@ static void launch_xflow_sf_t(nq_ctx* c, const FlowSel& sel, const SfArgs& a) {
 static void launch_xflow_sf(nq_ctx* c, const FlowSel& sel, const SfArgs& a) {
   if (c->p.model == NQ_MODEL_COUPLED) launch_xflow_sf_t<MODE_COUPLED>(c, sel, a);
   else launch_xflow_sf_t<MODE_UNCOUPLED>(c, sel, a);
+}
+// structure functions at two-dimensional separations (csrc/nq_sf2.hpp): the same row pass with plain stores to physical planes
+template <int MODE>
+static void launch_xflow_store_t(nq_ctx* c, const FlowSel& sel, const Sf2Store& st) {
+  with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    typedef XPlan<N> X;
+    hipLaunchKernelGGL((k_x_flow_store<N, MODE>), dim3(c->Nloc / X::C), dim3(X::THREADS), X::LDS_BYTES, c->stream, c->mQ, c->mQw, c->mU, c->mP, c->mPhi, c->mPhiy, c->twx, c->kk, sel, st);
+  });
+}
+static void launch_xflow_store(nq_ctx* c, const FlowSel& sel, const Sf2Store& st) {
+  if (c->p.model == NQ_MODEL_COUPLED) launch_xflow_store_t<MODE_COUPLED>(c, sel, st);
+  else launch_xflow_store_t<MODE_UNCOUPLED>(c, sel, st);
+}
+// which kernel serves rows of `cols` elements of these fields: the row route (points per thread, threads, LDS bytes) or the global
+// one.  The row route runs workgroups of up to 1024 threads with 1, 2, 4 or 8 points each; where the base values and the running
+// sums of that layout pass 128 registers (three field slots at 4096 columns, two real fields at 8192) it runs 512 threads with
+// twice the points (csrc/nq_sf2.hpp: sf2_tmax).  Past 4096 columns phi beside a real field and three real fields go the global way
+// (at 8192 columns their rows exceed the LDS).
+struct Sf2Route {
+  bool lds;
+  int pts, threads, nc;
+  size_t lds_bytes;
+};
+static Sf2Route sf2_route(int cols, int nreal, int phi) {
+  Sf2Route r = {};
+  const int nf = nreal + phi;
+  r.nc = nf == 1 ? sf_ncols<1>() : (nf == 2 ? sf_ncols<2>() : sf_ncols<3>());
+  r.pts = 1;
+  while (r.pts < 8 && (size_t)r.pts * SF2_MAX_THREADS < (size_t)cols) r.pts *= 2;
+  r.lds = (size_t)r.pts * SF2_MAX_THREADS >= (size_t)cols;
+  if (nf == 3 && r.pts == 4) r.pts = 8;                  // 512 threads
+  else if (nf == 2 && !phi && r.pts == 8) r.pts = 16;    // 512 threads
+  else if (r.pts == 8 && nf > 1) r.lds = false;
+  r.threads = ((cols + r.pts - 1) / r.pts + 63) / 64 * 64;
+  r.lds_bytes = ((size_t)(nreal + 2 * phi) * cols + 2 * (size_t)(r.threads / 64) * r.nc) * sizeof(double);
+  if (r.lds_bytes > SF2_LDS_LIMIT) r.lds = false;
+  if (!r.lds) {
+    r.threads = SF2_GLOBAL_THREADS;
+    r.lds_bytes = 0;
+  }
+  return r;
+}
+// workgroups of a call: one per row while the partials (blocks x vectors x columns) stay within NQ_SF_PART_MAX_BYTES
+static int sf2_grid(int rows, int nvec, int nc) {
+  const size_t most = (size_t)NQ_SF_PART_MAX_BYTES / ((size_t)nvec * nc * sizeof(double));
+  return (size_t)rows < most ? rows : (int)most;
+}
+template <int NREAL, int PHI>
+static void sf2_launch_fields(hipStream_t s, int nblk, const Sf2Route& r, const SfPlanes& pl, const Sf2Args& a) {
+  constexpr int NF = NREAL + PHI;
+  const dim3 g(nblk), b(r.threads);
+  if (!r.lds) hipLaunchKernelGGL((k_sf_plane2_global<NREAL, PHI>), g, b, 0, s, pl, a);
+  else if (r.pts == 1) hipLaunchKernelGGL((k_sf_plane2<1, NREAL, PHI>), g, b, r.lds_bytes, s, pl, a);
+  else if (r.pts == 2) hipLaunchKernelGGL((k_sf_plane2<2, NREAL, PHI>), g, b, r.lds_bytes, s, pl, a);
+  else if (r.pts == 4) {
+    if constexpr (NF < 3) hipLaunchKernelGGL((k_sf_plane2<4, NREAL, PHI>), g, b, r.lds_bytes, s, pl, a);
+  } else if (r.pts == 8) {
+    if constexpr (NF != 2) hipLaunchKernelGGL((k_sf_plane2<8, NREAL, PHI>), g, b, r.lds_bytes, s, pl, a);
+  } else {
+    if constexpr (NREAL == 2 && PHI == 0) hipLaunchKernelGGL((k_sf_plane2<16, NREAL, PHI>), g, b, r.lds_bytes, s, pl, a);
+  }
+}
+static_assert(sf2_lds_bytes<3, 0>(4096, 512) <= SF2_LDS_LIMIT && sf2_lds_bytes<2, 1>(4096, 512) <= SF2_LDS_LIMIT && sf2_lds_bytes<2, 0>(8192, 512) <= SF2_LDS_LIMIT &&
+              sf2_lds_bytes<0, 1>(8192, 1024) <= SF2_LDS_LIMIT && sf2_lds_bytes<3, 0>(8192, 512) > SF2_LDS_LIMIT && sf2_lds_bytes<1, 1>(8192, 512) > SF2_LDS_LIMIT,
+              "which rows take the row route (DESIGN.md section 5w)");
+static_assert(sf2_tmax<8, 3, 0>() == 512 && sf2_tmax<8, 2, 1>() == 512 && sf2_tmax<16, 2, 0>() == 512 && sf2_tmax<8, 1, 0>() == 1024 && sf2_tmax<4, 2, 0>() == 1024,
+              "sf2_route's thread counts are the kernels' launch bounds");
+static void sf2_launch(hipStream_t s, int nblk, const Sf2Route& r, const SfPlanes& pl, const Sf2Args& a) {
+  switch (a.nreal * 2 + a.phi) {
+    case 2: sf2_launch_fields<1, 0>(s, nblk, r, pl, a); break;
+    case 4: sf2_launch_fields<2, 0>(s, nblk, r, pl, a); break;
+    case 6: sf2_launch_fields<3, 0>(s, nblk, r, pl, a); break;
+    case 1: sf2_launch_fields<0, 1>(s, nblk, r, pl, a); break;
+    case 3: sf2_launch_fields<1, 1>(s, nblk, r, pl, a); break;
+    default: sf2_launch_fields<2, 1>(s, nblk, r, pl, a);
+  }
 }
 static int hist_plane_grid(size_t n) { return (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024); }
 
@@ -5348,11 +5441,16 @@ static SfMap sf_map(int NF, int nfields, const int* canon, int ntriples) {
 }
 static int sf_plane_grid(int rows) { return rows < 1024 ? rows : 1024; }
 // the partials of a call: `count` doubles, allocated on first use and grown by the largest call (NQ_SF_PART_MAX_BYTES bounds it)
+static int sf_reserve_part(nq_ctx* c, size_t count, const char* fn);
 static int sf_reserve(nq_ctx* c, size_t count) {
   if (!c->sf_tab) {
     ALLOC(c, c->sf_tab, (size_t)SF_MAX_SEPS * sf_ncols<SF_MAX_FIELDS>());
     ALLOC(c, c->sf_seps, (size_t)SF_MAX_SEPS);
   }
+  return sf_reserve_part(c, count, "nq_structure");
+}
+// the partials alone: nq_structure2 shares them (its table is its own)
+static int sf_reserve_part(nq_ctx* c, size_t count, const char* fn) {
   if (count <= c->sf_part_count) return 0;
   if (c->sf_part_raw) {
     const int rc = nq_sync(c);                           // a launch of the last call may still write them
@@ -5371,7 +5469,7 @@ static int sf_reserve(nq_ctx* c, size_t count) {
   void* p = nullptr;
   if (hipMalloc(&p, count * sizeof(double)) != hipSuccess) {
     (void)hipGetLastError();
-    NQ_FAIL(c, -5, "nq_structure: cannot allocate %zu bytes of device memory for the workgroup partials", count * sizeof(double));
+    NQ_FAIL(c, -5, "%s: cannot allocate %zu bytes of device memory for the workgroup partials", fn, count * sizeof(double));
   }
   c->allocs.push_back(p);
   c->bytes += (long long)(count * sizeof(double));
@@ -5488,6 +5586,222 @@ int nq_structure_read(nq_ctx* c, long long* samples, double* out) {
   HIPCHK(c, hipSetDevice(c->device));
   *samples = g.samples;
   HIPCHK(c, hipMemcpyAsync(out, c->sf_tab, sizeof(double) * g.nsep * (g.nf * SF_COLS + g.ntri), hipMemcpyDeviceToHost, c->stream));
+  return nq_sync(c);
+}
+
+// ---- structure functions at two-dimensional separations (csrc/nq_sf2.hpp) -----------------------------------
+static_assert(SF2_MAX_VECS == NQ_SF2_MAX_VECS, "limits of nq_structure2");
+static_assert((size_t)64 * NQ_SF2_MAX_VECS * sf_ncols<SF_MAX_FIELDS>() * sizeof(double) <= NQ_SF_PART_MAX_BYTES, "64 workgroups of the longest list fit the partials");
+// The call in the kernels' terms: fields and triples through sf_plan (canon, nreal, phi, the triples in slots); the vectors checked,
+// r_x brought to [0, cols), sorted by (r_y, r_x) into `sorted` with their position in the caller's list; the rotated pair in slots.
+// nullptr, or what is wrong.
+static const char* sf2_plan(int rows, int cols, int nfields, const bool* cplx, int nvec, const int* vecs, const double* proj, int pa, int pb,
+                            int ntriples, const int* triples, Sf2Args* a, int* canon, Sf2Vec* sorted) {
+  static char msg[256];
+  static const int one = 1;
+  SfArgs x;
+  if (const char* bad = sf_plan(cols, nfields, cplx, 1, &one, ntriples, triples, &x, canon)) return bad;
+  *a = Sf2Args();
+  a->nreal = x.nreal;
+  a->phi = x.phi;
+  a->ntri = x.ntri;
+  for (int k = 0; k < x.ntri; ++k) a->tri |= sf2_tri_pack(k, x.ta[k], x.tb[k], x.tc[k]);
+  if (!vecs || nvec < 1 || nvec > SF2_MAX_VECS) return "1 to 256 vectors";
+  for (int i = 0; i < nvec; ++i) {
+    const int rx = vecs[2 * i], ry = vecs[2 * i + 1];
+    if (rx <= -cols || rx >= cols || ry < 0 || ry >= rows || (rx == 0 && ry == 0)) {
+      snprintf(msg, sizeof(msg), "vector (%d, %d) at position %d (r_x in [%d, %d], r_y in [0, %d], not (0, 0))", rx, ry, i, -(cols - 1), cols - 1, rows - 1);
+      return msg;
+    }
+    sorted[i].rx = rx < 0 ? rx + cols : rx;
+    sorted[i].ry = ry;
+    sorted[i].slot = i;
+    sorted[i].pad = 0;
+  }
+  std::sort(sorted, sorted + nvec, [](const Sf2Vec& p, const Sf2Vec& q) { return p.ry != q.ry ? p.ry < q.ry : (p.rx != q.rx ? p.rx < q.rx : p.slot < q.slot); });
+  for (int i = 1; i < nvec; ++i)
+    if (sorted[i].rx == sorted[i - 1].rx && sorted[i].ry == sorted[i - 1].ry) {
+      snprintf(msg, sizeof(msg), "the vectors at positions %d and %d are one vector (or one and its periodic image r_x - nx)", sorted[i - 1].slot, sorted[i].slot);
+      return msg;
+    }
+  a->nvec = nvec;
+  a->pa = a->pb = -1;
+  if (!proj) {
+    if (pa != -1 || pb != -1) return "proj_a, proj_b without proj (NULL goes with -1, -1)";
+  } else {
+    if (pa < 0 || pa >= nfields || pb < 0 || pb >= nfields) return "proj_a, proj_b are indices into the field list";
+    if (pa == pb) return "the projection names one field twice";
+    if (cplx[pa] || cplx[pb]) return "the projection rotates two real fields, not the complex one";
+    for (int i = 0; i < 2 * nvec; ++i)
+      if (!std::isfinite(proj[i])) return "proj holds a non-finite value";
+    a->pa = canon[pa];
+    a->pb = canon[pb];
+  }
+  return nullptr;
+}
+// `bytes` of device memory in *raw (counted, owned by the context), grown by the largest call; a failure leaves the old buffer
+static int sf2_grow(nq_ctx* c, void** raw, size_t* have, size_t bytes, const char* what) {
+  if (bytes <= *have) return 0;
+  void* p = nullptr;
+  if (hipMalloc(&p, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    NQ_FAIL(c, -5, "nq_structure2: cannot allocate %zu bytes of device memory for %s", bytes, what);
+  }
+  if (*raw) {
+    const int rc = nq_sync(c);                           // a launch of the last call may still use it
+    if (rc) {
+      (void)hipFree(p);
+      return rc;
+    }
+    for (size_t i = 0; i < c->allocs.size(); ++i)
+      if (c->allocs[i] == *raw) {
+        c->allocs.erase(c->allocs.begin() + i);
+        break;
+      }
+    (void)hipFree(*raw);
+    c->bytes -= (long long)*have;
+  }
+  c->allocs.push_back(p);
+  c->bytes += (long long)bytes;
+  *raw = p;
+  *have = bytes;
+  return 0;
+}
+static int alloc_all_or_none(nq_ctx* c, std::vector<std::pair<void**, size_t>>& want, const char* fn);
+
+int nq_structure2(nq_ctx* c, int nfields, const int* fields, int nvec, const int* vecs, const double* proj, int proj_a, int proj_b,
+                  int ntriples, const int* triples, int accumulate) {
+  NQ_SINGLE_RANK(c, "nq_structure2");
+  if (!fields || nfields < 1 || nfields > SF_MAX_FIELDS) NQ_FAIL(c, -1, "nq_structure2: %d fields (1 to %d)", nfields, SF_MAX_FIELDS);
+  bool cplx[SF_MAX_FIELDS] = {};
+  for (int i = 0; i < nfields; ++i) {
+    cplx[i] = fields[i] == NQ_SF_PHI;
+    if ((cplx[i] || is_flow(fields[i])) && !c->kernel_family)
+      NQ_FAIL(c, -1, "nq_structure2: field %d (NQ_FLOW_*, NQ_SF_PHI) on a QGModel context: its plane route has q and its passive scalar only (DESIGN.md section 7)", fields[i]);
+    if (!cplx[i] && !is_flow(fields[i]) && hist_slot(c, fields[i]) < 0)
+      NQ_FAIL(c, -1, "nq_structure2: field %d is not available here (Kernel family: NQ_PDF_Q, NQ_PDF_QPSI, NQ_PDF_PHI2, the NQ_FLOW_* fields and NQ_SF_PHI; QGModel: NQ_PDF_Q, with its passive scalar NQ_PDF_C)", fields[i]);
+    for (int k = 0; k < i; ++k)
+      if (fields[k] == fields[i]) NQ_FAIL(c, -1, "nq_structure2: field %d listed twice", fields[i]);
+  }
+  if (c->kernel_family ? !c->have_phi : !c->have_q) NQ_FAIL(c, -4, "nq_structure2: %s has not been called", c->kernel_family ? "set_phi" : "set_q");
+  const int N = c->N;
+  Sf2Args a;
+  int canon[SF_MAX_FIELDS] = {};
+  Sf2Vec sorted[SF2_MAX_VECS];
+  if (const char* bad = sf2_plan(N, N, nfields, cplx, nvec, vecs, proj, proj_a, proj_b, ntriples, triples, &a, canon, sorted)) NQ_FAIL(c, -1, "nq_structure2: %s", bad);
+  nq_ctx::Sf2Cfg cfg;
+  cfg.nf = nfields;
+  cfg.nvec = nvec;
+  cfg.ntri = ntriples;
+  cfg.pa = proj_a;
+  cfg.pb = proj_b;
+  cfg.has_proj = proj != nullptr;
+  for (int i = 0; i < nfields; ++i) cfg.fields[i] = fields[i];
+  for (int i = 0; i < 2 * nvec; ++i) cfg.vecs[i] = vecs[i];
+  for (int i = 0; proj && i < 2 * nvec; ++i) cfg.proj[i] = proj[i];
+  for (int k = 0; k < 3 * ntriples; ++k) cfg.tri[k] = triples[k];
+  if (accumulate) {
+    const nq_ctx::Sf2Cfg& o = c->sf2_cfg;
+    bool same = c->sf2_tab && o.samples > 0 && o.nf == cfg.nf && o.nvec == cfg.nvec && o.ntri == cfg.ntri && o.pa == cfg.pa && o.pb == cfg.pb && o.has_proj == cfg.has_proj;
+    for (int i = 0; same && i < nfields; ++i) same = o.fields[i] == cfg.fields[i];
+    for (int i = 0; same && i < 2 * nvec; ++i) same = o.vecs[i] == cfg.vecs[i] && (!proj || memcmp(&o.proj[i], &cfg.proj[i], sizeof(double)) == 0);
+    for (int k = 0; same && k < 3 * ntriples; ++k) same = o.tri[k] == cfg.tri[k];
+    if (!same) NQ_FAIL(c, -1, "nq_structure2: accumulate = 1 needs the fields, vectors, projection and triples of the call that zeroed the table");
+    cfg.samples = o.samples;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const int nout = nfields * SF_COLS + ntriples;
+  const Sf2Route route = sf2_route(N, a.nreal, a.phi);
+  const int nblk = sf2_grid(N, nvec, route.nc);
+  if (!c->sf2_tab) {
+    std::vector<std::pair<void**, size_t>> want;
+    want.push_back({(void**)&c->sf2_tab, sizeof(double) * SF2_MAX_VECS * sf_ncols<SF_MAX_FIELDS>()});
+    want.push_back({(void**)&c->sf2_vecs, sizeof(Sf2Vec) * SF2_MAX_VECS});
+    want.push_back({(void**)&c->sf2_proj, sizeof(double) * 2 * SF2_MAX_VECS});
+    const int rc = alloc_all_or_none(c, want, "nq_structure2");
+    if (rc) return rc;
+  }
+  {
+    const int rc = sf_reserve_part(c, (size_t)nblk * nvec * route.nc, "nq_structure2");
+    if (rc) return rc;
+  }
+  const size_t plane = (size_t)N * N;
+  if (c->kernel_family) {
+    const int rc = sf2_grow(c, &c->sf2_planes, &c->sf2_planes_count, (size_t)(a.nreal + 2 * a.phi) * plane * sizeof(double), "the physical planes");
+    if (rc) return rc;
+  }
+  a.part = c->sf_part;
+  a.vecs = c->sf2_vecs;
+  a.proj = proj ? c->sf2_proj : nullptr;
+  for (int i = 0; i < nvec; ++i) c->sf2_vecs_host[i] = sorted[i];
+  HIPCHK(c, hipMemcpyAsync(c->sf2_vecs, c->sf2_vecs_host, sizeof(Sf2Vec) * nvec, hipMemcpyHostToDevice, c->stream));
+  if (proj) {
+    for (int i = 0; i < 2 * nvec; ++i) c->sf2_proj_host[i] = proj[i];
+    HIPCHK(c, hipMemcpyAsync(c->sf2_proj, c->sf2_proj_host, sizeof(double) * 2 * nvec, hipMemcpyHostToDevice, c->stream));
+  }
+  SfPlanes pl = {};
+  pl.rows = pl.cols = N;
+  if (!c->kernel_family) {
+    int mask = 0;
+    for (int i = 0; i < nfields; ++i) mask |= 1 << hist_slot(c, fields[i]);
+    const double* qc[2];
+    hist_qg_planes(c, mask, &qc[0], &qc[1]);
+    for (int i = 0; i < nfields; ++i) {
+      pl.p[canon[i]] = qc[hist_slot(c, fields[i])];
+      pl.stride[canon[i]] = 1;
+    }
+  } else {
+    double* pool = static_cast<double*>(c->sf2_planes);
+    for (int i = 0; i < nfields; ++i) {                 // the real planes in slot order, then the complex one
+      pl.p[canon[i]] = pool + (size_t)canon[i] * plane;
+      pl.stride[canon[i]] = cplx[i] ? 2 : 1;
+    }
+    if (nfields <= flow_nv_of(c)) {
+      FlowSel sel = flow_sel_none(c);
+      Sf2Store st = {};
+      for (int i = 0; i < nfields; ++i) {
+        if (cplx[i]) {
+          sel.phi = 1;
+          st.phi = reinterpret_cast<cd*>(pool + (size_t)canon[i] * plane);
+        } else {
+          sel.code[canon[i]] = fields[i];
+          st.re[canon[i]] = pool + (size_t)canon[i] * plane;
+        }
+      }
+      launch_xflow_store(c, sel, st);
+    } else {
+      for (int i = 0; i < nfields; ++i) {               // one value per launch, in the launch's slot 0, into that field's plane
+        FlowSel sel = flow_sel_none(c);
+        Sf2Store st = {};
+        if (cplx[i]) {
+          sel.phi = 1;
+          st.phi = reinterpret_cast<cd*>(pool + (size_t)canon[i] * plane);
+        } else {
+          sel.code[0] = fields[i];
+          st.re[0] = pool + (size_t)canon[i] * plane;
+        }
+        launch_xflow_store(c, sel, st);
+      }
+    }
+  }
+  sf2_launch(c->stream, nblk, route, pl, a);
+  const int tgrid = (nvec * route.nc + SF_TOTAL_ENTRIES - 1) / SF_TOTAL_ENTRIES;
+  hipLaunchKernelGGL(k_sf_total, dim3(tgrid), dim3(SF_TOTAL_RUNS * SF_TOTAL_ENTRIES), 0, c->stream, (const double*)c->sf_part, nblk, nvec, route.nc,
+                     sf_map(route.nc == sf_ncols<1>() ? 1 : (route.nc == sf_ncols<2>() ? 2 : 3), nfields, canon, ntriples), nout, accumulate, c->sf2_tab);
+  HIPCHK(c, hipGetLastError());
+  ++cfg.samples;
+  c->sf2_cfg = cfg;
+  return 0;
+}
+
+int nq_structure2_read(nq_ctx* c, long long* samples, double* out) {
+  NQ_SINGLE_RANK(c, "nq_structure2_read");
+  if (!samples || !out) NQ_FAIL(c, -1, "nq_structure2_read: null output");
+  const nq_ctx::Sf2Cfg& g = c->sf2_cfg;
+  if (!c->sf2_tab || g.nf == 0) NQ_FAIL(c, -4, "nq_structure2_read: no nq_structure2 call yet");
+  HIPCHK(c, hipSetDevice(c->device));
+  *samples = g.samples;
+  HIPCHK(c, hipMemcpyAsync(out, c->sf2_tab, sizeof(double) * g.nvec * (g.nf * SF_COLS + g.ntri), hipMemcpyDeviceToHost, c->stream));
   return nq_sync(c);
 }
 
@@ -6679,6 +6993,52 @@ int nq_any_increments(nq_any* e, int nfields, const void* const* planes, const i
   hipLaunchKernelGGL(k_sf_total, dim3((nsep * nc + SF_TOTAL_ENTRIES - 1) / SF_TOTAL_ENTRIES), dim3(SF_TOTAL_RUNS * SF_TOTAL_ENTRIES), 0, e->stream, (const double*)a.part, nblk, nsep, nc, sf_map(SF_MAX_FIELDS, nfields, canon, ntriples), nout, 0, tab);
   ANYCHK(e, hipGetLastError());
   ANYCHK(e, hipMemcpyAsync(out, tab, sizeof(double) * nsep * nout, hipMemcpyDeviceToHost, e->stream));
+  return nq_any_sync(e);
+}
+// The same at two-dimensional separations: nq_structure2's plane kernels on engine planes
+int nq_any_increments2(nq_any* e, int nfields, const void* const* planes, const int* what, int rows, int cols, int nvec, const int* vecs,
+                       const double* proj, int proj_a, int proj_b, int ntriples, const int* triples, double* out) {
+  if (!e || !planes || !what || !out || rows < 1 || cols < 2) return -1;
+  if (nfields < 1 || nfields > SF_MAX_FIELDS) ANYFAIL(e, -1, "nq_any_increments2: %d fields (1 to %d)", nfields, SF_MAX_FIELDS);
+  bool cplx[SF_MAX_FIELDS] = {};
+  for (int i = 0; i < nfields; ++i) {
+    if (!planes[i]) ANYFAIL(e, -1, "nq_any_increments2: plane %d is null", i);
+    if (what[i] != 0 && what[i] != 2) ANYFAIL(e, -1, "nq_any_increments2: what[%d] = %d (0: Re, 2: complex)", i, what[i]);
+    cplx[i] = what[i] == 2;
+  }
+  Sf2Args a;
+  int canon[SF_MAX_FIELDS] = {};
+  Sf2Vec sorted[SF2_MAX_VECS];
+  if (const char* bad = sf2_plan(rows, cols, nfields, cplx, nvec, vecs, proj, proj_a, proj_b, ntriples, triples, &a, canon, sorted))
+    ANYFAIL(e, -1, "nq_any_increments2: %s", bad);
+  ANYCHK(e, hipSetDevice(e->device));
+  const Sf2Route route = sf2_route(cols, a.nreal, a.phi);
+  const int nblk = sf2_grid(rows, nvec, route.nc), nout = nfields * SF_COLS + ntriples;
+  double *tab = nullptr, *dproj = nullptr;
+  Sf2Vec* dvecs = nullptr;
+  AnyScratch tmp;
+  ANYCHK(e, tmp.get(&a.part, (size_t)nblk * nvec * route.nc));
+  ANYCHK(e, tmp.get(&tab, (size_t)nvec * nout));
+  ANYCHK(e, tmp.get(&dvecs, (size_t)nvec));
+  ANYCHK(e, hipMemcpyAsync(dvecs, sorted, sizeof(Sf2Vec) * nvec, hipMemcpyHostToDevice, e->stream));
+  a.vecs = dvecs;
+  if (proj) {
+    ANYCHK(e, tmp.get(&dproj, (size_t)2 * nvec));
+    ANYCHK(e, hipMemcpyAsync(dproj, proj, sizeof(double) * 2 * nvec, hipMemcpyHostToDevice, e->stream));
+    a.proj = dproj;
+  }
+  SfPlanes pl = {};
+  for (int i = 0; i < nfields; ++i) {
+    pl.p[canon[i]] = reinterpret_cast<const double*>(planes[i]);
+    pl.stride[canon[i]] = 2;
+  }
+  pl.rows = rows;
+  pl.cols = cols;
+  sf2_launch(e->stream, nblk, route, pl, a);
+  hipLaunchKernelGGL(k_sf_total, dim3((nvec * route.nc + SF_TOTAL_ENTRIES - 1) / SF_TOTAL_ENTRIES), dim3(SF_TOTAL_RUNS * SF_TOTAL_ENTRIES), 0, e->stream, (const double*)a.part,
+                     nblk, nvec, route.nc, sf_map(route.nc == sf_ncols<1>() ? 1 : (route.nc == sf_ncols<2>() ? 2 : 3), nfields, canon, ntriples), nout, 0, tab);
+  ANYCHK(e, hipGetLastError());
+  ANYCHK(e, hipMemcpyAsync(out, tab, sizeof(double) * nvec * nout, hipMemcpyDeviceToHost, e->stream));
   return nq_any_sync(e);
 }
 int nq_any_set_elem(nq_any* e, void* plane, long long index, double re, double im) {

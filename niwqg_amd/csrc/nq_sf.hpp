@@ -74,7 +74,8 @@ __device__ __forceinline__ void sf_zero(double (&acc)[NF][SF_COLS], double (&tri
 // nw * NC doubles of LDS; the caller alternates two of them, so one barrier per call suffices (a buffer is rewritten two calls
 // later, after the barrier of the call in between, which its readers reach only after their reads).
 template <int NF>
-__device__ __forceinline__ void sf_block_store(double (&acc)[NF][SF_COLS], double (&tri)[sf_ntri<NF>()], double* buf, double* __restrict__ dst) {
+__device__ __forceinline__ void sf_block_store(double (&acc)[NF][SF_COLS], double (&tri)[sf_ntri<NF>()], double* buf, double* __restrict__ dst,
+                                               bool add = false) {          // add: on top of dst (the same workgroup wrote it before)
   constexpr int NC = sf_ncols<NF>();
   const int tid = threadIdx.x, wave = tid >> 6, nw = (int)blockDim.x >> 6;
 #pragma unroll
@@ -87,7 +88,7 @@ __device__ __forceinline__ void sf_block_store(double (&acc)[NF][SF_COLS], doubl
   if (tid < NC) {
     double x = 0.0;
     for (int w = 0; w < nw; ++w) x += buf[w * NC + tid];
-    dst[tid] = x;
+    dst[tid] = add ? dst[tid] + x : x;
   }
 }
 
