@@ -317,6 +317,40 @@ int nq_structure2(nq_ctx* ctx, int nfields, const int* fields, int nvec, const i
                   const int* triples /* ntriples x 3 indices into fields */, int accumulate);
 int nq_structure2_read(nq_ctx* ctx, long long* samples, double* out /* nvec x (9 nfields + ntriples) raw sums */);
 
+/* PDFs of the field increments: COUNTS of the increments whose moments nq_structure and nq_structure2 sum,
+ * per separation (or vector) and field.  fields, seps, vecs, proj, proj_a, proj_b: exactly as those two calls take them (no
+ * triples).  A real field is binned signed; NQ_SF_PHI is binned as |d phi| = sqrt(Re^2 + Im^2).  With proj the pair is rotated first
+ * (L in proj_a's table, T in proj_b's).  The bin rule is nq_field_hist's, with one range per (separation, field): lo, hi = n x
+ * nfields doubles each (finite, lo < hi), s = bins / (hi - lo) formed once on the host; bins in [1, NQ_IPDF_MAX_BINS].
+ *
+ * nq_increment_range / nq_increment_range2: the range pass: out[(i nfields + f) 2] = sum d (NQ_SF_PHI: sum |d phi|), [.. + 1] = sum
+ *   d^2 (sum |d phi|^2) of separation i and field f over the plane, from nq_structure's / nq_structure2's kernels into a table of this
+ *   feature: the running tables, sample counts and configurations of those two calls are not touched (the workgroup partials are
+ *   shared, within NQ_SF_PART_MAX_BYTES; nq_increment_range2 stores the Kernel family's values to the planes nq_structure2 uses).
+ * nq_increment_hist / nq_increment_hist2: one state into the count table on the device; accumulate = 0 zeroes it first, 1 adds to
+ *   it and needs the fields, separations or vectors, projection, ranges and bins of the call that zeroed it.  Nothing is copied
+ *   to the host.  One table serves both calls.  On the fused grids the Kernel family's nq_increment_hist runs ONE row pass
+ *   (k_x_flow_ipdf: the value rows in LDS, a table of 32-bit counters per separation in LDS, flushed to the 64-bit table with
+ *   integer atomics); at nx = 8192 one launch per field, every combination of fields included.  QGModel and nq_increment_hist2
+ *   go through physical planes (k_ipdf_plane).
+ * nq_increment_hist_read: *samples = states in the table, out = n x nfields x (bins + 3) counts in the caller's field order: the
+ *   bins, below, above, NaN.
+ * Integer counters only: bit-reproducible.  The buffers are allocated by the first call, the count table is grown by the largest
+ * one, NQ_IPDF_DEVICE_BYTES at most in all beside what nq_structure / nq_structure2 own (counted by nq_device_bytes, freed with the
+ * context).  Reads the state, writes only these buffers.  -1: bad arguments, a field the model lacks, accumulate = 1 after
+ * another configuration; -4: slab contexts, nothing set yet, no table yet; -5: an allocation failed, everything as it was.      */
+#define NQ_IPDF_MAX_BINS NQ_PDF_MAX_BINS
+#define NQ_IPDF_DEVICE_BYTES (NQ_SF2_MAX_VECS * (NQ_SF_MAX_FIELDS * (NQ_IPDF_MAX_BINS + 3) * 8 + NQ_SF_MAX_FIELDS * 3 * 8 + 16 + 16 + (NQ_SF_MAX_FIELDS * NQ_SF_COLS + NQ_SF_MAX_TRIPLES) * 8) + NQ_SF_MAX_SEPS * 4)
+int nq_increment_range(nq_ctx* ctx, int nfields, const int* fields, int nsep, const int* seps, double* out /* nsep x nfields x 2 */);
+int nq_increment_range2(nq_ctx* ctx, int nfields, const int* fields, int nvec, const int* vecs /* nvec x 2: r_x, r_y */,
+                        const double* proj /* NULL or nvec x 2: c_x, c_y */, int proj_a, int proj_b, double* out /* nvec x nfields x 2 */);
+int nq_increment_hist(nq_ctx* ctx, int nfields, const int* fields, int nsep, const int* seps, const double* lo /* nsep x nfields */,
+                      const double* hi, int bins, int accumulate);
+int nq_increment_hist2(nq_ctx* ctx, int nfields, const int* fields, int nvec, const int* vecs /* nvec x 2: r_x, r_y */,
+                       const double* proj /* NULL or nvec x 2: c_x, c_y */, int proj_a, int proj_b, const double* lo /* nvec x nfields */,
+                       const double* hi, int bins, int accumulate);
+int nq_increment_hist_read(nq_ctx* ctx, long long* samples, unsigned long long* out /* n x nfields x (bins + 3) counts */);
+
 /* Lagrangian particles, single-rank contexts only (slab contexts refuse every call with -4).
  * After every step of nq_step the library moves each particle one classical RK4 step through U_tot = (U + u, v), u = -d psi/dy,
  * v = d psi/dx of the ph the context holds, linear in time between U0 (start of the step) and U1 (after it):
@@ -874,6 +908,12 @@ int nq_any_increments(nq_any* eng, int nfields, const void* const* planes, const
 int nq_any_increments2(nq_any* eng, int nfields, const void* const* planes, const int* what /* 0 Re, 2 complex */, int rows, int cols,
                        int nvec, const int* vecs, const double* proj, int proj_a, int proj_b, int ntriples, const int* triples,
                        double* out);
+/* PDFs of the increments on engine planes (nq_increment_hist2 above: vectors, projection, ranges, bin rule and return codes;
+ * planes and what as nq_any_increments2 takes them).  out: the counts of this one state, nvec x nfields x (bins + 3).  An
+ * x-separation r is the vector (r, 0).  Synchronous. */
+int nq_any_increment_hist(nq_any* eng, int nfields, const void* const* planes, const int* what /* 0 Re, 2 complex */, int rows, int cols,
+                          int nvec, const int* vecs, const double* proj, int proj_a, int proj_b, const double* lo, const double* hi,
+                          int bins, unsigned long long* out);
 /* Lagrangian particles on engine planes (the RK4 step and interpolation of nq_particles_attach above): pos holds n complex
  * x + i y; U0, U1 and plane are (nx, nx) complex planes, velocity planes as u + i v; out[i] = plane at pos[i] (real and
  * imaginary parts interpolated each) */

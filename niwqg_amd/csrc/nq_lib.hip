@@ -18,6 +18,7 @@
 #include "nq_flow.hpp"
 #include "nq_sf.hpp"
 #include "nq_sf2.hpp"
+#include "nq_ipdf.hpp"
 #include "nq_forcing.hpp"
 
 using namespace nq;
@@ -267,6 +268,23 @@ struct nq_ctx {
     double proj[2 * SF2_MAX_VECS] = {};
     long long samples = 0;
   } sf2_cfg;
+  // PDFs of the increments (nq_increment_hist, nq_increment_hist2, nq_increment_range*; csrc/nq_ipdf.hpp): the 64-bit count table
+  // (grown by the largest call), the ranges, the separations or vectors and the projection on the device with their staging copies,
+  // the table of the range pass's sums, and the call that zeroed the count table (one table for both kinds of call)
+  void* ipdf_tab = nullptr;
+  size_t ipdf_tab_bytes = 0;
+  double *ipdf_rng = nullptr, *ipdf_proj = nullptr, *ipdf_sums = nullptr;
+  int* ipdf_seps = nullptr;
+  Sf2Vec* ipdf_vecs = nullptr;
+  int ipdf_seps_host[SF_MAX_SEPS] = {};
+  Sf2Vec ipdf_vecs_host[SF2_MAX_VECS] = {};
+  double ipdf_proj_host[2 * SF2_MAX_VECS] = {}, ipdf_rng_host[3 * SF_MAX_FIELDS * SF2_MAX_VECS] = {};
+  struct IpdfCfg {
+    int kind = 0, nf = 0, fields[SF_MAX_FIELDS] = {}, n = 0, vecs[2 * SF2_MAX_VECS] = {}, pa = -1, pb = -1, bins = 0;   // kind 1: separations (in vecs[0..n)), 2: vectors
+    bool has_proj = false;
+    double proj[2 * SF2_MAX_VECS] = {}, lo[SF_MAX_FIELDS * SF2_MAX_VECS] = {}, hi[SF_MAX_FIELDS * SF2_MAX_VECS] = {};
+    long long samples = 0;
+  } ipdf_cfg;
   cd *tr_h = nullptr, *tr_f = nullptr;               // its planes on slab contexts (two half, one full-width; P == 1: scr_*)
   double *carryW = nullptr, *carryQ = nullptr;    // spectral sums of the state at the start of the next step
   double *gradS1 = nullptr, *acc = nullptr;       // stale-aware sum wv2|phih_grad|^2 ; Ke,Pw,Kw increments
@@ -2539,6 +2557,19 @@ static void launch_xflow_store_t(nq_ctx* c, const FlowSel& sel, const Sf2Store& 
 static void launch_xflow_store(nq_ctx* c, const FlowSel& sel, const Sf2Store& st) {
   if (c->p.model == NQ_MODEL_COUPLED) launch_xflow_store_t<MODE_COUPLED>(c, sel, st);
   else launch_xflow_store_t<MODE_UNCOUPLED>(c, sel, st);
+}
+// PDFs of the increments (csrc/nq_ipdf.hpp): the same row pass with the value rows and a table of counters per separation in LDS
+template <int MODE>
+static void launch_xflow_ipdf_t(nq_ctx* c, const FlowSel& sel, const IpdfArgs& a) {
+  with_row_size(c->N, [&](auto n) {
+    constexpr int N = decltype(n)::value;
+    typedef XPlan<N> X;
+    hipLaunchKernelGGL((k_x_flow_ipdf<N, MODE>), dim3(c->Nloc / X::C), dim3(X::THREADS), ipdf_lds_bytes<N>(a.nreal, a.phi, a.bins), c->stream, c->mQ, c->mQw, c->mU, c->mP, c->mPhi, c->mPhiy, c->twx, c->kk, sel, a);
+  });
+}
+static void launch_xflow_ipdf(nq_ctx* c, const FlowSel& sel, const IpdfArgs& a) {
+  if (c->p.model == NQ_MODEL_COUPLED) launch_xflow_ipdf_t<MODE_COUPLED>(c, sel, a);
+  else launch_xflow_ipdf_t<MODE_UNCOUPLED>(c, sel, a);
 }
 // which kernel serves rows of `cols` elements of these fields: the row route (points per thread, threads, LDS bytes) or the global
 // one.  The row route runs workgroups of up to 1024 threads with 1, 2, 4 or 8 points each; where the base values and the running
@@ -5442,12 +5473,12 @@ static SfMap sf_map(int NF, int nfields, const int* canon, int ntriples) {
 static int sf_plane_grid(int rows) { return rows < 1024 ? rows : 1024; }
 // the partials of a call: `count` doubles, allocated on first use and grown by the largest call (NQ_SF_PART_MAX_BYTES bounds it)
 static int sf_reserve_part(nq_ctx* c, size_t count, const char* fn);
-static int sf_reserve(nq_ctx* c, size_t count) {
+static int sf_reserve(nq_ctx* c) {
   if (!c->sf_tab) {
     ALLOC(c, c->sf_tab, (size_t)SF_MAX_SEPS * sf_ncols<SF_MAX_FIELDS>());
     ALLOC(c, c->sf_seps, (size_t)SF_MAX_SEPS);
   }
-  return sf_reserve_part(c, count, "nq_structure");
+  return 0;
 }
 // the partials alone: nq_structure2 shares them (its table is its own)
 static int sf_reserve_part(nq_ctx* c, size_t count, const char* fn) {
@@ -5476,6 +5507,68 @@ static int sf_reserve_part(nq_ctx* c, size_t count, const char* fn) {
   c->sf_part_raw = p;
   c->sf_part = static_cast<double*>(p);
   c->sf_part_count = count;
+  return 0;
+}
+
+// The launches of one call: the sums of the current state into `tab` (nsep rows of 9 nfields + ntriples; on top of it with
+// `accumulate`), through the shared partials.  dseps / hseps: the separations on the device and their staging copy.  The caller has
+// checked the call (sf_plan: a, canon) and owns `tab`: nq_structure's running table, or the range pass of nq_increment_range.
+static int sf_sums_into(nq_ctx* c, const char* fn, int nfields, const int* fields, const bool* cplx, SfArgs a, const int* canon, int nsep,
+                        const int* seps, int ntriples, const int* triples, int accumulate, double* tab, int* dseps, int* hseps) {
+  const bool one = c->kernel_family && flow_nv_of(c) == 1;        // one value per thread: a launch per field
+  const int nout = nfields * SF_COLS + ntriples;
+  const int NF = one ? 1 : SF_MAX_FIELDS, nc = one ? sf_ncols<1>() : sf_ncols<SF_MAX_FIELDS>();
+  const int nblk = c->kernel_family ? xdiag_blocks(c) : sf_plane_grid(c->N);
+  {
+    const int rc = sf_reserve_part(c, (size_t)nblk * nsep * nc, fn);
+    if (rc) return rc;
+  }
+  a.part = c->sf_part;
+  a.seps = dseps;
+  for (int s = 0; s < nsep; ++s) hseps[s] = seps[s];
+  HIPCHK(c, hipMemcpyAsync(dseps, hseps, sizeof(int) * nsep, hipMemcpyHostToDevice, c->stream));
+  const int tgrid = (nsep * nc + SF_TOTAL_ENTRIES - 1) / SF_TOTAL_ENTRIES;
+  if (!c->kernel_family) {
+    SfPlanes pl = {};
+    int mask = 0;
+    for (int i = 0; i < nfields; ++i) mask |= 1 << hist_slot(c, fields[i]);
+    const double* qc[2];
+    hist_qg_planes(c, mask, &qc[0], &qc[1]);
+    for (int i = 0; i < nfields; ++i) {
+      pl.p[canon[i]] = qc[hist_slot(c, fields[i])];
+      pl.stride[canon[i]] = 1;
+    }
+    pl.rows = pl.cols = c->N;
+    hipLaunchKernelGGL(k_sf_plane, dim3(nblk), dim3(SF_PLANE_THREADS), 0, c->stream, pl, a);
+    hipLaunchKernelGGL(k_sf_total, dim3(tgrid), dim3(SF_TOTAL_RUNS * SF_TOTAL_ENTRIES), 0, c->stream, (const double*)c->sf_part, nblk, nsep, nc, sf_map(NF, nfields, canon, ntriples), nout, accumulate, tab);
+  } else if (!one) {
+    FlowSel sel = flow_sel_none(c);
+    for (int i = 0; i < nfields; ++i)
+      if (!cplx[i]) sel.code[canon[i]] = fields[i];
+    sel.phi = a.phi;
+    launch_xflow_sf(c, sel, a);
+    hipLaunchKernelGGL(k_sf_total, dim3(tgrid), dim3(SF_TOTAL_RUNS * SF_TOTAL_ENTRIES), 0, c->stream, (const double*)c->sf_part, nblk, nsep, nc, sf_map(NF, nfields, canon, ntriples), nout, accumulate, tab);
+  } else {
+    for (int i = 0; i < nfields; ++i) {                 // one field per launch, in the launch's slot 0, into its own columns
+      FlowSel sel = flow_sel_none(c);
+      SfArgs g = a;
+      g.nreal = cplx[i] ? 0 : 1;
+      g.phi = cplx[i] ? 1 : 0;
+      g.ntri = 0;
+      if (!cplx[i]) sel.code[0] = fields[i];
+      sel.phi = g.phi;
+      SfMap m;
+      for (int k = 0; k < sf_ncols<SF_MAX_FIELDS>(); ++k) m.col[k] = k < SF_COLS ? i * SF_COLS + k : -1;
+      for (int k = 0; k < ntriples; ++k)
+        if (triples[3 * k] == i) {                       // (i, i, i): refused above otherwise
+          g.ta[g.ntri] = g.tb[g.ntri] = g.tc[g.ntri] = 0;
+          m.col[SF_COLS + g.ntri++] = nfields * SF_COLS + k;
+        }
+      launch_xflow_sf(c, sel, g);
+      hipLaunchKernelGGL(k_sf_total, dim3(tgrid), dim3(SF_TOTAL_RUNS * SF_TOTAL_ENTRIES), 0, c->stream, (const double*)c->sf_part, nblk, nsep, nc, m, nout, accumulate, tab);
+    }
+  }
+  HIPCHK(c, hipGetLastError());
   return 0;
 }
 
@@ -5520,59 +5613,11 @@ int nq_structure(nq_ctx* c, int nfields, const int* fields, int nsep, const int*
     cfg.samples = o.samples;
   }
   HIPCHK(c, hipSetDevice(c->device));
-  const int nout = nfields * SF_COLS + ntriples;
-  const int NF = one ? 1 : SF_MAX_FIELDS, nc = one ? sf_ncols<1>() : sf_ncols<SF_MAX_FIELDS>();
-  const int nblk = c->kernel_family ? xdiag_blocks(c) : sf_plane_grid(c->N);
   {
-    const int rc = sf_reserve(c, (size_t)nblk * nsep * nc);
+    int rc = sf_reserve(c);
+    if (!rc) rc = sf_sums_into(c, "nq_structure", nfields, fields, cplx, a, canon, nsep, seps, ntriples, triples, accumulate, c->sf_tab, c->sf_seps, c->sf_seps_host);
     if (rc) return rc;
   }
-  a.part = c->sf_part;
-  a.seps = c->sf_seps;
-  for (int s = 0; s < nsep; ++s) c->sf_seps_host[s] = seps[s];
-  HIPCHK(c, hipMemcpyAsync(c->sf_seps, c->sf_seps_host, sizeof(int) * nsep, hipMemcpyHostToDevice, c->stream));
-  const int tgrid = (nsep * nc + SF_TOTAL_ENTRIES - 1) / SF_TOTAL_ENTRIES;
-  if (!c->kernel_family) {
-    SfPlanes pl = {};
-    int mask = 0;
-    for (int i = 0; i < nfields; ++i) mask |= 1 << hist_slot(c, fields[i]);
-    const double* qc[2];
-    hist_qg_planes(c, mask, &qc[0], &qc[1]);
-    for (int i = 0; i < nfields; ++i) {
-      pl.p[canon[i]] = qc[hist_slot(c, fields[i])];
-      pl.stride[canon[i]] = 1;
-    }
-    pl.rows = pl.cols = c->N;
-    hipLaunchKernelGGL(k_sf_plane, dim3(nblk), dim3(SF_PLANE_THREADS), 0, c->stream, pl, a);
-    hipLaunchKernelGGL(k_sf_total, dim3(tgrid), dim3(SF_TOTAL_RUNS * SF_TOTAL_ENTRIES), 0, c->stream, (const double*)c->sf_part, nblk, nsep, nc, sf_map(NF, nfields, canon, ntriples), nout, accumulate, c->sf_tab);
-  } else if (!one) {
-    FlowSel sel = flow_sel_none(c);
-    for (int i = 0; i < nfields; ++i)
-      if (!cplx[i]) sel.code[canon[i]] = fields[i];
-    sel.phi = a.phi;
-    launch_xflow_sf(c, sel, a);
-    hipLaunchKernelGGL(k_sf_total, dim3(tgrid), dim3(SF_TOTAL_RUNS * SF_TOTAL_ENTRIES), 0, c->stream, (const double*)c->sf_part, nblk, nsep, nc, sf_map(NF, nfields, canon, ntriples), nout, accumulate, c->sf_tab);
-  } else {
-    for (int i = 0; i < nfields; ++i) {                 // one field per launch, in the launch's slot 0, into its own columns
-      FlowSel sel = flow_sel_none(c);
-      SfArgs g = a;
-      g.nreal = cplx[i] ? 0 : 1;
-      g.phi = cplx[i] ? 1 : 0;
-      g.ntri = 0;
-      if (!cplx[i]) sel.code[0] = fields[i];
-      sel.phi = g.phi;
-      SfMap m;
-      for (int k = 0; k < sf_ncols<SF_MAX_FIELDS>(); ++k) m.col[k] = k < SF_COLS ? i * SF_COLS + k : -1;
-      for (int k = 0; k < ntriples; ++k)
-        if (triples[3 * k] == i) {                       // (i, i, i): refused above otherwise
-          g.ta[g.ntri] = g.tb[g.ntri] = g.tc[g.ntri] = 0;
-          m.col[SF_COLS + g.ntri++] = nfields * SF_COLS + k;
-        }
-      launch_xflow_sf(c, sel, g);
-      hipLaunchKernelGGL(k_sf_total, dim3(tgrid), dim3(SF_TOTAL_RUNS * SF_TOTAL_ENTRIES), 0, c->stream, (const double*)c->sf_part, nblk, nsep, nc, m, nout, accumulate, c->sf_tab);
-    }
-  }
-  HIPCHK(c, hipGetLastError());
   ++cfg.samples;
   c->sf_cfg = cfg;
   return 0;
@@ -5640,12 +5685,12 @@ static const char* sf2_plan(int rows, int cols, int nfields, const bool* cplx, i
   return nullptr;
 }
 // `bytes` of device memory in *raw (counted, owned by the context), grown by the largest call; a failure leaves the old buffer
-static int sf2_grow(nq_ctx* c, void** raw, size_t* have, size_t bytes, const char* what) {
+static int sf2_grow(nq_ctx* c, void** raw, size_t* have, size_t bytes, const char* what, const char* fn = "nq_structure2") {
   if (bytes <= *have) return 0;
   void* p = nullptr;
   if (hipMalloc(&p, bytes) != hipSuccess) {
     (void)hipGetLastError();
-    NQ_FAIL(c, -5, "nq_structure2: cannot allocate %zu bytes of device memory for %s", bytes, what);
+    NQ_FAIL(c, -5, "%s: cannot allocate %zu bytes of device memory for %s", fn, bytes, what);
   }
   if (*raw) {
     const int rc = nq_sync(c);                           // a launch of the last call may still use it
@@ -5669,75 +5714,14 @@ static int sf2_grow(nq_ctx* c, void** raw, size_t* have, size_t bytes, const cha
 }
 static int alloc_all_or_none(nq_ctx* c, std::vector<std::pair<void**, size_t>>& want, const char* fn);
 
-int nq_structure2(nq_ctx* c, int nfields, const int* fields, int nvec, const int* vecs, const double* proj, int proj_a, int proj_b,
-                  int ntriples, const int* triples, int accumulate) {
-  NQ_SINGLE_RANK(c, "nq_structure2");
-  if (!fields || nfields < 1 || nfields > SF_MAX_FIELDS) NQ_FAIL(c, -1, "nq_structure2: %d fields (1 to %d)", nfields, SF_MAX_FIELDS);
-  bool cplx[SF_MAX_FIELDS] = {};
-  for (int i = 0; i < nfields; ++i) {
-    cplx[i] = fields[i] == NQ_SF_PHI;
-    if ((cplx[i] || is_flow(fields[i])) && !c->kernel_family)
-      NQ_FAIL(c, -1, "nq_structure2: field %d (NQ_FLOW_*, NQ_SF_PHI) on a QGModel context: its plane route has q and its passive scalar only (DESIGN.md section 7)", fields[i]);
-    if (!cplx[i] && !is_flow(fields[i]) && hist_slot(c, fields[i]) < 0)
-      NQ_FAIL(c, -1, "nq_structure2: field %d is not available here (Kernel family: NQ_PDF_Q, NQ_PDF_QPSI, NQ_PDF_PHI2, the NQ_FLOW_* fields and NQ_SF_PHI; QGModel: NQ_PDF_Q, with its passive scalar NQ_PDF_C)", fields[i]);
-    for (int k = 0; k < i; ++k)
-      if (fields[k] == fields[i]) NQ_FAIL(c, -1, "nq_structure2: field %d listed twice", fields[i]);
-  }
-  if (c->kernel_family ? !c->have_phi : !c->have_q) NQ_FAIL(c, -4, "nq_structure2: %s has not been called", c->kernel_family ? "set_phi" : "set_q");
+// The physical planes of a call's fields in the kernels' canonical slots: QGModel's scratch planes (an inverse transform each), or,
+// on the Kernel family, the context's pool, filled by the store pass (grown by the largest call; a failure leaves the old pool)
+static int sf2_planes_of(nq_ctx* c, const char* fn, int nfields, const int* fields, const bool* cplx, const int* canon, int nreal, int phi, SfPlanes* out) {
   const int N = c->N;
-  Sf2Args a;
-  int canon[SF_MAX_FIELDS] = {};
-  Sf2Vec sorted[SF2_MAX_VECS];
-  if (const char* bad = sf2_plan(N, N, nfields, cplx, nvec, vecs, proj, proj_a, proj_b, ntriples, triples, &a, canon, sorted)) NQ_FAIL(c, -1, "nq_structure2: %s", bad);
-  nq_ctx::Sf2Cfg cfg;
-  cfg.nf = nfields;
-  cfg.nvec = nvec;
-  cfg.ntri = ntriples;
-  cfg.pa = proj_a;
-  cfg.pb = proj_b;
-  cfg.has_proj = proj != nullptr;
-  for (int i = 0; i < nfields; ++i) cfg.fields[i] = fields[i];
-  for (int i = 0; i < 2 * nvec; ++i) cfg.vecs[i] = vecs[i];
-  for (int i = 0; proj && i < 2 * nvec; ++i) cfg.proj[i] = proj[i];
-  for (int k = 0; k < 3 * ntriples; ++k) cfg.tri[k] = triples[k];
-  if (accumulate) {
-    const nq_ctx::Sf2Cfg& o = c->sf2_cfg;
-    bool same = c->sf2_tab && o.samples > 0 && o.nf == cfg.nf && o.nvec == cfg.nvec && o.ntri == cfg.ntri && o.pa == cfg.pa && o.pb == cfg.pb && o.has_proj == cfg.has_proj;
-    for (int i = 0; same && i < nfields; ++i) same = o.fields[i] == cfg.fields[i];
-    for (int i = 0; same && i < 2 * nvec; ++i) same = o.vecs[i] == cfg.vecs[i] && (!proj || memcmp(&o.proj[i], &cfg.proj[i], sizeof(double)) == 0);
-    for (int k = 0; same && k < 3 * ntriples; ++k) same = o.tri[k] == cfg.tri[k];
-    if (!same) NQ_FAIL(c, -1, "nq_structure2: accumulate = 1 needs the fields, vectors, projection and triples of the call that zeroed the table");
-    cfg.samples = o.samples;
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  const int nout = nfields * SF_COLS + ntriples;
-  const Sf2Route route = sf2_route(N, a.nreal, a.phi);
-  const int nblk = sf2_grid(N, nvec, route.nc);
-  if (!c->sf2_tab) {
-    std::vector<std::pair<void**, size_t>> want;
-    want.push_back({(void**)&c->sf2_tab, sizeof(double) * SF2_MAX_VECS * sf_ncols<SF_MAX_FIELDS>()});
-    want.push_back({(void**)&c->sf2_vecs, sizeof(Sf2Vec) * SF2_MAX_VECS});
-    want.push_back({(void**)&c->sf2_proj, sizeof(double) * 2 * SF2_MAX_VECS});
-    const int rc = alloc_all_or_none(c, want, "nq_structure2");
-    if (rc) return rc;
-  }
-  {
-    const int rc = sf_reserve_part(c, (size_t)nblk * nvec * route.nc, "nq_structure2");
-    if (rc) return rc;
-  }
   const size_t plane = (size_t)N * N;
   if (c->kernel_family) {
-    const int rc = sf2_grow(c, &c->sf2_planes, &c->sf2_planes_count, (size_t)(a.nreal + 2 * a.phi) * plane * sizeof(double), "the physical planes");
+    const int rc = sf2_grow(c, &c->sf2_planes, &c->sf2_planes_count, (size_t)(nreal + 2 * phi) * plane * sizeof(double), "the physical planes", fn);
     if (rc) return rc;
-  }
-  a.part = c->sf_part;
-  a.vecs = c->sf2_vecs;
-  a.proj = proj ? c->sf2_proj : nullptr;
-  for (int i = 0; i < nvec; ++i) c->sf2_vecs_host[i] = sorted[i];
-  HIPCHK(c, hipMemcpyAsync(c->sf2_vecs, c->sf2_vecs_host, sizeof(Sf2Vec) * nvec, hipMemcpyHostToDevice, c->stream));
-  if (proj) {
-    for (int i = 0; i < 2 * nvec; ++i) c->sf2_proj_host[i] = proj[i];
-    HIPCHK(c, hipMemcpyAsync(c->sf2_proj, c->sf2_proj_host, sizeof(double) * 2 * nvec, hipMemcpyHostToDevice, c->stream));
   }
   SfPlanes pl = {};
   pl.rows = pl.cols = N;
@@ -5784,11 +5768,97 @@ int nq_structure2(nq_ctx* c, int nfields, const int* fields, int nvec, const int
       }
     }
   }
+  *out = pl;
+  return 0;
+}
+// The launches of one call: the sums of the current state into `tab` (nvec rows; on top of it with `accumulate`) through the shared
+// partials.  dvecs, dproj / hvecs, hproj: the sorted vectors and the projection on the device and their staging copies.  The caller
+// has checked the call (sf2_plan: a, canon, sorted) and owns `tab`: nq_structure2's running table, or nq_increment_range2's.
+static int sf2_sums_into(nq_ctx* c, const char* fn, int nfields, const int* fields, const bool* cplx, Sf2Args a, const int* canon, const Sf2Vec* sorted,
+                         int nvec, const double* proj, int ntriples, int accumulate, double* tab, Sf2Vec* dvecs, Sf2Vec* hvecs, double* dproj, double* hproj) {
+  const int N = c->N, nout = nfields * SF_COLS + ntriples;
+  const Sf2Route route = sf2_route(N, a.nreal, a.phi);
+  const int nblk = sf2_grid(N, nvec, route.nc);
+  {
+    const int rc = sf_reserve_part(c, (size_t)nblk * nvec * route.nc, fn);
+    if (rc) return rc;
+  }
+  a.part = c->sf_part;
+  a.vecs = dvecs;
+  a.proj = proj ? dproj : nullptr;
+  for (int i = 0; i < nvec; ++i) hvecs[i] = sorted[i];
+  HIPCHK(c, hipMemcpyAsync(dvecs, hvecs, sizeof(Sf2Vec) * nvec, hipMemcpyHostToDevice, c->stream));
+  if (proj) {
+    for (int i = 0; i < 2 * nvec; ++i) hproj[i] = proj[i];
+    HIPCHK(c, hipMemcpyAsync(dproj, hproj, sizeof(double) * 2 * nvec, hipMemcpyHostToDevice, c->stream));
+  }
+  SfPlanes pl = {};
+  {
+    const int rc = sf2_planes_of(c, fn, nfields, fields, cplx, canon, a.nreal, a.phi, &pl);
+    if (rc) return rc;
+  }
   sf2_launch(c->stream, nblk, route, pl, a);
   const int tgrid = (nvec * route.nc + SF_TOTAL_ENTRIES - 1) / SF_TOTAL_ENTRIES;
   hipLaunchKernelGGL(k_sf_total, dim3(tgrid), dim3(SF_TOTAL_RUNS * SF_TOTAL_ENTRIES), 0, c->stream, (const double*)c->sf_part, nblk, nvec, route.nc,
-                     sf_map(route.nc == sf_ncols<1>() ? 1 : (route.nc == sf_ncols<2>() ? 2 : 3), nfields, canon, ntriples), nout, accumulate, c->sf2_tab);
+                     sf_map(route.nc == sf_ncols<1>() ? 1 : (route.nc == sf_ncols<2>() ? 2 : 3), nfields, canon, ntriples), nout, accumulate, tab);
   HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+int nq_structure2(nq_ctx* c, int nfields, const int* fields, int nvec, const int* vecs, const double* proj, int proj_a, int proj_b,
+                  int ntriples, const int* triples, int accumulate) {
+  NQ_SINGLE_RANK(c, "nq_structure2");
+  if (!fields || nfields < 1 || nfields > SF_MAX_FIELDS) NQ_FAIL(c, -1, "nq_structure2: %d fields (1 to %d)", nfields, SF_MAX_FIELDS);
+  bool cplx[SF_MAX_FIELDS] = {};
+  for (int i = 0; i < nfields; ++i) {
+    cplx[i] = fields[i] == NQ_SF_PHI;
+    if ((cplx[i] || is_flow(fields[i])) && !c->kernel_family)
+      NQ_FAIL(c, -1, "nq_structure2: field %d (NQ_FLOW_*, NQ_SF_PHI) on a QGModel context: its plane route has q and its passive scalar only (DESIGN.md section 7)", fields[i]);
+    if (!cplx[i] && !is_flow(fields[i]) && hist_slot(c, fields[i]) < 0)
+      NQ_FAIL(c, -1, "nq_structure2: field %d is not available here (Kernel family: NQ_PDF_Q, NQ_PDF_QPSI, NQ_PDF_PHI2, the NQ_FLOW_* fields and NQ_SF_PHI; QGModel: NQ_PDF_Q, with its passive scalar NQ_PDF_C)", fields[i]);
+    for (int k = 0; k < i; ++k)
+      if (fields[k] == fields[i]) NQ_FAIL(c, -1, "nq_structure2: field %d listed twice", fields[i]);
+  }
+  if (c->kernel_family ? !c->have_phi : !c->have_q) NQ_FAIL(c, -4, "nq_structure2: %s has not been called", c->kernel_family ? "set_phi" : "set_q");
+  const int N = c->N;
+  Sf2Args a;
+  int canon[SF_MAX_FIELDS] = {};
+  Sf2Vec sorted[SF2_MAX_VECS];
+  if (const char* bad = sf2_plan(N, N, nfields, cplx, nvec, vecs, proj, proj_a, proj_b, ntriples, triples, &a, canon, sorted)) NQ_FAIL(c, -1, "nq_structure2: %s", bad);
+  nq_ctx::Sf2Cfg cfg;
+  cfg.nf = nfields;
+  cfg.nvec = nvec;
+  cfg.ntri = ntriples;
+  cfg.pa = proj_a;
+  cfg.pb = proj_b;
+  cfg.has_proj = proj != nullptr;
+  for (int i = 0; i < nfields; ++i) cfg.fields[i] = fields[i];
+  for (int i = 0; i < 2 * nvec; ++i) cfg.vecs[i] = vecs[i];
+  for (int i = 0; proj && i < 2 * nvec; ++i) cfg.proj[i] = proj[i];
+  for (int k = 0; k < 3 * ntriples; ++k) cfg.tri[k] = triples[k];
+  if (accumulate) {
+    const nq_ctx::Sf2Cfg& o = c->sf2_cfg;
+    bool same = c->sf2_tab && o.samples > 0 && o.nf == cfg.nf && o.nvec == cfg.nvec && o.ntri == cfg.ntri && o.pa == cfg.pa && o.pb == cfg.pb && o.has_proj == cfg.has_proj;
+    for (int i = 0; same && i < nfields; ++i) same = o.fields[i] == cfg.fields[i];
+    for (int i = 0; same && i < 2 * nvec; ++i) same = o.vecs[i] == cfg.vecs[i] && (!proj || memcmp(&o.proj[i], &cfg.proj[i], sizeof(double)) == 0);
+    for (int k = 0; same && k < 3 * ntriples; ++k) same = o.tri[k] == cfg.tri[k];
+    if (!same) NQ_FAIL(c, -1, "nq_structure2: accumulate = 1 needs the fields, vectors, projection and triples of the call that zeroed the table");
+    cfg.samples = o.samples;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->sf2_tab) {
+    std::vector<std::pair<void**, size_t>> want;
+    want.push_back({(void**)&c->sf2_tab, sizeof(double) * SF2_MAX_VECS * sf_ncols<SF_MAX_FIELDS>()});
+    want.push_back({(void**)&c->sf2_vecs, sizeof(Sf2Vec) * SF2_MAX_VECS});
+    want.push_back({(void**)&c->sf2_proj, sizeof(double) * 2 * SF2_MAX_VECS});
+    const int rc = alloc_all_or_none(c, want, "nq_structure2");
+    if (rc) return rc;
+  }
+  {
+    const int rc = sf2_sums_into(c, "nq_structure2", nfields, fields, cplx, a, canon, sorted, nvec, proj, ntriples, accumulate, c->sf2_tab, c->sf2_vecs,
+                                 c->sf2_vecs_host, c->sf2_proj, c->sf2_proj_host);
+    if (rc) return rc;
+  }
   ++cfg.samples;
   c->sf2_cfg = cfg;
   return 0;
@@ -5802,6 +5872,301 @@ int nq_structure2_read(nq_ctx* c, long long* samples, double* out) {
   HIPCHK(c, hipSetDevice(c->device));
   *samples = g.samples;
   HIPCHK(c, hipMemcpyAsync(out, c->sf2_tab, sizeof(double) * g.nvec * (g.nf * SF_COLS + g.ntri), hipMemcpyDeviceToHost, c->stream));
+  return nq_sync(c);
+}
+
+// ---- PDFs of the increments (csrc/nq_ipdf.hpp) ---------------------------------------------------------------
+static_assert(IPDF_MAX_BINS == NQ_IPDF_MAX_BINS, "limits of nq_increment_hist");
+constexpr size_t IPDF_SMALL_BYTES = sizeof(double) * 3 * SF_MAX_FIELDS * SF2_MAX_VECS + sizeof(double) * 2 * SF2_MAX_VECS + sizeof(Sf2Vec) * SF2_MAX_VECS +
+                                    sizeof(double) * SF2_MAX_VECS * sf_ncols<SF_MAX_FIELDS>() + sizeof(int) * SF_MAX_SEPS;
+static_assert(sizeof(unsigned long long) * SF2_MAX_VECS * SF_MAX_FIELDS * (IPDF_MAX_BINS + 3) + IPDF_SMALL_BYTES <= (size_t)NQ_IPDF_DEVICE_BYTES,
+              "the largest count table and the small buffers are what the header declares");
+constexpr int IPDF_PLANE_GRID = 512;              // workgroups of k_ipdf_plane: each flushes one table per vector
+// the fields of a call: nq_structure's checks; cplx[i]: field i is NQ_SF_PHI
+static int ipdf_check_fields(nq_ctx* c, const char* fn, int nfields, const int* fields, bool* cplx) {
+  if (!fields || nfields < 1 || nfields > SF_MAX_FIELDS) NQ_FAIL(c, -1, "%s: %d fields (1 to %d)", fn, nfields, SF_MAX_FIELDS);
+  for (int i = 0; i < nfields; ++i) {
+    cplx[i] = fields[i] == NQ_SF_PHI;
+    if ((cplx[i] || is_flow(fields[i])) && !c->kernel_family)
+      NQ_FAIL(c, -1, "%s: field %d (NQ_FLOW_*, NQ_SF_PHI) on a QGModel context: its plane route has q and its passive scalar only (DESIGN.md section 7)", fn, fields[i]);
+    if (!cplx[i] && !is_flow(fields[i]) && hist_slot(c, fields[i]) < 0)
+      NQ_FAIL(c, -1, "%s: field %d is not available here (Kernel family: NQ_PDF_Q, NQ_PDF_QPSI, NQ_PDF_PHI2, the NQ_FLOW_* fields and NQ_SF_PHI; QGModel: NQ_PDF_Q, with its passive scalar NQ_PDF_C)", fn, fields[i]);
+    for (int k = 0; k < i; ++k)
+      if (fields[k] == fields[i]) NQ_FAIL(c, -1, "%s: field %d listed twice", fn, fields[i]);
+  }
+  if (c->kernel_family ? !c->have_phi : !c->have_q) NQ_FAIL(c, -4, "%s: %s has not been called", fn, c->kernel_family ? "set_phi" : "set_q");
+  return 0;
+}
+// bins and the n x nfields ranges of a call; nullptr, or what is wrong
+static const char* ipdf_check_ranges(int n, int nfields, const double* lo, const double* hi, int bins) {
+  static char msg[256];
+  if (bins < 1 || bins > IPDF_MAX_BINS) {
+    snprintf(msg, sizeof(msg), "bins = %d (1 to %d: the LDS tables of a workgroup)", bins, IPDF_MAX_BINS);
+    return msg;
+  }
+  if (!lo || !hi) return "null ranges";
+  for (int i = 0; i < n * nfields; ++i)
+    if (!std::isfinite(lo[i]) || !std::isfinite(hi[i]) || !(lo[i] < hi[i])) {
+      snprintf(msg, sizeof(msg), "range [%g, %g] of row %d, field %d (finite, lo < hi)", lo[i], hi[i], i / nfields, i % nfields);
+      return msg;
+    }
+  return nullptr;
+}
+// the small buffers: all of them or none
+static int ipdf_reserve(nq_ctx* c, const char* fn) {
+  if (c->ipdf_rng) return 0;
+  std::vector<std::pair<void**, size_t>> want;
+  want.push_back({(void**)&c->ipdf_rng, sizeof(double) * 3 * SF_MAX_FIELDS * SF2_MAX_VECS});
+  want.push_back({(void**)&c->ipdf_proj, sizeof(double) * 2 * SF2_MAX_VECS});
+  want.push_back({(void**)&c->ipdf_vecs, sizeof(Sf2Vec) * SF2_MAX_VECS});
+  want.push_back({(void**)&c->ipdf_sums, sizeof(double) * SF2_MAX_VECS * sf_ncols<SF_MAX_FIELDS>()});
+  want.push_back({(void**)&c->ipdf_seps, sizeof(int) * SF_MAX_SEPS});
+  return alloc_all_or_none(c, want, fn);
+}
+// columns 0 and 1 of every field of the range pass's table -> out
+static int ipdf_range_out(nq_ctx* c, int n, int nfields, double* out) {
+  const int nout = nfields * SF_COLS;
+  std::vector<double> host((size_t)n * nout);
+  HIPCHK(c, hipMemcpyAsync(host.data(), c->ipdf_sums, sizeof(double) * host.size(), hipMemcpyDeviceToHost, c->stream));
+  const int rc = nq_sync(c);
+  if (rc) return rc;
+  for (int i = 0; i < n; ++i)
+    for (int f = 0; f < nfields; ++f) {
+      out[((size_t)i * nfields + f) * 2] = host[(size_t)i * nout + f * SF_COLS];
+      out[((size_t)i * nfields + f) * 2 + 1] = host[(size_t)i * nout + f * SF_COLS + 1];
+    }
+  return 0;
+}
+
+int nq_increment_range(nq_ctx* c, int nfields, const int* fields, int nsep, const int* seps, double* out) {
+  static const char* fn = "nq_increment_range";
+  NQ_SINGLE_RANK(c, "nq_increment_range");
+  bool cplx[SF_MAX_FIELDS] = {};
+  {
+    const int rc = ipdf_check_fields(c, fn, nfields, fields, cplx);
+    if (rc) return rc;
+  }
+  if (!out) NQ_FAIL(c, -1, "%s: null output", fn);
+  SfArgs a;
+  int canon[SF_MAX_FIELDS] = {};
+  if (const char* bad = sf_plan(c->N, nfields, cplx, nsep, seps, 0, nullptr, &a, canon)) NQ_FAIL(c, -1, "%s: %s", fn, bad);
+  HIPCHK(c, hipSetDevice(c->device));
+  {
+    int rc = ipdf_reserve(c, fn);
+    if (!rc) rc = sf_sums_into(c, fn, nfields, fields, cplx, a, canon, nsep, seps, 0, nullptr, 0, c->ipdf_sums, c->ipdf_seps, c->ipdf_seps_host);
+    if (rc) return rc;
+  }
+  return ipdf_range_out(c, nsep, nfields, out);
+}
+
+int nq_increment_range2(nq_ctx* c, int nfields, const int* fields, int nvec, const int* vecs, const double* proj, int proj_a, int proj_b, double* out) {
+  static const char* fn = "nq_increment_range2";
+  NQ_SINGLE_RANK(c, "nq_increment_range2");
+  bool cplx[SF_MAX_FIELDS] = {};
+  {
+    const int rc = ipdf_check_fields(c, fn, nfields, fields, cplx);
+    if (rc) return rc;
+  }
+  if (!out) NQ_FAIL(c, -1, "%s: null output", fn);
+  Sf2Args a;
+  int canon[SF_MAX_FIELDS] = {};
+  Sf2Vec sorted[SF2_MAX_VECS];
+  if (const char* bad = sf2_plan(c->N, c->N, nfields, cplx, nvec, vecs, proj, proj_a, proj_b, 0, nullptr, &a, canon, sorted)) NQ_FAIL(c, -1, "%s: %s", fn, bad);
+  HIPCHK(c, hipSetDevice(c->device));
+  {
+    int rc = ipdf_reserve(c, fn);
+    if (!rc) rc = sf2_sums_into(c, fn, nfields, fields, cplx, a, canon, sorted, nvec, proj, 0, 0, c->ipdf_sums, c->ipdf_vecs, c->ipdf_vecs_host, c->ipdf_proj, c->ipdf_proj_host);
+    if (rc) return rc;
+  }
+  return ipdf_range_out(c, nvec, nfields, out);
+}
+
+// What the two counting calls share once the call is checked: accumulate = 1 against the call that zeroed the table, the buffers
+// (the count table grown to this call), the table zeroed without `accumulate`, the ranges on the device.  cfg: this call, samples
+// filled in.  g: bins, nfields, rng and tab filled in.
+static int ipdf_begin(nq_ctx* c, const char* fn, nq_ctx::IpdfCfg& cfg, const double* lo, const double* hi, int accumulate, IpdfArgs* g) {
+  const int cells = cfg.n * cfg.nf;
+  for (int i = 0; i < cells; ++i) {
+    cfg.lo[i] = lo[i];
+    cfg.hi[i] = hi[i];
+  }
+  if (accumulate) {
+    const nq_ctx::IpdfCfg& o = c->ipdf_cfg;
+    bool same = c->ipdf_tab && o.samples > 0 && o.kind == cfg.kind && o.nf == cfg.nf && o.n == cfg.n && o.bins == cfg.bins && o.pa == cfg.pa && o.pb == cfg.pb &&
+                o.has_proj == cfg.has_proj;
+    for (int i = 0; same && i < cfg.nf; ++i) same = o.fields[i] == cfg.fields[i];
+    for (int i = 0; same && i < (cfg.kind == 1 ? 1 : 2) * cfg.n; ++i) same = o.vecs[i] == cfg.vecs[i];
+    for (int i = 0; same && cfg.has_proj && i < 2 * cfg.n; ++i) same = memcmp(&o.proj[i], &cfg.proj[i], sizeof(double)) == 0;
+    for (int i = 0; same && i < cells; ++i) same = memcmp(&o.lo[i], &cfg.lo[i], sizeof(double)) == 0 && memcmp(&o.hi[i], &cfg.hi[i], sizeof(double)) == 0;
+    if (!same) NQ_FAIL(c, -1, "%s: accumulate = 1 needs the fields, separations or vectors, projection, ranges and bins of the call that zeroed the table", fn);
+    cfg.samples = o.samples;
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t bytes = sizeof(unsigned long long) * cells * (cfg.bins + 3);
+  {
+    int rc = ipdf_reserve(c, fn);
+    if (!rc) rc = sf2_grow(c, &c->ipdf_tab, &c->ipdf_tab_bytes, bytes, "the count table", fn);
+    if (rc) return rc;
+  }
+  if (!accumulate) HIPCHK(c, hipMemsetAsync(c->ipdf_tab, 0, bytes, c->stream));
+  for (int i = 0; i < cells; ++i) {
+    c->ipdf_rng_host[3 * i] = lo[i];
+    c->ipdf_rng_host[3 * i + 1] = hi[i];
+    c->ipdf_rng_host[3 * i + 2] = (double)cfg.bins / (hi[i] - lo[i]);
+  }
+  HIPCHK(c, hipMemcpyAsync(c->ipdf_rng, c->ipdf_rng_host, sizeof(double) * 3 * cells, hipMemcpyHostToDevice, c->stream));
+  g->bins = cfg.bins;
+  g->nfields = cfg.nf;
+  g->rng = c->ipdf_rng;
+  g->tab = static_cast<unsigned long long*>(c->ipdf_tab);
+  return 0;
+}
+static void ipdf_plane_launch(hipStream_t s, const SfPlanes& pl, const IpdfArgs& g) {
+  const int grid = pl.rows < IPDF_PLANE_GRID ? pl.rows : IPDF_PLANE_GRID;
+  hipLaunchKernelGGL(k_ipdf_plane, dim3(grid), dim3(IPDF_PLANE_THREADS), 2 * sizeof(unsigned) * ipdf_words(g.nreal + g.phi, g.bins), s, pl, g);
+}
+// the vectors of a call on the device, from the context's staging copy
+static int ipdf_put_vecs(nq_ctx* c, const Sf2Vec* v, int n, const double* proj) {
+  for (int i = 0; i < n; ++i) c->ipdf_vecs_host[i] = v[i];
+  HIPCHK(c, hipMemcpyAsync(c->ipdf_vecs, c->ipdf_vecs_host, sizeof(Sf2Vec) * n, hipMemcpyHostToDevice, c->stream));
+  if (proj) {
+    for (int i = 0; i < 2 * n; ++i) c->ipdf_proj_host[i] = proj[i];
+    HIPCHK(c, hipMemcpyAsync(c->ipdf_proj, c->ipdf_proj_host, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+  }
+  return 0;
+}
+
+int nq_increment_hist(nq_ctx* c, int nfields, const int* fields, int nsep, const int* seps, const double* lo, const double* hi, int bins, int accumulate) {
+  static const char* fn = "nq_increment_hist";
+  NQ_SINGLE_RANK(c, "nq_increment_hist");
+  bool cplx[SF_MAX_FIELDS] = {};
+  {
+    const int rc = ipdf_check_fields(c, fn, nfields, fields, cplx);
+    if (rc) return rc;
+  }
+  SfArgs a;
+  int canon[SF_MAX_FIELDS] = {};
+  if (const char* bad = sf_plan(c->N, nfields, cplx, nsep, seps, 0, nullptr, &a, canon)) NQ_FAIL(c, -1, "%s: %s", fn, bad);
+  if (const char* bad = ipdf_check_ranges(nsep, nfields, lo, hi, bins)) NQ_FAIL(c, -1, "%s: %s", fn, bad);
+  nq_ctx::IpdfCfg cfg;
+  cfg.kind = 1;
+  cfg.nf = nfields;
+  cfg.n = nsep;
+  cfg.bins = bins;
+  for (int i = 0; i < nfields; ++i) cfg.fields[i] = fields[i];
+  for (int s = 0; s < nsep; ++s) cfg.vecs[s] = seps[s];
+  IpdfArgs g = {};
+  {
+    const int rc = ipdf_begin(c, fn, cfg, lo, hi, accumulate, &g);
+    if (rc) return rc;
+  }
+  g.nsep = nsep;
+  g.nreal = a.nreal;
+  g.phi = a.phi;
+  g.pa = g.pb = -1;
+  for (int i = 0; i < nfields; ++i) g.out[canon[i]] = i;
+  if (!c->kernel_family) {                              // planes: the separations as the vectors (r, 0)
+    Sf2Vec v[SF_MAX_SEPS];
+    for (int s = 0; s < nsep; ++s) v[s] = Sf2Vec{seps[s], 0, s, 0};
+    {
+      const int rc = ipdf_put_vecs(c, v, nsep, nullptr);
+      if (rc) return rc;
+    }
+    g.vecs = c->ipdf_vecs;
+    SfPlanes pl = {};
+    {
+      const int rc = sf2_planes_of(c, fn, nfields, fields, cplx, canon, a.nreal, a.phi, &pl);
+      if (rc) return rc;
+    }
+    ipdf_plane_launch(c->stream, pl, g);
+  } else {
+    for (int s = 0; s < nsep; ++s) c->ipdf_seps_host[s] = seps[s];
+    HIPCHK(c, hipMemcpyAsync(c->ipdf_seps, c->ipdf_seps_host, sizeof(int) * nsep, hipMemcpyHostToDevice, c->stream));
+    g.seps = c->ipdf_seps;
+    if (nfields <= flow_nv_of(c)) {
+      FlowSel sel = flow_sel_none(c);
+      for (int i = 0; i < nfields; ++i)
+        if (!cplx[i]) sel.code[canon[i]] = fields[i];
+      sel.phi = a.phi;
+      launch_xflow_ipdf(c, sel, g);
+    } else {
+      for (int i = 0; i < nfields; ++i) {               // one field per launch, in the launch's slot 0, into its own part of the table
+        FlowSel sel = flow_sel_none(c);
+        IpdfArgs k = g;
+        k.nreal = cplx[i] ? 0 : 1;
+        k.phi = cplx[i] ? 1 : 0;
+        k.out[0] = i;
+        if (!cplx[i]) sel.code[0] = fields[i];
+        sel.phi = k.phi;
+        launch_xflow_ipdf(c, sel, k);
+      }
+    }
+  }
+  HIPCHK(c, hipGetLastError());
+  ++cfg.samples;
+  c->ipdf_cfg = cfg;
+  return 0;
+}
+
+int nq_increment_hist2(nq_ctx* c, int nfields, const int* fields, int nvec, const int* vecs, const double* proj, int proj_a, int proj_b, const double* lo,
+                       const double* hi, int bins, int accumulate) {
+  static const char* fn = "nq_increment_hist2";
+  NQ_SINGLE_RANK(c, "nq_increment_hist2");
+  bool cplx[SF_MAX_FIELDS] = {};
+  {
+    const int rc = ipdf_check_fields(c, fn, nfields, fields, cplx);
+    if (rc) return rc;
+  }
+  Sf2Args a;
+  int canon[SF_MAX_FIELDS] = {};
+  Sf2Vec sorted[SF2_MAX_VECS];
+  if (const char* bad = sf2_plan(c->N, c->N, nfields, cplx, nvec, vecs, proj, proj_a, proj_b, 0, nullptr, &a, canon, sorted)) NQ_FAIL(c, -1, "%s: %s", fn, bad);
+  if (const char* bad = ipdf_check_ranges(nvec, nfields, lo, hi, bins)) NQ_FAIL(c, -1, "%s: %s", fn, bad);
+  nq_ctx::IpdfCfg cfg;
+  cfg.kind = 2;
+  cfg.nf = nfields;
+  cfg.n = nvec;
+  cfg.bins = bins;
+  cfg.pa = proj_a;
+  cfg.pb = proj_b;
+  cfg.has_proj = proj != nullptr;
+  for (int i = 0; i < nfields; ++i) cfg.fields[i] = fields[i];
+  for (int i = 0; i < 2 * nvec; ++i) cfg.vecs[i] = vecs[i];
+  for (int i = 0; proj && i < 2 * nvec; ++i) cfg.proj[i] = proj[i];
+  IpdfArgs g = {};
+  {
+    int rc = ipdf_begin(c, fn, cfg, lo, hi, accumulate, &g);
+    if (!rc) rc = ipdf_put_vecs(c, sorted, nvec, proj);
+    if (rc) return rc;
+  }
+  g.nsep = nvec;
+  g.vecs = c->ipdf_vecs;
+  g.proj = proj ? c->ipdf_proj : nullptr;
+  g.nreal = a.nreal;
+  g.phi = a.phi;
+  g.pa = a.pa;
+  g.pb = a.pb;
+  for (int i = 0; i < nfields; ++i) g.out[canon[i]] = i;
+  SfPlanes pl = {};
+  {
+    const int rc = sf2_planes_of(c, fn, nfields, fields, cplx, canon, a.nreal, a.phi, &pl);
+    if (rc) return rc;
+  }
+  ipdf_plane_launch(c->stream, pl, g);
+  HIPCHK(c, hipGetLastError());
+  ++cfg.samples;
+  c->ipdf_cfg = cfg;
+  return 0;
+}
+
+int nq_increment_hist_read(nq_ctx* c, long long* samples, unsigned long long* out) {
+  NQ_SINGLE_RANK(c, "nq_increment_hist_read");
+  if (!samples || !out) NQ_FAIL(c, -1, "nq_increment_hist_read: null output");
+  const nq_ctx::IpdfCfg& g = c->ipdf_cfg;
+  if (!c->ipdf_tab || g.nf == 0) NQ_FAIL(c, -4, "nq_increment_hist_read: no nq_increment_hist or nq_increment_hist2 call yet");
+  HIPCHK(c, hipSetDevice(c->device));
+  *samples = g.samples;
+  HIPCHK(c, hipMemcpyAsync(out, c->ipdf_tab, sizeof(unsigned long long) * g.n * g.nf * (g.bins + 3), hipMemcpyDeviceToHost, c->stream));
   return nq_sync(c);
 }
 
@@ -7039,6 +7404,71 @@ int nq_any_increments2(nq_any* e, int nfields, const void* const* planes, const 
                      nblk, nvec, route.nc, sf_map(route.nc == sf_ncols<1>() ? 1 : (route.nc == sf_ncols<2>() ? 2 : 3), nfields, canon, ntriples), nout, 0, tab);
   ANYCHK(e, hipGetLastError());
   ANYCHK(e, hipMemcpyAsync(out, tab, sizeof(double) * nvec * nout, hipMemcpyDeviceToHost, e->stream));
+  return nq_any_sync(e);
+}
+// PDFs of the increments on engine planes: nq_increment_hist2's plane kernel, the counts of one state
+int nq_any_increment_hist(nq_any* e, int nfields, const void* const* planes, const int* what, int rows, int cols, int nvec, const int* vecs,
+                          const double* proj, int proj_a, int proj_b, const double* lo, const double* hi, int bins, unsigned long long* out) {
+  if (!e || !planes || !what || !out || rows < 1 || cols < 2) return -1;
+  if (nfields < 1 || nfields > SF_MAX_FIELDS) ANYFAIL(e, -1, "nq_any_increment_hist: %d fields (1 to %d)", nfields, SF_MAX_FIELDS);
+  bool cplx[SF_MAX_FIELDS] = {};
+  for (int i = 0; i < nfields; ++i) {
+    if (!planes[i]) ANYFAIL(e, -1, "nq_any_increment_hist: plane %d is null", i);
+    if (what[i] != 0 && what[i] != 2) ANYFAIL(e, -1, "nq_any_increment_hist: what[%d] = %d (0: Re, 2: complex)", i, what[i]);
+    cplx[i] = what[i] == 2;
+  }
+  Sf2Args a;
+  int canon[SF_MAX_FIELDS] = {};
+  Sf2Vec sorted[SF2_MAX_VECS];
+  if (const char* bad = sf2_plan(rows, cols, nfields, cplx, nvec, vecs, proj, proj_a, proj_b, 0, nullptr, &a, canon, sorted))
+    ANYFAIL(e, -1, "nq_any_increment_hist: %s", bad);
+  if (const char* bad = ipdf_check_ranges(nvec, nfields, lo, hi, bins)) ANYFAIL(e, -1, "nq_any_increment_hist: %s", bad);
+  ANYCHK(e, hipSetDevice(e->device));
+  const int cells = nvec * nfields;
+  const size_t words = (size_t)cells * (bins + 3);
+  std::vector<double> rng((size_t)3 * cells);
+  for (int i = 0; i < cells; ++i) {
+    rng[3 * i] = lo[i];
+    rng[3 * i + 1] = hi[i];
+    rng[3 * i + 2] = (double)bins / (hi[i] - lo[i]);
+  }
+  IpdfArgs g = {};
+  unsigned long long* tab = nullptr;
+  double *drng = nullptr, *dproj = nullptr;
+  Sf2Vec* dvecs = nullptr;
+  AnyScratch tmp;
+  ANYCHK(e, tmp.get(&tab, words));
+  ANYCHK(e, tmp.get(&drng, rng.size()));
+  ANYCHK(e, tmp.get(&dvecs, (size_t)nvec));
+  ANYCHK(e, hipMemsetAsync(tab, 0, sizeof(unsigned long long) * words, e->stream));
+  ANYCHK(e, hipMemcpyAsync(drng, rng.data(), sizeof(double) * rng.size(), hipMemcpyHostToDevice, e->stream));
+  ANYCHK(e, hipMemcpyAsync(dvecs, sorted, sizeof(Sf2Vec) * nvec, hipMemcpyHostToDevice, e->stream));
+  if (proj) {
+    ANYCHK(e, tmp.get(&dproj, (size_t)2 * nvec));
+    ANYCHK(e, hipMemcpyAsync(dproj, proj, sizeof(double) * 2 * nvec, hipMemcpyHostToDevice, e->stream));
+  }
+  g.nsep = nvec;
+  g.vecs = dvecs;
+  g.proj = dproj;
+  g.pa = a.pa;
+  g.pb = a.pb;
+  g.nreal = a.nreal;
+  g.phi = a.phi;
+  g.nfields = nfields;
+  g.bins = bins;
+  g.rng = drng;
+  g.tab = tab;
+  SfPlanes pl = {};
+  for (int i = 0; i < nfields; ++i) {
+    g.out[canon[i]] = i;
+    pl.p[canon[i]] = reinterpret_cast<const double*>(planes[i]);
+    pl.stride[canon[i]] = 2;
+  }
+  pl.rows = rows;
+  pl.cols = cols;
+  ipdf_plane_launch(e->stream, pl, g);
+  ANYCHK(e, hipGetLastError());
+  ANYCHK(e, hipMemcpyAsync(out, tab, sizeof(unsigned long long) * words, hipMemcpyDeviceToHost, e->stream));
   return nq_any_sync(e);
 }
 int nq_any_set_elem(nq_any* e, void* plane, long long index, double re, double im) {
