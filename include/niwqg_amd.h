@@ -351,6 +351,56 @@ int nq_increment_hist2(nq_ctx* ctx, int nfields, const int* fields, int nvec, co
                        const double* hi, int bins, int accumulate);
 int nq_increment_hist_read(nq_ctx* ctx, long long* samples, unsigned long long* out /* n x nfields x (bins + 3) counts */);
 
+/* Vortex census: the connected components of a thresholded field, labelled and summed on the device.
+ * fields: 1 to 3 different REAL ids out of those nq_field_hist takes for the model (not NQ_SF_PHI); fields[crit] is the criterion a,
+ * all of them are summed.  Point (y, x) is in the SET when a < t (NQ_VX_BELOW), a > t (NQ_VX_ABOVE) or |a| > t (NQ_VX_ABS_ABOVE) for
+ * the finite threshold t; NaN is never in the set.  Components: those of the set under connectivity 4 or 8 on the doubly periodic
+ * grid (column nx - 1 neighbours column 0, row ny - 1 row 0).  The LABEL of a component is the smallest linear index y nx + x of its
+ * points, so the label plane does not depend on the order of execution.  Table: one row per component in ascending label order,
+ * NQ_VX_COLS + nfields 64-bit integers:
+ *   [0] label, (y0, x0) = divmod(label, nx)      [1] area in points       [2], [3] sum dx, sum dy
+ *   [4], [5], [6] sum dx^2, sum dy^2, sum dx dy   [7], [8] bit patterns of the minimum and the maximum of a (doubles; -0 < +0)
+ *   [9 + f] sum rint(a_f 2^s_f), half to even, a non-finite value counting 0
+ * with dx = ((x - x0 + nx/2) mod nx) - nx/2 and dy likewise: the periodic offsets from the label's own point, in [-n/2, n/2) (a
+ * component wider than half the domain gets what this formula gives).  s_f = 61 - ceil(log2(nx ny)) - e with max |a_f| = m 2^e, m in
+ * [0.5, 1) over the finite values of the plane (s_f = 0 for a plane without a non-zero finite value): no sum over any subset of
+ * the plane leaves int64, and a component's sum is sum a_f to within area 2^(-s_f - 1).  Integer sums: bit-reproducible.
+ * capacity in [1, NQ_VX_MAX_CAPACITY]: the table holds the first min(total, capacity) components in label order; the points of
+ * later ones are labelled, not summed.
+ *
+ * nq_vortex_range: out[4 f ..] = min, max, sum, sum of squares of field f over its finite values (+inf, -inf, 0, 0 without any),
+ *   from workgroup partials added in a fixed order (deterministic); one small download.  It needs the small buffers only and
+ *   keeps results of its own: the last census stays readable after it.
+ * nq_vortex_census: every phase on the device, in stream order (range and scales, row runs, lock-free union-find across rows,
+ *   flatten, rank, sums reduced per run within a wave and flushed with 64-bit integer atomics; csrc/nq_vortex.hpp).  Nothing is copied to the host, the host does not
+ *   wait.
+ * nq_vortex_read: info = {components found, rows in the table, points in the set, non-finite values met in the fields of the call,
+ *   s_0, s_1, s_2}; table (or NULL): room for capacity rows, the first info[1] are written.
+ * nq_vortex_labels: the ny x nx label plane of the last census, -1 outside the set.
+ * nq_vortex_stats: out[4 f ..] = min, max, sum, sum of squares of field f of the last census, from its own range pass (what
+ *   nq_vortex_range would have returned on that state); -4 before a census.
+ * The Kernel family's values go through the physical planes nq_structure2 stores (grown by the largest call; a failure leaves the
+ * old pool).  The label plane, the rank plane, the small buffers and the table are this feature's own: allocated by the first
+ * call, grown all or none, counted by nq_device_bytes, freed with the context.  Reads the state, writes only these buffers and the
+ * shared plane pool: the tables, sample counts and configurations of nq_structure2 and nq_increment_hist2 are not touched.
+ * -1: bad arguments (a field the model lacks, a NQ_FLOW_* field on a QGModel context, a field listed twice, NQ_SF_PHI, a non-finite
+ * threshold, connectivity other than 4 or 8, capacity out of range); -4: slab contexts, nothing set yet, a read before a census;
+ * -5: an allocation failed, everything as it was.                                                                              */
+enum { NQ_VX_BELOW = 0, NQ_VX_ABOVE = 1, NQ_VX_ABS_ABOVE = 2 };
+#define NQ_VX_COLS 9
+#define NQ_VX_MAX_CAPACITY 1048576
+int nq_vortex_range(nq_ctx* ctx, int nfields, const int* fields, double* out /* nfields x 4: min, max, sum, sum of squares */);
+int nq_vortex_census(nq_ctx* ctx, int nfields, const int* fields, int crit /* index into fields */, int mode, double threshold,
+                     int connectivity /* 4 | 8 */, int capacity);
+/* nq_vortex_census, synchronous, with device events between its phases (tools/vortices_cost.py): ms[0] the planes (the store
+ * pass, or QGModel's transforms), then the range pass, the row pass, the merge, flatten + rank, the sums.  The census it leaves is
+ * the one nq_vortex_census would have left. */
+int nq_vortex_profile(nq_ctx* ctx, int nfields, const int* fields, int crit, int mode, double threshold, int connectivity,
+                      int capacity, double* ms /* 6 */);
+int nq_vortex_read(nq_ctx* ctx, long long* info /* 7 */, long long* table /* NULL or capacity x (NQ_VX_COLS + nfields) */);
+int nq_vortex_labels(nq_ctx* ctx, int* out /* ny x nx labels, -1 outside the set */);
+int nq_vortex_stats(nq_ctx* ctx, double* out /* nfields x 4: min, max, sum, sum of squares */);
+
 /* Lagrangian particles, single-rank contexts only (slab contexts refuse every call with -4).
  * After every step of nq_step the library moves each particle one classical RK4 step through U_tot = (U + u, v), u = -d psi/dy,
  * v = d psi/dx of the ph the context holds, linear in time between U0 (start of the step) and U1 (after it):
@@ -914,6 +964,12 @@ int nq_any_increments2(nq_any* eng, int nfields, const void* const* planes, cons
 int nq_any_increment_hist(nq_any* eng, int nfields, const void* const* planes, const int* what /* 0 Re, 2 complex */, int rows, int cols,
                           int nvec, const int* vecs, const double* proj, int proj_a, int proj_b, const double* lo, const double* hi,
                           int bins, unsigned long long* out);
+/* Vortex census on engine planes (nq_vortex_census above: set, components, labels, table, capacity and return codes).  planes:
+ * 1 to 3 different (rows, cols) complex planes whose REAL parts are the fields; rows, cols: even, from 4 to 16384, no power of two
+ * or multiple of 64 needed.  info: the 7 entries of nq_vortex_read; table: room for capacity x (NQ_VX_COLS + nplanes), the first
+ * info[1] rows are written; labels (or NULL): rows x cols.  Synchronous; its device buffers live for the call. */
+int nq_any_components(nq_any* eng, int nplanes, const void* const* planes, int rows, int cols, int crit, int mode, double threshold,
+                      int connectivity, int capacity, long long* info, long long* table, int* labels);
 /* Lagrangian particles on engine planes (the RK4 step and interpolation of nq_particles_attach above): pos holds n complex
  * x + i y; U0, U1 and plane are (nx, nx) complex planes, velocity planes as u + i v; out[i] = plane at pos[i] (real and
  * imaginary parts interpolated each) */

@@ -19,6 +19,7 @@
 #include "nq_sf.hpp"
 #include "nq_sf2.hpp"
 #include "nq_ipdf.hpp"
+#include "nq_vortex.hpp"
 #include "nq_forcing.hpp"
 
 using namespace nq;
@@ -285,6 +286,11 @@ struct nq_ctx {
     double proj[2 * SF2_MAX_VECS] = {}, lo[SF_MAX_FIELDS * SF2_MAX_VECS] = {}, hi[SF_MAX_FIELDS * SF2_MAX_VECS] = {};
     long long samples = 0;
   } ipdf_cfg;
+  // vortex census (nq_vortex_*; csrc/nq_vortex.hpp): the label and rank planes, the small buffers (range partials, scales, info,
+  // per-row counts) and the table, grown by the largest capacity; the call nq_vortex_read and nq_vortex_labels answer for
+  void *vx_planes = nullptr, *vx_small = nullptr, *vx_tab = nullptr;
+  size_t vx_planes_bytes = 0, vx_small_bytes = 0, vx_tab_bytes = 0;
+  struct VxCfg { int nf = 0, cap = 0; bool census = false; } vx_cfg;
   cd *tr_h = nullptr, *tr_f = nullptr;               // its planes on slab contexts (two half, one full-width; P == 1: scr_*)
   double *carryW = nullptr, *carryQ = nullptr;    // spectral sums of the state at the start of the next step
   double *gradS1 = nullptr, *acc = nullptr;       // stale-aware sum wv2|phih_grad|^2 ; Ke,Pw,Kw increments
@@ -6170,6 +6176,284 @@ int nq_increment_hist_read(nq_ctx* c, long long* samples, unsigned long long* ou
   return nq_sync(c);
 }
 
+// ---- vortex census (csrc/nq_vortex.hpp) --------------------------------------------------------------------
+static_assert(VX_BELOW == NQ_VX_BELOW && VX_ABOVE == NQ_VX_ABOVE && VX_ABS_ABOVE == NQ_VX_ABS_ABOVE && VX_BASE_COLS == NQ_VX_COLS &&
+              VX_MAX_FIELDS == SF_MAX_FIELDS && VX_INFO == 7, "public constants of nq_vortex_census and the kernels'");
+// the device buffers of a census on planes of (rows, cols): two int32 planes, the small buffers, the table
+struct VxBufs {
+  int *L, *R, *rowroots, *rowset, *rowoff;
+  double* part;
+  VxRange* rng;
+  long long* info;
+  unsigned long long* tab;
+};
+static size_t vx_planes_bytes(int rows, int cols) { return 2 * sizeof(int) * (size_t)rows * cols; }
+static size_t vx_small_bytes(int rows) {
+  return sizeof(double) * VX_RANGE_GRID * VX_MAX_FIELDS * VX_RANGE_COLS + sizeof(VxRange) + sizeof(long long) * VX_INFO + 3 * sizeof(int) * (size_t)rows;
+}
+static size_t vx_tab_bytes(int cap) { return sizeof(unsigned long long) * (size_t)cap * (VX_BASE_COLS + VX_MAX_FIELDS); }
+static VxBufs vx_bufs(void* planes, void* small, void* tab, int rows, int cols) {
+  VxBufs b;
+  b.L = static_cast<int*>(planes);
+  b.R = b.L + (size_t)rows * cols;
+  b.part = static_cast<double*>(small);
+  b.rng = reinterpret_cast<VxRange*>(b.part + VX_RANGE_GRID * VX_MAX_FIELDS * VX_RANGE_COLS);
+  b.info = reinterpret_cast<long long*>(b.rng + 1);
+  b.rowroots = reinterpret_cast<int*>(b.info + VX_INFO);
+  b.rowset = b.rowroots + rows;
+  b.rowoff = b.rowset + rows;
+  b.tab = static_cast<unsigned long long*>(tab);
+  return b;
+}
+static_assert(sizeof(VxRange) % 8 == 0, "the small buffers stay 8-byte aligned");
+static const char* vx_check_call(int crit, int nfields, int mode, double threshold, int connectivity, int capacity) {
+  if (crit < 0 || crit >= nfields) return "crit is an index into the field list";
+  if (mode != NQ_VX_BELOW && mode != NQ_VX_ABOVE && mode != NQ_VX_ABS_ABOVE) return "mode is NQ_VX_BELOW, NQ_VX_ABOVE or NQ_VX_ABS_ABOVE";
+  if (!std::isfinite(threshold)) return "the threshold is not finite";
+  if (connectivity != 4 && connectivity != 8) return "connectivity is 4 or 8";
+  if (capacity < 1 || capacity > NQ_VX_MAX_CAPACITY) return "capacity outside [1, NQ_VX_MAX_CAPACITY]";
+  return nullptr;
+}
+// the range pass: min, max, sums and scales of every plane of the call into b.rng, the non-finite count and the scales into b.info
+static void vx_range_launch(hipStream_t s, const VxPlanes& pl, const VxBufs& b) {
+  const int nblk = pl.rows < VX_RANGE_GRID ? pl.rows : VX_RANGE_GRID;
+  int lg = 0;
+  while (((size_t)1 << lg) < (size_t)pl.rows * pl.cols) ++lg;
+  hipLaunchKernelGGL(k_vx_range, dim3(nblk), dim3(VX_THREADS), 0, s, pl, b.part);
+  hipLaunchKernelGGL(k_vx_scale, dim3(1), dim3(64 * VX_RANGE_COLS), 0, s, (const double*)b.part, nblk, pl.nf, lg, b.rng, b.info);
+}
+// every phase of one census, in stream order; nothing is copied, the host does not wait
+// (ev, for nq_vortex_profile: VX_PHASES + 1 events, ev[0] recorded by the caller; ev[k + 1] closes phase k: range, rows, merge,
+// flatten + prefix + rank, sums + finish)
+constexpr int VX_PHASES = 5;
+static void vx_census_launch(hipStream_t s, const VxPlanes& pl, int mode, double thr, int conn, int cap, const VxBufs& b, hipEvent_t* ev = nullptr) {
+  const int ncols = VX_BASE_COLS + pl.nf, rows = pl.rows, cols = pl.cols;
+  vx_range_launch(s, pl, b);
+  if (ev) (void)hipEventRecord(ev[1], s);
+  hipLaunchKernelGGL(k_vx_rows, dim3(rows), dim3(VX_THREADS), 0, s, pl, mode, thr, b.L);
+  if (ev) (void)hipEventRecord(ev[2], s);
+  hipLaunchKernelGGL(k_vx_merge, dim3(rows), dim3(VX_THREADS), 0, s, rows, cols, conn, b.L);
+  if (ev) (void)hipEventRecord(ev[3], s);
+  hipLaunchKernelGGL(k_vx_flatten, dim3(rows), dim3(VX_THREADS), 0, s, cols, b.L, b.rowroots, b.rowset);
+  hipLaunchKernelGGL(k_vx_prefix, dim3(1), dim3(VX_THREADS), 0, s, rows, cap, (const int*)b.rowroots, (const int*)b.rowset, b.rowoff, b.info);
+  hipLaunchKernelGGL(k_vx_rank, dim3(rows), dim3(VX_THREADS), 0, s, cols, cap, ncols, (const int*)b.L, (const int*)b.rowoff, b.R, b.tab);
+  if (ev) (void)hipEventRecord(ev[4], s);
+  hipLaunchKernelGGL(k_vx_sums, dim3(rows), dim3(VX_THREADS), 0, s, pl, cap, ncols, (const int*)b.L, (const int*)b.R, (const VxRange*)b.rng, b.tab);
+  const int fin = (cap + VX_THREADS - 1) / VX_THREADS;
+  hipLaunchKernelGGL(k_vx_finish, dim3(fin < 1024 ? fin : 1024), dim3(VX_THREADS), 0, s, ncols, (const long long*)b.info, b.tab);
+  if (ev) (void)hipEventRecord(ev[5], s);
+}
+// the fields of a call (real fields only) and the state: nq_structure2's checks without NQ_SF_PHI
+static int vx_check_fields(nq_ctx* c, const char* fn, int nfields, const int* fields) {
+  if (!fields || nfields < 1 || nfields > VX_MAX_FIELDS) NQ_FAIL(c, -1, "%s: %d fields (1 to %d)", fn, nfields, VX_MAX_FIELDS);
+  for (int i = 0; i < nfields; ++i) {
+    if (fields[i] == NQ_SF_PHI) NQ_FAIL(c, -1, "%s: NQ_SF_PHI is complex: a census thresholds and sums real fields (NQ_PDF_PHI2 is |phi|^2; DESIGN.md section 7)", fn);
+    if (is_flow(fields[i]) && !c->kernel_family)
+      NQ_FAIL(c, -1, "%s: field %d (NQ_FLOW_*) on a QGModel context: its plane route has q and its passive scalar only (DESIGN.md section 7)", fn, fields[i]);
+    if (!is_flow(fields[i]) && hist_slot(c, fields[i]) < 0)
+      NQ_FAIL(c, -1, "%s: field %d is not available here (Kernel family: NQ_PDF_Q, NQ_PDF_QPSI, NQ_PDF_PHI2 and the NQ_FLOW_* fields; QGModel: NQ_PDF_Q, with its passive scalar NQ_PDF_C)", fn, fields[i]);
+    for (int k = 0; k < i; ++k)
+      if (fields[k] == fields[i]) NQ_FAIL(c, -1, "%s: field %d listed twice", fn, fields[i]);
+  }
+  if (c->kernel_family ? !c->have_phi : !c->have_q) NQ_FAIL(c, -4, "%s: %s has not been called", fn, c->kernel_family ? "set_phi" : "set_q");
+  return 0;
+}
+// the feature's own buffers for this capacity: all of what is missing or too small, or none of it and -5 (the old buffers stay)
+// (cap = 0, a range call: the small buffers only.  The context's small buffers are two sets: the census's, then the range call's,
+// so that a range call leaves the scales and counts of the last census alone.)
+static int vx_reserve(nq_ctx* c, const char* fn, int cap) {
+  void** slot[3] = {&c->vx_planes, &c->vx_small, &c->vx_tab};
+  size_t* have[3] = {&c->vx_planes_bytes, &c->vx_small_bytes, &c->vx_tab_bytes};
+  const size_t need[3] = {cap ? vx_planes_bytes(c->N, c->N) : 0, 2 * vx_small_bytes(c->N), cap ? vx_tab_bytes(cap) : 0};
+  void* fresh[3] = {nullptr, nullptr, nullptr};
+  for (int i = 0; i < 3; ++i) {
+    if (need[i] <= *have[i]) continue;
+    if (hipMalloc(&fresh[i], need[i]) != hipSuccess) {
+      (void)hipGetLastError();
+      for (int k = 0; k < i; ++k)
+        if (fresh[k]) (void)hipFree(fresh[k]);
+      NQ_FAIL(c, -5, "%s: cannot allocate %zu bytes of device memory", fn, need[i]);
+    }
+  }
+  for (int i = 0; i < 3; ++i) {
+    if (!fresh[i]) continue;
+    if (*slot[i]) {
+      const int rc = nq_sync(c);                          // a launch of the last call may still use it
+      if (rc) {
+        for (int k = i; k < 3; ++k)
+          if (fresh[k]) (void)hipFree(fresh[k]);
+        return rc;
+      }
+      for (size_t k = 0; k < c->allocs.size(); ++k)
+        if (c->allocs[k] == *slot[i]) {
+          c->allocs.erase(c->allocs.begin() + k);
+          break;
+        }
+      (void)hipFree(*slot[i]);
+      c->bytes -= (long long)*have[i];
+      c->vx_cfg = nq_ctx::VxCfg();                        // what the old buffer held is gone
+    }
+    c->allocs.push_back(fresh[i]);
+    c->bytes += (long long)need[i];
+    *slot[i] = fresh[i];
+    *have[i] = need[i];
+  }
+  return 0;
+}
+static int vx_planes_for(nq_ctx* c, const char* fn, int nfields, const int* fields, int crit, VxPlanes* out) {
+  const bool cplx[SF_MAX_FIELDS] = {};
+  const int canon[SF_MAX_FIELDS] = {0, 1, 2};
+  SfPlanes sp = {};
+  const int rc = sf2_planes_of(c, fn, nfields, fields, cplx, canon, nfields, 0, &sp);
+  if (rc) return rc;
+  VxPlanes pl = {};
+  for (int i = 0; i < nfields; ++i) {
+    pl.p[i] = sp.p[i];
+    pl.stride[i] = sp.stride[i];
+  }
+  pl.nf = nfields;
+  pl.crit = crit;
+  pl.rows = sp.rows;
+  pl.cols = sp.cols;
+  *out = pl;
+  return 0;
+}
+
+int nq_vortex_range(nq_ctx* c, int nfields, const int* fields, double* out) {
+  static const char* fn = "nq_vortex_range";
+  NQ_SINGLE_RANK(c, "nq_vortex_range");
+  {
+    const int rc = vx_check_fields(c, fn, nfields, fields);
+    if (rc) return rc;
+  }
+  if (!out) NQ_FAIL(c, -1, "%s: null output", fn);
+  HIPCHK(c, hipSetDevice(c->device));
+  {
+    const int rc = vx_reserve(c, fn, 0);
+    if (rc) return rc;
+  }
+  VxPlanes pl;
+  {
+    const int rc = vx_planes_for(c, fn, nfields, fields, 0, &pl);
+    if (rc) return rc;
+  }
+  VxBufs b = vx_bufs(c->vx_small, static_cast<char*>(c->vx_small) + vx_small_bytes(c->N), nullptr, 0, 0);   // the second set
+  b.L = b.R = nullptr;                                    // a range call has no planes, table or per-row counts
+  b.rowroots = b.rowset = b.rowoff = nullptr;
+  vx_range_launch(c->stream, pl, b);
+  HIPCHK(c, hipGetLastError());
+  VxRange r;
+  HIPCHK(c, hipMemcpyAsync(&r, b.rng, sizeof(r), hipMemcpyDeviceToHost, c->stream));
+  {
+    const int rc = nq_sync(c);
+    if (rc) return rc;
+  }
+  for (int f = 0; f < nfields; ++f)
+    for (int k = 0; k < 4; ++k) out[4 * f + k] = r.v[f][k];
+  return 0;
+}
+
+static int vx_census(nq_ctx* c, const char* fn, int nfields, const int* fields, int crit, int mode, double threshold, int connectivity, int capacity, double* ms);
+int nq_vortex_census(nq_ctx* c, int nfields, const int* fields, int crit, int mode, double threshold, int connectivity, int capacity) {
+  NQ_SINGLE_RANK(c, "nq_vortex_census");
+  return vx_census(c, "nq_vortex_census", nfields, fields, crit, mode, threshold, connectivity, capacity, nullptr);
+}
+// the same census, synchronous, with device events between its phases: ms[0] the planes (store pass or QGModel's transforms), then
+// range, rows, merge, flatten + rank, sums
+int nq_vortex_profile(nq_ctx* c, int nfields, const int* fields, int crit, int mode, double threshold, int connectivity, int capacity, double* ms) {
+  NQ_SINGLE_RANK(c, "nq_vortex_profile");
+  if (!ms) NQ_FAIL(c, -1, "nq_vortex_profile: null output");
+  return vx_census(c, "nq_vortex_profile", nfields, fields, crit, mode, threshold, connectivity, capacity, ms);
+}
+static int vx_census(nq_ctx* c, const char* fn, int nfields, const int* fields, int crit, int mode, double threshold, int connectivity, int capacity, double* ms) {
+  {
+    const int rc = vx_check_fields(c, fn, nfields, fields);
+    if (rc) return rc;
+  }
+  if (const char* bad = vx_check_call(crit, nfields, mode, threshold, connectivity, capacity)) NQ_FAIL(c, -1, "%s: %s", fn, bad);
+  HIPCHK(c, hipSetDevice(c->device));
+  {
+    const int rc = vx_reserve(c, fn, capacity);
+    if (rc) return rc;
+  }
+  hipEvent_t ev[VX_PHASES + 2] = {};
+  int made = 0, rc = 0;
+  if (ms) {
+    while (made < VX_PHASES + 2 && hipEventCreate(&ev[made]) == hipSuccess) ++made;
+    if (made < VX_PHASES + 2 || hipEventRecord(ev[0], c->stream) != hipSuccess) {
+      (void)hipGetLastError();
+      rc = -5;
+    }
+  }
+  VxPlanes pl;
+  if (!rc) rc = vx_planes_for(c, fn, nfields, fields, crit, &pl);
+  if (!rc) {
+    if (ms) (void)hipEventRecord(ev[1], c->stream);
+    c->vx_cfg.census = false;
+    vx_census_launch(c->stream, pl, mode, threshold, connectivity, capacity, vx_bufs(c->vx_planes, c->vx_small, c->vx_tab, c->N, c->N), ms ? ev + 1 : nullptr);
+    if (hipGetLastError() != hipSuccess) rc = -5;
+  }
+  if (!rc) {
+    c->vx_cfg.nf = nfields;
+    c->vx_cfg.cap = capacity;
+    c->vx_cfg.census = true;
+    if (ms) rc = nq_sync(c);
+  }
+  if (ms) {
+    for (int i = 0; !rc && i <= VX_PHASES; ++i) {
+      float t = 0.f;
+      if (hipEventElapsedTime(&t, ev[i], ev[i + 1]) != hipSuccess) rc = -5;
+      ms[i] = t;
+    }
+    for (int i = 0; i < made; ++i) (void)hipEventDestroy(ev[i]);
+  }
+  if (rc == -5 && c->err.empty()) NQ_FAIL(c, -5, "%s: a launch or an event failed", fn);
+  return rc;
+}
+
+int nq_vortex_stats(nq_ctx* c, double* out) {
+  NQ_SINGLE_RANK(c, "nq_vortex_stats");
+  if (!out) NQ_FAIL(c, -1, "nq_vortex_stats: null output");
+  if (!c->vx_cfg.census) NQ_FAIL(c, -4, "nq_vortex_stats: no nq_vortex_census call yet");
+  HIPCHK(c, hipSetDevice(c->device));
+  VxRange r;
+  HIPCHK(c, hipMemcpyAsync(&r, vx_bufs(c->vx_planes, c->vx_small, c->vx_tab, c->N, c->N).rng, sizeof(r), hipMemcpyDeviceToHost, c->stream));
+  {
+    const int rc = nq_sync(c);
+    if (rc) return rc;
+  }
+  for (int f = 0; f < c->vx_cfg.nf; ++f)
+    for (int k = 0; k < 4; ++k) out[4 * f + k] = r.v[f][k];
+  return 0;
+}
+
+int nq_vortex_read(nq_ctx* c, long long* info, long long* table) {
+  NQ_SINGLE_RANK(c, "nq_vortex_read");
+  if (!info) NQ_FAIL(c, -1, "nq_vortex_read: null info");
+  if (!c->vx_cfg.census) NQ_FAIL(c, -4, "nq_vortex_read: no nq_vortex_census call yet");
+  HIPCHK(c, hipSetDevice(c->device));
+  const VxBufs b = vx_bufs(c->vx_planes, c->vx_small, c->vx_tab, c->N, c->N);
+  HIPCHK(c, hipMemcpyAsync(info, b.info, sizeof(long long) * VX_INFO, hipMemcpyDeviceToHost, c->stream));
+  {
+    const int rc = nq_sync(c);
+    if (rc) return rc;
+  }
+  if (table && info[1] > 0) {
+    HIPCHK(c, hipMemcpyAsync(table, b.tab, sizeof(long long) * (size_t)info[1] * (VX_BASE_COLS + c->vx_cfg.nf), hipMemcpyDeviceToHost, c->stream));
+    return nq_sync(c);
+  }
+  return 0;
+}
+
+int nq_vortex_labels(nq_ctx* c, int* out) {
+  NQ_SINGLE_RANK(c, "nq_vortex_labels");
+  if (!out) NQ_FAIL(c, -1, "nq_vortex_labels: null output");
+  if (!c->vx_cfg.census) NQ_FAIL(c, -4, "nq_vortex_labels: no nq_vortex_census call yet");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpyAsync(out, c->vx_planes, sizeof(int) * (size_t)c->N * c->N, hipMemcpyDeviceToHost, c->stream));
+  return nq_sync(c);
+}
+
 // ---- isotropic spectra of the diagnostics tick ----------------------------------------------------
 int nq_spectrum_shells(const nq_ctx* c) { return c ? nq_shell_count(c->N) : -1; }
 
@@ -7470,6 +7754,49 @@ int nq_any_increment_hist(nq_any* e, int nfields, const void* const* planes, con
   ANYCHK(e, hipGetLastError());
   ANYCHK(e, hipMemcpyAsync(out, tab, sizeof(unsigned long long) * words, hipMemcpyDeviceToHost, e->stream));
   return nq_any_sync(e);
+}
+// Vortex census on engine planes: nq_vortex_census's kernels on complex planes whose real parts are the fields
+int nq_any_components(nq_any* e, int nplanes, const void* const* planes, int rows, int cols, int crit, int mode, double threshold, int connectivity,
+                      int capacity, long long* info, long long* table, int* labels) {
+  if (!e || !planes || !info || !table) return -1;
+  if (nplanes < 1 || nplanes > VX_MAX_FIELDS) ANYFAIL(e, -1, "nq_any_components: %d planes (1 to %d)", nplanes, VX_MAX_FIELDS);
+  if (rows < 4 || cols < 4 || (rows & 1) || (cols & 1) || rows > VX_MAX_DIM || cols > VX_MAX_DIM)
+    ANYFAIL(e, -1, "nq_any_components: planes of %d x %d (even sizes from 4 to %d)", rows, cols, VX_MAX_DIM);
+  for (int i = 0; i < nplanes; ++i) {
+    if (!planes[i]) ANYFAIL(e, -1, "nq_any_components: plane %d is null", i);
+    for (int k = 0; k < i; ++k)
+      if (planes[k] == planes[i]) ANYFAIL(e, -1, "nq_any_components: plane %d listed twice", i);
+  }
+  if (const char* bad = vx_check_call(crit, nplanes, mode, threshold, connectivity, capacity)) ANYFAIL(e, -1, "nq_any_components: %s", bad);
+  ANYCHK(e, hipSetDevice(e->device));
+  AnyScratch tmp;
+  char *dplanes = nullptr, *dsmall = nullptr, *dtab = nullptr;
+  ANYCHK(e, tmp.get(&dplanes, vx_planes_bytes(rows, cols)));
+  ANYCHK(e, tmp.get(&dsmall, vx_small_bytes(rows)));
+  ANYCHK(e, tmp.get(&dtab, vx_tab_bytes(capacity)));
+  const VxBufs b = vx_bufs(dplanes, dsmall, dtab, rows, cols);
+  VxPlanes pl = {};
+  for (int i = 0; i < nplanes; ++i) {
+    pl.p[i] = reinterpret_cast<const double*>(planes[i]);
+    pl.stride[i] = 2;
+  }
+  pl.nf = nplanes;
+  pl.crit = crit;
+  pl.rows = rows;
+  pl.cols = cols;
+  vx_census_launch(e->stream, pl, mode, threshold, connectivity, capacity, b);
+  ANYCHK(e, hipGetLastError());
+  ANYCHK(e, hipMemcpyAsync(info, b.info, sizeof(long long) * VX_INFO, hipMemcpyDeviceToHost, e->stream));
+  if (labels) ANYCHK(e, hipMemcpyAsync(labels, b.L, sizeof(int) * (size_t)rows * cols, hipMemcpyDeviceToHost, e->stream));
+  {
+    const int rc = nq_any_sync(e);
+    if (rc) return rc;
+  }
+  if (info[1] > 0) {
+    ANYCHK(e, hipMemcpyAsync(table, b.tab, sizeof(long long) * (size_t)info[1] * (VX_BASE_COLS + nplanes), hipMemcpyDeviceToHost, e->stream));
+    return nq_any_sync(e);
+  }
+  return 0;
 }
 int nq_any_set_elem(nq_any* e, void* plane, long long index, double re, double im) {
   if (!e || !plane || index < 0) return -1;
